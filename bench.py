@@ -17,11 +17,16 @@ the weak-scaling rate (64 candidates per GPU) is measured in the same run and re
 Other workloads (their own metric strings; not the headline): `ddpmpp32_rejection` (configs[1]: DDPM++ CIFAR-32, rejection N=16,
 brightness) and `adm64_mcts` (configs[4]: ADM-64 MCTS, S rollouts per timestep, imagenet scorer; one step = one whole search).
 
-Prints ONE JSON line on rank 0 with, besides the contract fields: `roofline` (dominant kernel = the implicit-GEMM conv:
-algorithmic conv FLOPs / summed launch durations from HIP events attached to the kernel's own dispatch), `cpu_baseline` (the CPU
-oracle on this box's host cores, one iteration over the same 64 candidates), `parity` (GPU f32 / f16 / bf16 rewards and argmax
-against that oracle iteration on the SAME inputs, plus index agreement of the 16-bit modes over 8 more iterations) and
-`e2e_evals_per_s` (config 3 end to end through generate_image_grid, host RNG and uploads included).
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times exactly K steps and prints ONE JSON line on
+rank 0 with the contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step);
+the fields of the legs below are null there.  `--dump-outputs DIR` writes what the timed path computed in its last timed step as
+DIR/<name>.npy (float32 / float64): the same arguments give the same inputs, so two builds can be compared output for output.
+
+`--full` adds, after the timed steps: `roofline` (dominant kernel = the implicit-GEMM conv: algorithmic conv FLOPs / summed launch
+durations from HIP events attached to the kernel's own dispatch), `cpu_baseline` (the CPU oracle on this box's host cores, one
+iteration over the same 64 candidates), `parity` (GPU f32 / f16 / bf16 rewards and argmax against that oracle iteration on the SAME
+inputs, plus index agreement of the 16-bit modes), `e2e_evals_per_s` (config 3 end to end through generate_image_grid, host RNG and
+uploads included), `parity_modes`, `other_dtype`, `sub_records` and, on several ranks, `weak_value`.
 """
 import argparse
 import json
@@ -78,6 +83,28 @@ def log(msg):
         print(f'[bench +{time.perf_counter() - _T0:7.1f}s] {msg}', file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: `arrays` (name -> tensor / number) as d/<name>.npy, float64 where the path computed float64 (and for
+    indices, which it holds exactly), float32 otherwise; at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    import torch
+    out = {}
+    for name, v in arrays.items():
+        t = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        out[name] = t.to(torch.float64 if wide else torch.float32).numpy()
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(d, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(d, name + '.npy'), x)
+    log(f'outputs of the last timed step -> {d}: ' + ', '.join(f'{k}{list(x.shape)}' for k, x in out.items()))
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -101,10 +128,15 @@ def parse(argv=None):
     ap.add_argument('--conv-sequence', default=None, help='write the per-launch conv shape sequence of one step (JSON) for tools/pmc_traffic.py')
     ap.add_argument('--conv-table', action='store_true', help='log the per-shape conv launch table of the instrumented steps')
     ap.add_argument('--cpu-sample', type=int, default=64, help='candidates in the CPU-baseline / parity iteration')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure the roofline, CPU baseline, parity, end-to-end, other dtypes, '
+                    'sub-records and the weak-scaling leg (the --no-* flags trim these); without it the run times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the timed path computed in its last timed step as DIR/<name>.npy')
     a = ap.parse_args(argv)
     d_steps, d_warm = {'adm64_eps_greedy': (6, 2), 'ddpmpp32_rejection': (20, 3), 'adm64_mcts': (1, 0)}[a.workload]
     a.steps = d_steps if a.steps is None else a.steps
     a.warmup = d_warm if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if a.candidates is None:
         a.candidates = 16 if a.workload == 'ddpmpp32_rejection' else 64
     return a
@@ -448,13 +480,20 @@ class EpsGreedyIteration:
     def __call__(self, s):
         q = s % len(self.noise)
         cand = self.candidates(q, self.lo, self.hi)
-        _, x0 = self.L.step(self.x_cur, self.t_steps[self.i], self.t_steps[self.i + 1], self.i, cand, self.lab_l, nb=self.nl)
+        x_next, x0 = self.L.step(self.x_cur, self.t_steps[self.i], self.t_steps[self.i + 1], self.i, cand, self.lab_l, nb=self.nl)
         loc = self.L.score(self.scorer, x0, self.lab_l).to(self.job.dev, self.torch.float32)
         scores = self.shards.gather_rewards(loc, self.n_total, 1).cpu()
         best = int(scores.argmax())                                   # first max; identical on every rank
         self.pivot = self.candidates(q, best, best + 1)               # every rank rebuilds the survivor (edm/main.py:848-857)
         self.last_scores = scores
+        self.last_x_next, self.last_x0 = x_next, x0
         return best
+
+    def outputs(self):
+        """what the last call handed back (bench.py --dump-outputs): the rewards of all candidates, the selected index, the survivor
+        (new pivot) and this rank's candidates after the Heun step together with the denoised images that were scored"""
+        return {'rewards': self.last_scores, 'selected': int(self.last_scores.argmax()), 'pivot': self.pivot,
+                'x_next': self.last_x_next, 'denoised': self.last_x0}
 
 
 def scorer_dtype(dtype):
@@ -911,9 +950,11 @@ def run_eps_greedy(a, job):
     graph_replays = net._graphs.replays - replays0
     value = 2 * n_total * a.steps / dt
     log(f'timed region: {dt:.3f}s for {a.steps} steps -> {value:.1f} evals/s')
+    if a.dump_outputs and rank == 0:            # before anything below runs the iteration again
+        dump_outputs(a.dump_outputs, it.outputs())
 
     weak = None
-    if world > 1 and a.scaling == 'strong' and not a.no_weak:        # weak-scaling rate in the same run (64 candidates PER GPU)
+    if a.full and world > 1 and a.scaling == 'strong' and not a.no_weak:        # weak-scaling rate in the same run (64 candidates PER GPU)
         itw = EpsGreedyIteration(job, net, scorer, a.candidates * world)
         for s in range(3):
             itw(s)
@@ -923,7 +964,7 @@ def run_eps_greedy(a, job):
         log(f'weak-scaling leg: {weak:.1f} evals/s')
 
     roof = None
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         caches = [net._graphs] + ([scorer.model._graphs] if hasattr(scorer, 'model') else [])
         reps = min(2, a.steps)
         if rank == 0:
@@ -935,7 +976,7 @@ def run_eps_greedy(a, job):
     job.barrier()
 
     extra = {}
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         if not a.no_e2e and a.candidates == 64 and a.scorer == 'imagenet':
             extra.update(e2e_leg(job, net, scorer, dtype))
             log(f'end-to-end config 3: {extra["e2e_evals_per_s"]} evals/s')
@@ -1069,9 +1110,10 @@ def oracle_rejection32_step(n_total, seed=0):
                                                f'+ brightness score), fp32 torch-CPU oracle'}, float(sc.max())
 
 
-def rejection32_record(a, job, steps=None, warmup=None, cpu=True):
+def rejection32_record(a, job, steps=None, warmup=None, cpu=True, dump=None):
     """BASELINE configs[1]: DDPM++ CIFAR-32, rejection sampling over N=16 trajectories, brightness scorer.  One step = one Heun step
-    of the N trajectories (2*N candidate U-Net evaluations) + the score of the predicted images; sigma step 5, S_churn = 40."""
+    of the N trajectories (2*N candidate U-Net evaluations) + the score of the predicted images; sigma step 5, S_churn = 40.
+    dump: directory for the outputs of the last timed step (--dump-outputs)."""
     import torch
     from diffusion_tts_amd import init as dinit, ops
     from diffusion_tts_amd.config import ddpmpp_cifar10
@@ -1100,18 +1142,24 @@ def rejection32_record(a, job, steps=None, warmup=None, cpu=True):
     eps = [torch.randn(n_total, 3, 32, 32, generator=g, dtype=torch.float64)[lo:hi].to(dev).contiguous() for _ in range(4)]
     lab = torch.eye(10)[torch.tensor([3])].repeat(nl, 1).to(dev).contiguous()
 
+    last = {}
+
     def one_step(s):
         xn, _ = L.step(x, t_steps[5], t_steps[6], 5, eps[s % 4], lab, nb=nl)
         loc = L.score(scorer, xn, lab).to(dev, torch.float32)
-        return int(shards.gather_rewards(loc, n_total, 1).cpu().argmax())
+        rewards = shards.gather_rewards(loc, n_total, 1).cpu()
+        last.update(rewards=rewards, x_next=xn)
+        return int(rewards.argmax())
 
     for s in range(3):
         one_step(s)
     torch.cuda.synchronize(dev)
     dt = job.timed(one_step, steps, warmup)
     value = 2 * n_total * steps / dt
+    if dump and rank == 0:              # the rewards of all trajectories, the selected one and this rank's trajectories after the step
+        dump_outputs(dump, dict(rewards=last['rewards'], selected=int(last['rewards'].argmax()), x_next=last['x_next']))
     roof = None
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         if rank == 0:
             roof = conv_roofline(a, lambda s: one_step(s), min(2, steps), a.dtype, value / world, GFLOP_PER_EVAL['ddpmpp32'], [net._graphs])
         else:
@@ -1119,7 +1167,7 @@ def rejection32_record(a, job, steps=None, warmup=None, cpu=True):
                 one_step(s)
     job.barrier()
     cpu_rec = None
-    if cpu and rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and cpu and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu_rec, _ = oracle_rejection32_step(n_total)
     return {
         'metric': 'candidate U-Net steps/sec, EDM CIFAR-10 32x32 rejection N=16', 'value': round(value, 2),
@@ -1133,14 +1181,15 @@ def rejection32_record(a, job, steps=None, warmup=None, cpu=True):
 
 
 def run_rejection32(a, job):
-    rec = rejection32_record(a, job)
+    rec = rejection32_record(a, job, dump=a.dump_outputs)
     if job.rank == 0:
         print(json.dumps(rec), flush=True)
 
 
-def mcts_record(a, job, S, steps, warmup, built=None):
+def mcts_record(a, job, S, steps, warmup, built=None, dump=None):
     """BASELINE configs[4]: ADM-64 MCTS, S rollouts per timestep, imagenet scorer.  One step = one whole image search through
-    generate_image_grid (18 sigma steps; node expansions batched, ragged rollouts batched and sharded over the ranks)."""
+    generate_image_grid (18 sigma steps; node expansions batched, ragged rollouts batched and sharded over the ranks).
+    dump: directory for the outputs of the last timed search (--dump-outputs)."""
     import numpy as np
     import torch
     from diffusion_tts_amd.sampler import SamplingMethod, generate_image_grid
@@ -1155,14 +1204,18 @@ def mcts_record(a, job, S, steps, warmup, built=None):
                                    S_min=0.05, S_max=50, S_noise=1.003, sampling_method=SamplingMethod.MCTS,
                                    sampling_params=dict(scorer=scorer, N=a.mcts_children, S=S_), compute_dtype=dtype, verbose=False)
     search(min(S, 16), 0)                       # setup: kernel attributes, graph captures of the common batch sizes
-    rows = [0]
+    rows, last = [0], {}
 
     def one_step(s):
-        rows[0] += search(S, 1 + s)['net_rows']
+        res = search(S, 1 + s)
+        rows[0] += res['net_rows']
+        last.update(res)
     for s in range(warmup):
         one_step(s)
     rows[0] = 0
     dt = job.timed(one_step, steps, 0)
+    if dump and job.rank == 0:          # what generate_image_grid hands back: final state, image, its score
+        dump_outputs(dump, {k_: last[k_] for k_ in ('x', 'image', 'final_scores')})
     rows_total = rows[0]                        # rows of THIS rank; rollouts are sharded, expansions replicated
     if job.world > 1:
         t = torch.tensor([rows_total], dtype=torch.float64, device=job.dev if job.backend == 'nccl' else 'cpu')
@@ -1184,7 +1237,7 @@ def mcts_record(a, job, S, steps, warmup, built=None):
 
 
 def run_mcts(a, job):
-    rec = mcts_record(a, job, a.S, a.steps, a.warmup)
+    rec = mcts_record(a, job, a.S, a.steps, a.warmup, dump=a.dump_outputs)
     if job.rank == 0:
         print(json.dumps(rec), flush=True)
 

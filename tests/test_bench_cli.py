@@ -29,6 +29,30 @@ def test_launcher_builds_one_rank_per_gpu(monkeypatch):
     a = bench.parse([])
     assert (a.gpus, a.scaling, a.candidates, a.workload, a.cpu_sample) == (1, 'strong', 64, 'adm64_eps_greedy', 64)
     assert a.dtype == 'f16x3'            # the metric of record is measured in the mode that reproduces the reference's selections
+    assert a.full is False and a.dump_outputs is None          # a plain run times the steps and prints the line, nothing more
+    f = bench.parse(['--full', '--dump-outputs', 'out_dir', '--steps', '5', '--warmup', '0'])
+    assert (f.full, f.dump_outputs, f.steps, f.warmup) == (True, 'out_dir', 5, 0)
+
+
+def test_dump_outputs_writes_float32_or_float64_within_the_limit(tmp_path):
+    """--dump-outputs: float64 results stay float64, indices are written exactly (float64), other floats as float32; an
+    output set over the limit is an error before anything is written."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.randn(4, 3, 8, 8, dtype=torch.float64)
+    r = torch.rand(4, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / 'o'), {'x_next': x, 'rewards': r, 'selected': 3, 'image': torch.arange(6, dtype=torch.uint8)})
+    got = {p.stem: np.load(p) for p in (tmp_path / 'o').iterdir()}
+    assert sorted(got) == ['image', 'rewards', 'selected', 'x_next']
+    assert got['x_next'].dtype == np.float64 and np.array_equal(got['x_next'], x.numpy())
+    assert got['rewards'].dtype == np.float32 and np.array_equal(got['rewards'], r.numpy())
+    assert got['selected'].dtype == np.float64 and got['selected'] == 3.0
+    assert np.array_equal(got['image'], np.arange(6, dtype=np.float64))
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), {'a': torch.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1, dtype=torch.float64)})
+    assert not (tmp_path / 'big').exists()
 
 
 @pytest.mark.gpu
@@ -39,7 +63,7 @@ def test_two_ranks_started_by_the_bench_itself_shard_the_64_candidates():
     env = dict(os.environ, DTS_DIST_BACKEND='gloo')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-kernel-timing'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full', '--no-kernel-timing'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -57,7 +57,7 @@ out = {'dtype': d['dtype'], 'kernel': rp['kernel'], 'rocprofv3_avg_launch_us': r
        'ratio_rocprof_over_in_process': round(rp_us / r['avg_launch_us'], 4),
        'how': 'rocprofv3 --kernel-trace --stats of `bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-e2e --no-parity --no-subrecords` (same '
               'workload, same graphs; a profiled process runs a few per cent slower: MI355X_MICROARCH.md DVFS item 2); in-process = HIP events attached to the '
-              'kernel\'s own dispatch in the default bench.py run.  FLOPs are ALGORITHMIC (f16x3: x3 for the matrix work)'}
+              'kernel\'s own dispatch in the bench.py --full run.  FLOPs are ALGORITHMIC (f16x3: x3 for the matrix work)'}
 try:      # the SAME profiled process measured both ways (final_profiles.sh: final_prof_both)
     b = json.loads([l for l in open('gpurun_out/final_prof_both.json') if l.startswith('{')][-1])['roofline']
     import os

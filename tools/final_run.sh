@@ -10,12 +10,12 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; rm -rf $O/final_*
 DTS_TEST_SHARDED_FULLSIZE=1 timeout -k 10 1100 python -m pytest tests/ -m gpu -q --timeout 900 --durations=12 > $O/final_pytest.log 2>&1 || { tail -20 $O/final_pytest.log; exit 1; }
 tail -2 $O/final_pytest.log
-python bench.py --steps 10 --warmup 3 --conv-table --conv-sequence $O/final_conv_sequence.json > $O/final_bench.json 2> $O/final_bench.err || { tail -5 $O/final_bench.err; exit 1; }
+python bench.py --steps 10 --warmup 3 --full --conv-table --conv-sequence $O/final_conv_sequence.json > $O/final_bench.json 2> $O/final_bench.err || { tail -5 $O/final_bench.err; exit 1; }
 Q="--no-cpu-baseline --no-e2e --no-parity --no-subrecords"
-python bench.py --steps 20 --warmup 5 --dtype bf16 --conv-table --conv-sequence $O/final_conv_sequence_bf16.json $Q > $O/final_bench_bf16.json 2> $O/final_bench_bf16.err || exit 1
-python bench.py --steps 4 --warmup 1 --dtype f32 $Q > $O/final_bench_f32.json 2> $O/final_bench_f32.err || exit 1
+python bench.py --steps 20 --warmup 5 --dtype bf16 --full --conv-table --conv-sequence $O/final_conv_sequence_bf16.json $Q > $O/final_bench_bf16.json 2> $O/final_bench_bf16.err || exit 1
+python bench.py --steps 4 --warmup 1 --dtype f32 --full $Q > $O/final_bench_f32.json 2> $O/final_bench_f32.err || exit 1
 timeout -k 10 600 python bench.py --workload adm64_mcts --S 256 > $O/final_bench_mcts.json 2> $O/final_bench_mcts.err || exit 1
-DTS_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 6 --no-kernel-timing > $O/final_bench_2rank_gloo.json 2> $O/final_bench_2rank_gloo.err || exit 1
+DTS_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 6 --full --no-kernel-timing > $O/final_bench_2rank_gloo.json 2> $O/final_bench_2rank_gloo.err || exit 1
 DTS_SHARD_ALWAYS_COLLECT=1 NCCL_DEBUG=VERSION python bench.py --steps 6 --warmup 2 $Q --no-kernel-timing > $O/final_bench_rccl1.json 2> $O/final_bench_rccl1.err || exit 1
 NG=$(python -c "import torch; print(torch.cuda.device_count())")
 if [ "$NG" -ge 2 ]; then
@@ -27,7 +27,7 @@ if [ "$NG" -ge 2 ]; then
   tail -3 $O/final_pytest_rccl.log
   for n in 1 2 4 8; do
     [ "$n" -le "$NG" ] || continue
-    python bench.py --gpus $n --steps 10 --warmup 3 $Q > $O/final_scale_n$n.json 2> $O/final_scale_n$n.err || exit 1
+    python bench.py --gpus $n --steps 10 --warmup 3 --full $Q > $O/final_scale_n$n.json 2> $O/final_scale_n$n.err || exit 1
     python - "$O/final_scale_n$n.json" $n <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); n = int(sys.argv[2])
