@@ -521,6 +521,7 @@ static int gn_apply_impl(const void* x1, int c1, const void* x2, int c2, int dty
                          int w, int silu, int pool, bool split, dts_stream s, void* raw_out) {
   const int C = c1 + c2;
   DTS_CHECK_ARG(x1 && coef && out, "dts_gn_apply: null pointer");
+  DTS_CHECK_ARG(n > 0 && h > 0 && w > 0 && C > 0, "dts_gn_apply: n=%d h=%d w=%d C=%d", n, h, w, C);
   DTS_CHECK_ARG(c2 == 0 || x2, "dts_gn_apply: c2 without x2");
   const int epv = dtype == DTS_F32 ? 4 : 8;
   DTS_CHECK_ARG(c1 % epv == 0 && c2 % epv == 0, "dts_gn_apply: channels (%d,%d) unsupported", c1, c2);
