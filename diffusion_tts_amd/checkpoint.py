@@ -11,8 +11,9 @@ a stub that keeps `class_name` and `state`, the module tree is walked through th
 with the reference's own state-dict key names.  Globals are resolved through an exact (module, name) allow-list of data constructors; everything else is refused, and the
 nested storage bytes are read by torch's restricted (`weights_only`) loader.
 
-Scope = the hot path's nets: EDMPrecond over DhariwalUNet (ADM) or SongUNet with the DDPM++
-options; VP/VE/iDDPM preconditioners and NCSN++ options raise NotImplementedError.
+Scope = the hot path's nets: EDMPrecond over DhariwalUNet (ADM) or SongUNet with the DDPM++ or the NCSN++
+options (Fourier embedding, residual encoder, [1,3,3,1] resampling: the `*-ve.pkl` files); VP/VE/iDDPM preconditioners, the 'skip'
+encoder / decoder and any other resampling filter raise NotImplementedError.
 """
 import collections
 import io
@@ -143,8 +144,9 @@ _ADM_DEFAULTS = dict(model_channels=192, channel_mult=[1, 2, 3, 4], channel_mult
 _SONG_DEFAULTS = dict(model_channels=128, channel_mult=[1, 2, 2, 2], channel_mult_emb=4, num_blocks=4, attn_resolutions=[16],
                       augment_dim=0, embedding_type='positional', channel_mult_noise=1, encoder_type='standard',
                       decoder_type='standard', resample_filter=[1, 1])    # SongUNet.__init__, networks.py:230-249
-_DDPMPP_ONLY = dict(embedding_type='positional', channel_mult_noise=1, encoder_type='standard', decoder_type='standard',
-                    resample_filter=[1, 1])
+# what networks.EDMPrecond implements of them: DDPM++ = the first entry of each, NCSN++ = the second (edm/train.py:116-121)
+_SONG_SUPPORTED = dict(embedding_type=('positional', 'fourier'), encoder_type=('standard', 'residual'), decoder_type=('standard',),
+                       resample_filter=([1, 1], [1, 3, 3, 1]))
 
 
 def _config(net: Persisted) -> EDMConfig:
@@ -160,11 +162,15 @@ def _config(net: Persisted) -> EDMConfig:
     if recorded is None:
         raise ValueError('the pickled denoiser did not record its constructor arguments (persistence.py:106-108)')
     kw.update({k: v for k, v in dict(recorded).items() if k in kw})
+    extra = {}
     if not adm:
-        for k, v in _DDPMPP_ONLY.items():
-            if list(kw[k]) != list(v) if isinstance(v, list) else kw[k] != v:
-                raise NotImplementedError(f'SongUNet option {k}={kw[k]!r}: only the DDPM++ configuration is supported')
-    return EDMConfig(arch='adm' if adm else 'ddpmpp', img_resolution=int(st['img_resolution']), img_channels=int(st['img_channels']),
+        kw['resample_filter'] = [int(t) if float(t) == int(t) else float(t) for t in kw['resample_filter']]
+        for k, ok in _SONG_SUPPORTED.items():
+            if kw[k] not in ok:
+                raise NotImplementedError(f'SongUNet option {k}={kw[k]!r}: supported are {list(ok)}')
+        extra = dict(embedding_type=kw['embedding_type'], channel_mult_noise=int(kw['channel_mult_noise']), encoder_type=kw['encoder_type'],
+                     resample_filter=kw['resample_filter'])
+    return EDMConfig(**extra, arch='adm' if adm else 'ddpmpp', img_resolution=int(st['img_resolution']), img_channels=int(st['img_channels']),
                      label_dim=int(st['label_dim']), model_channels=int(kw['model_channels']), channel_mult=list(kw['channel_mult']),
                      channel_mult_emb=int(kw['channel_mult_emb']), num_blocks=int(kw['num_blocks']),
                      attn_resolutions=list(kw['attn_resolutions']), augment_dim=int(kw['augment_dim']),
@@ -190,4 +196,21 @@ def load_edm_pickle(source, key: str = 'ema') -> Tuple[EDMConfig, 'collections.O
     cfg = _config(net)
     sd = collections.OrderedDict()
     _flatten(net, '', sd)
+    _check_buffers(cfg, sd)
     return cfg, sd
+
+
+def _check_buffers(cfg, sd):
+    """The constructor arguments say which resampling filter the file was trained with; the up / down Conv2d layers carry the taps themselves
+    as `resample_filter` buffers (networks.py:64-66) and the forward uses THOSE.  A file whose buffers disagree with its arguments would be
+    computed with the wrong filter here, so it is refused; so is a Fourier-embedding network without its frequency buffer."""
+    from .init import resample_filter_2d
+    want = resample_filter_2d(cfg.resample_filter)
+    for k, v in sd.items():
+        if k.endswith('.resample_filter'):
+            if tuple(v.shape) != tuple(want.shape) or not torch.allclose(v.detach().float().cpu(), want, rtol=0, atol=1e-6):
+                raise NotImplementedError(f'{k} does not hold the resample_filter={list(cfg.resample_filter)} the constructor arguments record')
+    if cfg.embedding_type == 'fourier':
+        fr = sd.get('model.map_noise.freqs')
+        if fr is None or fr.numel() != cfg.noise_channels // 2:
+            raise ValueError(f'Fourier embedding: model.map_noise.freqs with {cfg.noise_channels // 2} values expected')

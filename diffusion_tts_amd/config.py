@@ -3,7 +3,7 @@
 The block enumeration follows the reference constructors so that parameter names and shapes are the
 reference's own state-dict keys:
   DhariwalUNet.__init__  edm/training/networks.py:373-433   (ADM, ImageNet-64)
-  SongUNet.__init__      edm/training/networks.py:230-318   (DDPM++ options only, CIFAR-10)
+  SongUNet.__init__      edm/training/networks.py:230-318   (DDPM++ and NCSN++ options; 'standard' decoder)
   EncoderUNetModel.__init__  edm/unet.py:708-870            (ImageNet-64 noisy classifier)
 """
 from dataclasses import dataclass, field
@@ -25,10 +25,25 @@ class EDMConfig:
     sigma_data: float = 0.5
     sigma_min: float = 0.0
     sigma_max: float = float('inf')
+    # SongUNet options (networks.py:245-249); the defaults are DDPM++'s, NCSN++ is 'fourier', 2, 'residual', [1, 3, 3, 1]
+    embedding_type: str = 'positional'      # 'positional' | 'fourier'
+    channel_mult_noise: int = 1
+    encoder_type: str = 'standard'          # 'standard' | 'residual'
+    resample_filter: List[int] = field(default_factory=lambda: [1, 1])
 
     @property
     def emb_channels(self):
         return self.model_channels * self.channel_mult_emb
+
+    @property
+    def noise_channels(self):
+        """width of the noise embedding = input width of map_layer0 / output width of map_label (SongUNet, networks.py:258)"""
+        return self.model_channels * (1 if self.arch == 'adm' else self.channel_mult_noise)
+
+    @property
+    def fir(self):
+        """True when up / down sampling uses the [1, 3, 3, 1] filter instead of the 2x2 box / nearest neighbour"""
+        return list(self.resample_filter) == [1, 3, 3, 1]
 
 
 def adm_imagenet64(label_dim=1000) -> EDMConfig:
@@ -41,10 +56,23 @@ def ddpmpp_cifar10(label_dim=10) -> EDMConfig:
     return EDMConfig('ddpmpp', 32, 3, label_dim, 128, [2, 2, 2], 4, 4, [16], 9)
 
 
+_NCSNPP = dict(embedding_type='fourier', channel_mult_noise=2, encoder_type='residual', resample_filter=[1, 3, 3, 1])
+
+
+def ncsnpp_cifar10(label_dim=10) -> EDMConfig:
+    """edm/train.py:119-121,146-147 defaults for --arch=ncsnpp: the network of the published `edm-cifar10-32x32-*-ve.pkl` files."""
+    return EDMConfig('ddpmpp', 32, 3, label_dim, 128, [2, 2, 2], 4, 4, [16], 9, **_NCSNPP)
+
+
+def ncsnpp_ffhq64() -> EDMConfig:
+    """--arch=ncsnpp --cres=1,2,2,2 at 64x64, unconditional: the network of `edm-ffhq-64x64-uncond-ve.pkl` / `edm-afhqv2-64x64-uncond-ve.pkl`."""
+    return EDMConfig('ddpmpp', 64, 3, 0, 128, [1, 2, 2, 2], 4, 4, [16], 9, **_NCSNPP)
+
+
 @dataclass
 class Block:
     name: str
-    kind: str                 # 'conv' | 'block'
+    kind: str                 # 'conv' | 'block' | 'aux_residual' (the residual encoder's fused-resample 3x3 conv, networks.py:290-292)
     cin: int
     cout: int
     res_in: int
@@ -60,7 +88,7 @@ def edm_blocks(cfg: EDMConfig):
     mc = cfg.model_channels
     enc: List[Block] = []
     dec: List[Block] = []
-    c = cfg.img_channels
+    c = caux = cfg.img_channels
     nlev = len(cfg.channel_mult)
     for lvl, mult in enumerate(cfg.channel_mult):
         r = cfg.img_resolution >> lvl
@@ -70,13 +98,16 @@ def edm_blocks(cfg: EDMConfig):
             c = c0
         else:
             enc.append(Block(f'enc.{r}x{r}_down', 'block', c, c, 2 * r, r, down=True))
+            if not adm and cfg.encoder_type == 'residual':
+                enc.append(Block(f'enc.{r}x{r}_aux_residual', 'aux_residual', caux, c, 2 * r, r, down=True))
+                caux = c
         for j in range(cfg.num_blocks):
             co = mc * mult
             att = r in cfg.attn_resolutions
             heads = (co // 64 if adm else 1) if att else 0
             enc.append(Block(f'enc.{r}x{r}_block{j}', 'block', c, co, r, r, heads=heads))
             c = co
-    stack = [b.cout for b in enc]
+    stack = [b.cout for b in enc if b.kind != 'aux_residual']            # networks.py:298
     for lvl in range(nlev - 1, -1, -1):
         mult = cfg.channel_mult[lvl]
         r = cfg.img_resolution >> lvl

@@ -39,18 +39,28 @@ class _Builder:
         if bias:
             self.sd[f'{name}.bias'] = _winit([fout], mode, fin, fout) * b
 
-    def conv(self, name, cin, cout, k, mode='kaiming_normal', w=1, b=0):
-        if not k:
-            return
-        self.sd[f'{name}.weight'] = _winit([cout, cin, k, k], mode, cin * k * k, cout * k * k) * w
-        self.sd[f'{name}.bias'] = _winit([cout], mode, cin * k * k, cout * k * k) * b
+    def conv(self, name, cin, cout, k, mode='kaiming_normal', w=1, b=0, resample_filter=None):
+        if k:
+            self.sd[f'{name}.weight'] = _winit([cout, cin, k, k], mode, cin * k * k, cout * k * k) * w
+            self.sd[f'{name}.bias'] = _winit([cout], mode, cin * k * k, cout * k * k) * b
+        if resample_filter is not None:            # the buffer of an up / down Conv2d (networks.py:64-66), after its parameters
+            self.sd[f'{name}.resample_filter'] = resample_filter_2d(resample_filter)
 
     def norm(self, name, c):
         self.sd[f'{name}.weight'] = torch.ones(c)
         self.sd[f'{name}.bias'] = torch.zeros(c)
 
 
+def resample_filter_2d(taps):
+    """the `resample_filter` buffer of a reference Conv2d (networks.py:64-65): outer(f, f) / sum(f)^2, float32 [1, 1, k, k]"""
+    f = torch.as_tensor(list(taps), dtype=torch.float32)
+    return f.ger(f).unsqueeze(0).unsqueeze(1) / f.sum().square()
+
+
 def edm_state_dict(cfg: EDMConfig, seed: int = 0, prefix: str = 'model.'):
+    """Parameters of the reference constructor, draw for draw.  With the NCSN++ options the buffers travel too, in state_dict() order: the
+    Fourier embedding's `map_noise.freqs` is a random draw the network needs (networks.py:215), and the [1, 3, 3, 1] `resample_filter`s are
+    what checkpoint.load_edm_pickle checks a file's filter by.  (The DDPM++ dict keeps its historical form: parameters only.)"""
     torch.manual_seed(seed)
     adm = cfg.arch == 'adm'
     mc, emb = cfg.model_channels, cfg.emb_channels
@@ -69,26 +79,34 @@ def edm_state_dict(cfg: EDMConfig, seed: int = 0, prefix: str = 'model.'):
         init = dict(mode='xavier_uniform', w=1, b=0)
         zero = dict(mode='xavier_uniform', w=1e-5, b=0)
         attn = dict(mode='xavier_uniform', w=np.sqrt(0.2), b=0)
+        nc = cfg.noise_channels
+        if cfg.embedding_type == 'fourier':
+            B.sd['map_noise.freqs'] = torch.randn(nc // 2) * 16         # FourierEmbedding.__init__, networks.py:213-215
         if cfg.label_dim:
-            B.linear('map_label', cfg.label_dim, mc, **init)
+            B.linear('map_label', cfg.label_dim, nc, **init)
         if cfg.augment_dim:
-            B.linear('map_augment', cfg.augment_dim, mc, bias=False, **init)
-        B.linear('map_layer0', mc, emb, **init)
+            B.linear('map_augment', cfg.augment_dim, nc, bias=False, **init)
+        B.linear('map_layer0', nc, emb, **init)
         B.linear('map_layer1', emb, emb, **init)
     enc, dec, cfin = edm_blocks(cfg)
+    filt = list(cfg.resample_filter) if cfg.fir else None
     for blk in enc + dec:
         n = blk.name
+        rf = filt if (blk.up or blk.down) else None
         if blk.kind == 'conv':
             B.conv(n, blk.cin, blk.cout, 3, **init)
             continue
+        if blk.kind == 'aux_residual':
+            B.conv(n, blk.cin, blk.cout, 3, resample_filter=rf, **init)
+            continue
         B.norm(f'{n}.norm0', blk.cin)
-        B.conv(f'{n}.conv0', blk.cin, blk.cout, 3, **init)
+        B.conv(f'{n}.conv0', blk.cin, blk.cout, 3, resample_filter=rf, **init)
         B.linear(f'{n}.affine', emb, blk.cout * (2 if adm else 1), **init)
         B.norm(f'{n}.norm1', blk.cout)
         B.conv(f'{n}.conv1', blk.cout, blk.cout, 3, **zero)
         if blk.cin != blk.cout or blk.up or blk.down:
             k = 1 if ((not adm) or blk.cin != blk.cout) else 0      # resample_proj=True only for SongUNet
-            B.conv(f'{n}.skip', blk.cin, blk.cout, k, **init)
+            B.conv(f'{n}.skip', blk.cin, blk.cout, k, resample_filter=rf, **init)
         if blk.heads:
             B.norm(f'{n}.norm2', blk.cout)
             B.conv(f'{n}.qkv', blk.cout, blk.cout * 3, 1, **attn)

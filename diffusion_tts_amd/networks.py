@@ -11,6 +11,12 @@ Activations are NHWC in `dtype`.  Compute modes: ops.F16X3 (DEFAULT: split preci
 results -- same selected candidates as the reference's fp32 run, networks.py:658 on a CPU), float32 (parity mode on the f32 matrix
 instruction), bfloat16 / float16 (throughput modes: another sample after the first near-tied pick).
 
+NCSN++ (SongUNet with embedding_type='fourier', encoder_type='residual', resample_filter=[1,3,3,1]; the `*-ve.pkl` checkpoints) differs in
+three places: the noise embedding reads the checkpoint's frequency buffer; up / down blocks resample with the [1,3,3,1] filter, a pass of its
+own between the norm and conv0 and in front of the 1x1 skip conv (dts_resample_fir) instead of the pool inside gn_apply / the nearest-neighbour
+gather inside the conv; and after every down block the residual encoder's `x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2)` is
+space-to-depth + ONE conv launch (ops.fused_down_weight).  The ADM and DDPM++ sequences are untouched by those branches.
+
 Per UNetBlock (networks.py:166-187) the launch sequence is
   gn_coef+gn_apply(SiLU, [2x2 pool]) -> conv0 [fused nearest-up gather] -> gn_coef(+scale/shift)+gn_apply(SiLU)
   -> [1x1 skip conv | resample] -> conv1 (+residual, *skip_scale)
@@ -41,7 +47,7 @@ class _BlockParams:
 
 
 class EDMPrecond:
-    """EDMPrecond + DhariwalUNet / SongUNet(DDPM++) forward on MI355X."""
+    """EDMPrecond + DhariwalUNet / SongUNet(DDPM++ or NCSN++) forward on MI355X."""
 
     def __init__(self, cfg: EDMConfig, state_dict: Dict[str, torch.Tensor], device='cuda', dtype=ops.F16X3):
         if not torch.cuda.is_available():
@@ -57,6 +63,12 @@ class EDMPrecond:
         self.adm = cfg.arch == 'adm'
         self.eps = 1e-5 if self.adm else 1e-6
         self.skip_scale = 1.0 if self.adm else math.sqrt(0.5)
+        if not self.adm:
+            if cfg.embedding_type not in ('positional', 'fourier') or cfg.encoder_type not in ('standard', 'residual') \
+                    or list(cfg.resample_filter) not in ([1, 1], [1, 3, 3, 1]):
+                raise NotImplementedError(f'SongUNet options embedding_type={cfg.embedding_type!r}, encoder_type={cfg.encoder_type!r}, '
+                                          f'resample_filter={cfg.resample_filter!r}')
+        self.fir = (not self.adm) and cfg.fir            # resampling with [1,3,3,1] (a pass of its own) instead of the 2x2 box / nearest gather
         self.evals = 0                               # rows pushed through the denoiser (BASELINE metric unit)
         # GroupNorm apply inside the consuming 3x3 conv (built, bit-identical, tested) -- OFF by default: measured slower than the
         # separate apply pass (profiles/r02_gn_fusion.txt); DTS_GN_FUSE=1 turns it on
@@ -80,10 +92,19 @@ class EDMPrecond:
         if cfg.label_dim:
             self.label_w = f(sd['map_label.weight'])
             self.label_b = f(sd['map_label.bias']) if 'map_label.bias' in sd else None
-        half = mc // 2
-        freqs = torch.arange(0, half, dtype=torch.float32)
-        freqs = freqs / (half - (0 if self.adm else 1))           # endpoint=True for DDPM++ (networks.py:269)
-        self.freqs = ((1 / 10000) ** freqs).to(dev)
+        if not self.adm and cfg.embedding_type == 'fourier':
+            # FourierEmbedding (networks.py:212-220): the frequencies are a buffer of the checkpoint; 2*pi*freqs in float32 on the host, the
+            # reference's own expression, so the device multiplies c_noise by bit-identical factors
+            if 'map_noise.freqs' not in sd:
+                raise KeyError('map_noise.freqs: a Fourier-embedding network carries its frequencies in the state dict')
+            self.freqs = (2 * np.pi * sd['map_noise.freqs'].detach().to('cpu', torch.float32)).to(dev).contiguous()
+            if self.freqs.numel() != cfg.noise_channels // 2:
+                raise ValueError(f'map_noise.freqs has {self.freqs.numel()} entries, expected {cfg.noise_channels // 2}')
+        else:
+            half = mc // 2
+            freqs = torch.arange(0, half, dtype=torch.float32)
+            freqs = freqs / (half - (0 if self.adm else 1))           # endpoint=True for DDPM++ (networks.py:269)
+            self.freqs = ((1 / 10000) ** freqs).to(dev)
         enc, dec, cfin = edm_blocks(cfg)
         self.enc, self.dec = enc, dec
         first = enc[0]
@@ -94,6 +115,13 @@ class EDMPrecond:
             P = _BlockParams()
             n = b.name
             g = lambda k: sd[f'{n}.{k}']
+            if b.kind == 'aux_residual':
+                # the fused-resample 3x3 conv (networks.py:78-80) as a 3x3 conv over the space-to-depth image: composed once, here
+                P.cpad = -(-4 * b.cin // ops.conv_cin_granule(dt)) * ops.conv_cin_granule(dt)
+                P.w = ops.pack_conv_weight(ops.fused_down_weight(f(g('weight')), list(cfg.resample_filter), cpad=P.cpad), dt)
+                P.b = f(g('bias'))
+                self.blocks[n] = P
+                continue
             P.g0, P.b0 = f(g('norm0.weight')), f(g('norm0.bias'))
             P.w0, P.cb0 = ops.pack_conv_weight(f(g('conv0.weight')), dt), f(g('conv0.bias'))
             caff = b.cout * (2 if self.adm else 1)
@@ -176,7 +204,17 @@ class EDMPrecond:
         ss = aff[:, P.aff_off:P.aff_off + P.caff]
         bnc = None if self.adm else ss
         skip_src = None
-        if self.fuse_gn and not b.down and ops.conv_fuses_gn(x1, P.w0, x2=x2, up=b.up):
+        fir = self.fir and (b.up or b.down)
+        up = b.up and not fir                         # the conv's own nearest-neighbour gather: the [1,1] filter only
+        if fir:
+            # NCSN++ up / down block: silu(norm0(x)) and the raw block input each go through the [1,3,3,1] pass (networks.py:82-85), which in
+            # split-precision mode writes the operand images conv0 and the 1x1 skip conv read
+            h = ops.group_norm(x1, G(b.cin), self.eps, P.g0, P.b0, x2=x2, silu=True)
+            h = ops.conv2d(ops.resample_fir(h, b.up, split_out=self.x3), P.w0, P.cb0, bias_nc=bnc, gn_stats=True)
+            if x2 is not None:
+                raise NotImplementedError('a resampling block with a concatenated input')
+            skip_src = ops.resample_fir(x1, b.up, split_out=self.x3)
+        elif self.fuse_gn and not b.down and ops.conv_fuses_gn(x1, P.w0, x2=x2, up=b.up):
             # norm0 + SiLU applied inside conv0 on its staged input tile: the normalised (and, in the decoder, concatenated) tensor
             # is never written (networks.py:168)
             coef = ops.gn_coefficients(x1, G(b.cin), self.eps, P.g0, P.b0, x2=x2)
@@ -194,11 +232,11 @@ class EDMPrecond:
             coef1 = ops.gn_coefficients(h, G(b.cout), self.eps, P.g1, P.b1, scale_shift=ss if self.adm else None)
         else:
             h = ops.group_norm(h, G(b.cout), self.eps, P.g1, P.b1, scale_shift=ss if self.adm else None, silu=True, split_out=self.x3)
-        if P.skip_w is not None and skip_src is not None and ops.conv_folds_skip(h, P.w1, (skip_src, P.skip_w, b.up)):
+        if P.skip_w is not None and skip_src is not None and ops.conv_folds_skip(h, P.w1, (skip_src, P.skip_w, up)):
             # split-precision mode: the 1x1 skip convolution is a second K loop of conv1's launch (no f32 skip tensor written and read back)
             sk = None
         elif P.skip_w is not None and skip_src is not None:
-            sk = ops.conv2d(skip_src, P.skip_w, P.skip_b, up=b.up)
+            sk = ops.conv2d(skip_src, P.skip_w, P.skip_b, up=up)
         elif P.skip_w is not None:
             src1, src2 = (ops.resample2x(x1, up=False), None) if b.down else (x1, x2)
             sk = ops.conv2d(src1, P.skip_w, P.skip_b, x2=src2, up=b.up)
@@ -207,7 +245,7 @@ class EDMPrecond:
         else:
             sk = x1
         if sk is None:
-            x = ops.conv2d(h, P.w1, P.cb1_skip, skip=(skip_src, P.skip_w, b.up), out_scale=self.skip_scale, gn_stats=True)
+            x = ops.conv2d(h, P.w1, P.cb1_skip, skip=(skip_src, P.skip_w, up), out_scale=self.skip_scale, gn_stats=True)
         else:
             x = ops.conv2d(h, P.w1, P.cb1, residual=sk, out_scale=self.skip_scale, gn_stats=True,
                            gn_coef=coef1 if fuse1 else None, gn_silu=True)
@@ -232,7 +270,17 @@ class EDMPrecond:
         aff = ops.conv2d(e.view(1, n, 1, -1), self.aff_w, self.aff_b).view(n, self.aff_total)
         x = ops.conv_in3(xin, self.conv_in_w, self.conv_in_b, self.enc[0].cout, self.act_dtype)
         skips = [x]
+        aux, aux_nchw = xin, True                     # the residual encoder's second stream starts as the U-Net input (networks.py:336)
         for b in self.enc[1:]:
+            if b.kind == 'aux_residual':
+                # x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2)  (networks.py:342-343): space-to-depth, then one conv launch that
+                # adds the down block's output, scales, and emits the strip statistics of the next norm0
+                P = self.blocks[b.name]
+                s2d = ops.space_to_depth2(aux, self.dtype, nchw=aux_nchw, cpad=P.cpad)
+                x = ops.conv2d(s2d, P.w, P.b, residual=x, out_scale=math.sqrt(0.5), gn_stats=True)
+                skips[-1] = aux = x
+                aux_nchw = False
+                continue
             x = self._block(b, x, None, aff)
             skips.append(x)
         for b in self.dec:

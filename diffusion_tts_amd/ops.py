@@ -421,6 +421,71 @@ def resample2x(x, up):
     return out
 
 
+FIR_TAPS = (1, 3, 3, 1)       # the NCSN++ resampling filter (SongUNet resample_filter=[1,3,3,1]); per axis, before normalisation
+
+
+def resample_fir(x, up, split_out=False):
+    """2x down / up sampling with the [1,3,3,1] filter (dts_resample_fir): conv2d(x, F, stride 2, padding 1) / conv_transpose2d(x, 4F, stride 2,
+    padding 1) per channel, F = outer(k, k) / 64.  split_out (float32 input): the result leaves as a split-precision convolution's operand (SplitAct)."""
+    n, h, w, c = x.shape
+    ho, wo = (2 * h, 2 * w) if up else (h // 2, w // 2)
+    if split_out:
+        out = torch.empty((n, ho, wo, 2 * c), dtype=torch.float16, device=x.device)
+        _call('dts_resample_fir', _ptr(x, 'x', torch.float32), _ptr(out), L.DTS_F32, n, h, w, c, int(up), 1)
+        return SplitAct(out, c)
+    out = torch.empty((n, ho, wo, c), dtype=x.dtype, device=x.device)
+    _call('dts_resample_fir', _ptr(x), _ptr(out), dt_code(x.dtype), n, h, w, c, int(up), 0)
+    return out
+
+
+def conv_cin_granule(dtype):
+    """input channels of dts_conv2d come in multiples of this, per compute mode (one K step)"""
+    return 32 if dtype in (F16X3, torch.float32) else 64
+
+
+def space_to_depth2(x, dtype, nchw=False, cpad=None):
+    """[n, h, w, c] activations (or, nchw=True, the float32 [n, c, h, w] image) -> [n, h/2, w/2, cpad]: channel (ry*2 + rx)*c + ci of output
+    pixel (i, j) is input pixel (2i+ry, 2j+rx), channel ci; channels beyond 4c are zero (cpad defaults to 4c rounded up to the convolution's
+    granularity in compute mode `dtype`).  In the split-precision mode the result is a SplitAct.  The operand of a fused_down_weight()."""
+    if nchw:
+        n, c, h, w = x.shape
+    else:
+        n, h, w, c = x.shape
+    g = conv_cin_granule(dtype)
+    cpad = -(-4 * c // g) * g if cpad is None else cpad
+    x3, adt = dtype == F16X3, act_dtype(dtype)
+    if x.dtype != (torch.float32 if nchw else adt):
+        raise ValueError(f'space_to_depth2: input dtype {x.dtype} in compute mode {dtype_name(dtype)}')
+    out = torch.empty((n, h // 2, w // 2, 2 * cpad if x3 else cpad), dtype=torch.float16 if x3 else adt, device=x.device)
+    _call('dts_space_to_depth2', _ptr(x), int(nchw), _ptr(out), dt_code(adt), n, h, w, c, cpad, int(x3))
+    return SplitAct(out, cpad) if x3 else out
+
+
+def fused_down_weight(w, taps=FIR_TAPS, cpad=None, out_dtype=torch.float32):
+    """The weight of Conv2d(kernel=3, down=True, fused_resample=True) (networks.py:78-80: conv2d(x, w, padding=2), then the depthwise filter
+    F = outer(k, k) / sum(k)^2 at stride 2 without padding) as ONE 3x3 padding-1 convolution over space_to_depth2(x).
+
+    The two linear steps compose into a 6x6 stride-2 padding-2 convolution, W6[o,c,u,v] = sum_{a,b} F[a,b] w[o,c,u-a,v-b]; with u = 2t + r its
+    taps fall on the 2x2 phases r of the pixel blocks t - 1 .. t + 1, i.e. a 3x3 convolution of the 4c channels (ry, rx, c).  Composed in
+    float64 from the float32 weight, rounded once to `out_dtype`.  w: [O, C, 3, 3] (any device) -> [O, cpad or 4C, 3, 3] on w's device."""
+    O, Cin, kh, kw = w.shape
+    if (kh, kw) != (3, 3) or len(taps) != 4:
+        raise ValueError('fused_down_weight: a 3x3 weight and a 4-tap filter')
+    k = torch.tensor(list(taps), dtype=torch.float64, device=w.device)
+    F2 = torch.outer(k, k) / k.sum() ** 2
+    w64 = w.detach().to(torch.float64)
+    w6 = torch.zeros((O, Cin, 6, 6), dtype=torch.float64, device=w.device)
+    for a in range(4):
+        for b in range(4):
+            w6[:, :, a:a + 3, b:b + 3] += F2[a, b] * w64
+    # [O, C, ty, ry, tx, rx] -> [O, ry, rx, C, ty, tx]
+    w3 = w6.view(O, Cin, 3, 2, 3, 2).permute(0, 3, 5, 1, 2, 4).reshape(O, 4 * Cin, 3, 3)
+    cpad = 4 * Cin if cpad is None else cpad
+    out = torch.zeros((O, cpad, 3, 3), dtype=out_dtype, device=w.device)
+    out[:, :4 * Cin] = w3.to(out_dtype)
+    return out
+
+
 # ---- attention ----------------------------------------------------------------------------------
 def attention(qkv, heads, scale, x3=False, split_out=False):
     """qkv [n, t, 3*heads*d] (q|k|v blocks) -> [n, t, heads*d].  x3 (split-precision mode, float32 qkv or a SplitQKV, head dim 64): Q.K^T and

@@ -51,15 +51,19 @@ def load_network(spec, device='cuda', dtype=ops.F16X3):
     (edm/main.py:69-70); URLs cannot be fetched here, so accepted forms are: a ready network object; the local path of
     an EDM network pickle (`*.pkl`, read by checkpoint.load_edm_pickle without executing its embedded source); a
     torch-saved dict {'cfg': EDMConfig kwargs, 'state_dict': {...reference keys...}}; or 'random:<preset>[:seed]'
-    with preset in {adm_imagenet64, ddpmpp_cifar10} (random init + the documented weight rule)."""
+    with preset in {adm_imagenet64, ddpmpp_cifar10, ncsnpp_cifar10, ncsnpp_ffhq64} (random init + the documented weight rule)."""
     from . import init as dinit
-    from .config import EDMConfig, adm_imagenet64, ddpmpp_cifar10
+    from .config import EDMConfig, adm_imagenet64, ddpmpp_cifar10, ncsnpp_cifar10, ncsnpp_ffhq64
     from .networks import EDMPrecond
     if callable(spec) and hasattr(spec, 'round_sigma'):
         return spec
     if isinstance(spec, str) and spec.startswith('random:'):
         parts = spec.split(':')
-        preset = {'adm_imagenet64': adm_imagenet64, 'ddpmpp_cifar10': ddpmpp_cifar10}[parts[1]]()
+        presets = {'adm_imagenet64': adm_imagenet64, 'ddpmpp_cifar10': ddpmpp_cifar10, 'ncsnpp_cifar10': ncsnpp_cifar10,
+                   'ncsnpp_ffhq64': ncsnpp_ffhq64}
+        if parts[1] not in presets:
+            raise ValueError(f'unknown preset {parts[1]!r}: one of {sorted(presets)}')
+        preset = presets[parts[1]]()
         seed = int(parts[2]) if len(parts) > 2 else 0
         sd, _ = dinit.refill_degenerate(dinit.edm_state_dict(preset, seed), seed)
         return EDMPrecond(preset, sd, device=device, dtype=dtype)

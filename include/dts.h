@@ -42,12 +42,13 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 111        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 112        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
                                      110: dts_candidate_noise_sd takes the three scalars of the reference's product separately (scale [n][3]);
-                                     111: dts_conv_args.skip_* (a block's 1x1 skip convolution folded into its second 3x3), dts_conv_folds_skip) */
+                                     111: dts_conv_args.skip_* (a block's 1x1 skip convolution folded into its second 3x3), dts_conv_folds_skip;
+                                     112: dts_resample_fir, dts_space_to_depth2 (the NCSN++ options of SongUNet)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -159,6 +160,19 @@ int dts_gn_fused(const void* x1, int c1, const void* x2, int c2, int dtype, int 
                  const float* gamma, const float* beta, const void* scale_shift, int ld_ss, void* out, int silu, dts_stream s);
 /* 2x resampling of an NHWC tensor for the skip path: mode 0 = 2x2 average (down), 1 = nearest (up). */
 int dts_resample2x(const void* x, void* out, int dtype, int n, int h, int w, int c, int mode, dts_stream s);
+/* The same resampling with the NCSN++ filter, resample_filter = [1,3,3,1] (networks.py:64-65,82-85), F = outer(k,k) / 64:
+ *   up = 0: out [n][h/2][w/2][c] = conv2d(x, F, stride 2, padding 1) per channel;
+ *   up = 1: out [n][2h][2w][c] = conv_transpose2d(x, 4F, stride 2, padding 1) per channel (per axis: 3/4 of the nearer source pixel, 1/4 of
+ *           the farther one); pixels outside the image count as zero.
+ * c a multiple of the 16-byte vector (4 f32 / 8 16-bit elements).  split_out = 1 (dtype DTS_F32, c % 32 == 0): `out` is the f16 split
+ * operand image [..][2*c] of the result (dts_split3_f16's arithmetic and layout), what dts_conv2d(dtype = DTS_F16X3) reads. */
+int dts_resample_fir(const void* x, void* out, int dtype, int n, int h, int w, int c, int up, int split_out, dts_stream s);
+/* out [n][h/2][w/2][cpad], out[..][i][j][(ry*2 + rx)*c + ci] = x[..][2i+ry][2j+rx][ci], channels 4c .. cpad-1 zero.  x is NHWC in `dtype`, or
+ * (x_nchw_f32 = 1) the f32 NCHW image at the U-Net's input.  With it the residual encoder's fused-resample convolution (networks.py:78-80,
+ * 290-292: 3x3 with padding 2, then F at stride 2 without padding) is ONE dts_conv2d: the two steps compose into a 6x6 stride-2 padding-2
+ * convolution, which over this rearrangement is a 3x3 padding-1 convolution of 4c channels (ops.fused_down_weight builds its weight).
+ * cpad >= 4c, a multiple of dts_conv2d's channel granularity; split_out as in dts_resample_fir (cpad % 32 == 0). */
+int dts_space_to_depth2(const void* x, int x_nchw_f32, void* out, int dtype, int n, int h, int w, int c, int cpad, int split_out, dts_stream s);
 
 /* ---- K6: fused self-attention (networks.py:113-118,181-185; unet.py:355-372,388-407) -------------- */
 /* qkv NHWC-flattened [n][t][3*heads*d] laid out q[heads][d] | k[heads][d] | v[heads][d];

@@ -9,8 +9,10 @@ Arguments (verbatim from the reference):
     --method    : naive | rejection | beam | mcts | zero_order | eps_greedy (default naive)
     --prompt, --output, --N, --lambda_, --eps, --K, --B, --S, --seed, --device
 Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is no network here):
-    --network   : 'random:adm_imagenet64[:seed]' (default), 'random:ddpmpp_cifar10[:seed]', the local path of an NVIDIA EDM
-                  network pickle (*.pkl, read without executing its embedded source), or a .pt bundle
+    --network   : 'random:adm_imagenet64[:seed]' (default), 'random:ddpmpp_cifar10[:seed]', 'random:ncsnpp_cifar10[:seed]',
+                  'random:ncsnpp_ffhq64[:seed]', the local path of an NVIDIA EDM network pickle (*.pkl, read without executing its
+                  embedded source: EDMPrecond over the ADM, DDPM++ or NCSN++ U-Net, i.e. the published edm-*-adm.pkl, edm-*-vp.pkl
+                  and edm-*-ve.pkl files), or a .pt bundle
     --dtype     : f16x3 (default: split precision on the 16-bit matrix cores -- the reference's fp32 rewards and therefore its selected
                   candidates on the same seed, ~2.6x the f32 mode's speed) | f32 (parity mode, f32 matrix instruction) | bf16 | f16
                   (throughput modes: ~2.8x faster again, but a near-tied pick differs after ~10 decisions and the result is another sample)
