@@ -253,3 +253,88 @@ def vae_decoder_state_dict(block_out_channels=(128, 256, 512, 512), layers_per_b
     norm('decoder.conv_norm_out', block_out_channels[0])
     conv('decoder.conv_out', 3, block_out_channels[0], 3)
     return sd
+
+
+def sd_unet_state_dict(block_out_channels=(320, 640, 1280, 1280), heads=8, cross_attention_dim=768, layers_per_block=2, seed=0):
+    """Random-init parameters of the SD-1.x U-Net under diffusers' key names and shapes (`UNet2DConditionModel.state_dict()`,
+    sd/diffusers/src/diffusers/models/unets/unet_2d_condition.py; 686 tensors at SD-1.5's size): BASELINE config 4 prescribes random-init
+    weights (SD-1.5's cannot be fetched).  Own seeded initialiser, fan-in scaled so that activations stay O(1) through the 22 residual and
+    16 transformer blocks.  The gains of the time-embedding path (time_embedding.*, time_emb_proj) and of the text path (attn2: peaked
+    softmax over the tokens, full-gain output projection) are raised so that the output DEPENDS on the timestep and on the context by
+    far more than a 16-bit pipeline's error -- a golden test could not otherwise tell a model that ignores them
+    (tests/golden/make_golden_sd_unet.py asserts the margins).  `heads`: diffusers' `attention_head_dim` of SD-1.x, i.e. the number of
+    heads of every transformer block.  Keys in construction order."""
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    boc = tuple(block_out_channels)
+    temb = 4 * boc[0]
+
+    def conv(key, cout, cin, k, gain=1.0):
+        sd[key + '.weight'] = torch.randn(cout, cin, k, k, generator=g) * (gain / math.sqrt(cin * k * k))
+        sd[key + '.bias'] = torch.randn(cout, generator=g) * 0.05
+
+    def lin(key, cout, cin, gain=1.0, bias=True):
+        sd[key + '.weight'] = torch.randn(cout, cin, generator=g) * (gain / math.sqrt(cin))
+        if bias:
+            sd[key + '.bias'] = torch.randn(cout, generator=g) * 0.05
+
+    def norm(key, c):
+        sd[key + '.weight'] = 1.0 + 0.1 * torch.randn(c, generator=g)
+        sd[key + '.bias'] = 0.1 * torch.randn(c, generator=g)
+
+    def resnet(key, cin, cout):
+        norm(key + '.norm1', cin); conv(key + '.conv1', cout, cin, 3)
+        lin(key + '.time_emb_proj', cout, temb, gain=1.5)
+        norm(key + '.norm2', cout); conv(key + '.conv2', cout, cout, 3, gain=0.5)
+        if cin != cout:
+            conv(key + '.conv_shortcut', cout, cin, 1)
+
+    def transformer(key, c):
+        norm(key + '.norm', c)
+        conv(key + '.proj_in', c, c, 1)
+        t = key + '.transformer_blocks.0'
+        norm(t + '.norm1', c)
+        for n in ('to_q', 'to_k', 'to_v'):
+            lin(f'{t}.attn1.{n}', c, c, bias=False)
+        lin(t + '.attn1.to_out.0', c, c, gain=0.5)
+        norm(t + '.norm2', c)
+        lin(t + '.attn2.to_q', c, c, gain=2.0, bias=False)
+        lin(t + '.attn2.to_k', c, cross_attention_dim, gain=2.0, bias=False)
+        lin(t + '.attn2.to_v', c, cross_attention_dim, bias=False)
+        lin(t + '.attn2.to_out.0', c, c, gain=1.0)
+        norm(t + '.norm3', c)
+        lin(t + '.ff.net.0.proj', 8 * c, c)
+        lin(t + '.ff.net.2', c, 4 * c, gain=0.5)
+        conv(key + '.proj_out', c, c, 1, gain=0.5)
+
+    conv('conv_in', boc[0], 4, 3)
+    lin('time_embedding.linear_1', temb, boc[0], gain=2.0)
+    lin('time_embedding.linear_2', temb, temb, gain=2.0)
+    skips = [boc[0]]
+    prev = boc[0]
+    for i, c in enumerate(boc):
+        last = i == len(boc) - 1
+        for j in range(layers_per_block):
+            resnet(f'down_blocks.{i}.resnets.{j}', prev, c)
+            if not last:
+                transformer(f'down_blocks.{i}.attentions.{j}', c)
+            prev = c
+            skips.append(c)
+        if not last:
+            conv(f'down_blocks.{i}.downsamplers.0.conv', c, c, 3)
+            skips.append(c)
+    top = boc[-1]
+    resnet('mid_block.resnets.0', top, top)
+    transformer('mid_block.attentions.0', top)
+    resnet('mid_block.resnets.1', top, top)
+    for i, c in enumerate(boc[::-1]):
+        for j in range(layers_per_block + 1):
+            resnet(f'up_blocks.{i}.resnets.{j}', prev + skips.pop(), c)
+            if i != 0:
+                transformer(f'up_blocks.{i}.attentions.{j}', c)
+            prev = c
+        if i != len(boc) - 1:
+            conv(f'up_blocks.{i}.upsamplers.0.conv', c, c, 3)
+    norm('conv_norm_out', boc[0])
+    conv('conv_out', 4, boc[0], 3)
+    return sd

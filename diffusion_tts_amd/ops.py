@@ -520,6 +520,58 @@ def attention_x3_ok(t, d):
     return d == 64 and t >= 128 and os.environ.get('DTS_X3_FUSE_IMAGES', '1') != '0'     # (0: A/B aid -- f32 tensors + split passes)
 
 
+def cross_attention(q, kv, heads, scale, kv_rows=None):
+    """q [n, tq, heads*d], kv [m, tk, 2*heads*d] (k | v blocks; 1 <= tk <= 128) -> [n, tq, heads*d] (dts_cross_attention; float16 / bfloat16).
+    kv_rows: int32 [n] on the device, sample i attends to kv[kv_rows[i]] (entries in [0, m)); None: m == n, row for row."""
+    n, tq, c = q.shape
+    m, tk, c2 = kv.shape
+    if c2 != 2 * c or c % heads or (kv_rows is None and m != n) or (kv_rows is not None and tuple(kv_rows.shape) != (n,)):
+        raise ValueError(f'cross_attention: q {tuple(q.shape)}, kv {tuple(kv.shape)}, {heads} heads' + ('' if kv_rows is None else f', kv_rows {tuple(kv_rows.shape)}'))
+    out = torch.empty((n, tq, c), dtype=q.dtype, device=q.device)
+    _call('dts_cross_attention', _ptr(q, 'q'), _ptr(kv, 'kv', q.dtype), _ptr(kv_rows, 'kv_rows', torch.int32), m, _ptr(out), dt_code(q.dtype),
+          n, tq, tk, heads, c // heads, float(scale))
+    return out
+
+
+def layer_norm(x, gamma, beta, eps=1e-5):
+    """LayerNorm over the last dimension of a contiguous float16 / bfloat16 tensor; gamma, beta float32 [c] (dts_layer_norm)."""
+    c = x.shape[-1]
+    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
+        raise ValueError(f'layer_norm: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} for {c} channels')
+    out = torch.empty_like(x)
+    _call('dts_layer_norm', _ptr(x, 'x'), _ptr(out), dt_code(x.dtype), x.numel() // c, c, float(eps), _ptr(gamma, 'gamma', torch.float32),
+          _ptr(beta, 'beta', torch.float32))
+    return out
+
+
+def geglu(x):
+    """x [..., 2*inner] -> x[..., :inner] * gelu(x[..., inner:]) with the exact (erf) GELU (dts_geglu; float16 / bfloat16)."""
+    inner = x.shape[-1] // 2
+    if x.shape[-1] != 2 * inner:
+        raise ValueError(f'geglu: odd last dimension {x.shape[-1]}')
+    out = torch.empty(tuple(x.shape[:-1]) + (inner,), dtype=x.dtype, device=x.device)
+    _call('dts_geglu', _ptr(x, 'x'), _ptr(out), dt_code(x.dtype), x.numel() // (2 * inner), inner)
+    return out
+
+
+def stride2_conv_weight(w, cpad=None):
+    """The weight of Conv2d(kernel 3, stride 2, padding 1) (diffusers Downsample2D) as a 3x3 padding-1 stride-1 convolution over
+    space_to_depth2(x): output pixel (i, j) reads input rows 2i - 1, 2i, 2i + 1 = phase 1 of pixel block i - 1 and phases 0, 1 of block i, so
+    of the 3 x 3 block taps only those at offsets {-1, 0} are live and each carries the source taps that fall on its phases (the others stay
+    zero: 4 x the multiply-adds of the strided form).  w [O, C, 3, 3] -> [O, cpad or 4C, 3, 3], channel (ry*2 + rx)*C + c; a pure rearrangement."""
+    O, Cin, kh, kw = w.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError('stride2_conv_weight: a 3x3 weight')
+    cpad = 4 * Cin if cpad is None else cpad
+    out = torch.zeros((O, cpad, 3, 3), dtype=w.dtype, device=w.device)
+    place = ((0, 1), (1, 0), (1, 1))                 # source tap u -> (block tap t, phase r): 2i + u - 1 = 2(i + t - 1) + r
+    for u, (ty, ry) in enumerate(place):
+        for v, (tx, rx) in enumerate(place):
+            ch = (ry * 2 + rx) * Cin
+            out[:, ch:ch + Cin, ty, tx] = w[:, :, u, v]
+    return out
+
+
 # ---- embedding / preconditioning ----------------------------------------------------------------
 def linear(x, w, bias=None, *, act_in=False, act_out=False, out=None, accumulate=False):
     m, k = x.shape

@@ -1,0 +1,368 @@
+"""The SD-1.x U-Net on the HIP kernels: drop-in for the `unet` object of the SD search loop
+(`unet(sample, t, encoder_hidden_states=..., return_dict=False)[0]`, `.config`, `.dtype`, `.device`), i.e. for `UNet2DConditionModel.forward`
+of the vendored diffusers (sd/diffusers/src/diffusers/models/unets/unet_2d_condition.py, unet_2d_blocks.py, resnet.py,
+transformers/transformer_2d.py, attention.py, attention_processor.py).
+
+Two U-Net rows per candidate per DDIM step are the largest cost of an SD search; here they run on the same kernels as the EDM denoisers
+and the VAE decoder, plus the three the transformer blocks need:
+  3x3 / 1x1 convs, every Linear      -> dts_conv2d (implicit GEMM on MFMA; nearest-2x upsample fused into the gather; time-embedding
+                                        addend, residual add in the epilogue; the up blocks' channel concat as the x2 operand, never a copy)
+  GroupNorm(32) [+ SiLU]             -> dts_gn_* (statistics fused into the producing conv's epilogue where possible)
+  self-attention                     -> dts_attention
+  attention over the text tokens     -> dts_cross_attention (K and V of a head in LDS at once; rows that share a context share its k|v)
+  LayerNorm, GEGLU                   -> dts_layer_norm, dts_geglu
+  time embedding                     -> dts_pos_embedding, dts_linear (f32)
+  Downsample2D (3x3, stride 2)       -> dts_space_to_depth2 + a 3x3 stride-1 conv over 4C channels (ops.stride2_conv_weight)
+Activations are NHWC in `dtype` (float16 like the reference pipeline, or bfloat16).  The 4 latent channels are zero-padded to 64 for the
+MFMA conv (cin % 64 == 0) and conv_out's 4 output channels likewise (cout % 64 == 0).  SD-1.5's head dims 40 / 80 / 160 are zero-padded to
+64 / 128 / 256 at load time (rows of to_q / to_k / to_v, columns of to_out.0; scale = 1/sqrt(true dim)): exact, see pad_head_rows.
+
+Parameters: a state dict with diffusers' key names (`UNet2DConditionModel.state_dict()` / the safetensors file of SD-1.5's unet/).
+Stock SD-1.x configuration only (check_config); anything else is refused by name.
+"""
+import math
+import types
+
+import torch
+
+from . import ops
+
+STOCK = {
+    '_class_name': 'UNet2DConditionModel',
+    'down_block_types': ['CrossAttnDownBlock2D', 'CrossAttnDownBlock2D', 'CrossAttnDownBlock2D', 'DownBlock2D'],
+    'mid_block_type': 'UNetMidBlock2DCrossAttn',
+    'up_block_types': ['UpBlock2D', 'CrossAttnUpBlock2D', 'CrossAttnUpBlock2D', 'CrossAttnUpBlock2D'],
+    'use_linear_projection': False, 'act_fn': 'silu', 'norm_num_groups': 32, 'norm_eps': 1e-5, 'resnet_time_scale_shift': 'default',
+    'flip_sin_to_cos': True, 'freq_shift': 0, 'transformer_layers_per_block': 1, 'class_embed_type': None, 'addition_embed_type': None,
+    'num_class_embeds': None, 'time_cond_proj_dim': None, 'encoder_hid_dim': None, 'encoder_hid_dim_type': None,
+    'dual_cross_attention': False, 'only_cross_attention': False, 'upcast_attention': False, 'center_input_sample': False,
+    'in_channels': 4, 'out_channels': 4, 'time_embedding_type': 'positional', 'time_embedding_dim': None, 'timestep_post_act': None,
+    'time_embedding_act_fn': None, 'conv_in_kernel': 3, 'conv_out_kernel': 3, 'downsample_padding': 1, 'mid_block_scale_factor': 1,
+    'num_attention_heads': None, 'attention_type': 'default', 'cross_attention_norm': None, 'resnet_skip_time_act': False,
+    'resnet_out_scale_factor': 1.0, 'class_embeddings_concat': False, 'mid_block_only_cross_attention': None,
+    'reverse_transformer_layers_per_block': None, 'addition_time_embed_dim': None, 'projection_class_embeddings_input_dim': None,
+    'dropout': 0.0,
+}
+
+
+def check_config(cfg):
+    """Raises ValueError naming the first key of a diffusers U-Net config that is not the stock SD-1.x setting (keys that are absent
+    have diffusers' defaults, which are the stock ones)."""
+    for key, want in STOCK.items():
+        if key not in cfg:
+            continue
+        got = cfg[key]
+        if isinstance(got, tuple):
+            got = list(got)
+        if got != want:
+            raise ValueError(f'SDUNet: {key}={cfg[key]!r} is not the stock SD-1.x U-Net ({want!r})')
+    for key in ('attention_head_dim', 'layers_per_block', 'cross_attention_dim'):
+        if key in cfg and not isinstance(cfg[key], int):
+            raise ValueError(f'SDUNet: {key}={cfg[key]!r} is not the stock SD-1.x U-Net (one integer)')
+    if 'block_out_channels' in cfg and len(cfg['block_out_channels']) != 4:
+        raise ValueError(f'SDUNet: block_out_channels={cfg["block_out_channels"]!r} is not the stock SD-1.x U-Net (four levels)')
+
+
+def padded_head_dim(d):
+    """the head dim of the attention kernels (64 / 128 / 256) that holds a true head dim d"""
+    for dp in (64, 128, 256):
+        if d <= dp:
+            return dp
+    raise ValueError(f'SDUNet: head dim {d} exceeds the attention kernels\' 256')
+
+
+def pad_head_rows(w, heads, dpad):
+    """to_q / to_k / to_v weight [heads*d, cin] -> [heads*dpad, cin]: each head's d output rows followed by dpad - d zero rows.  With the
+    matching pad_head_cols of to_out.0 the attention is unchanged: the padded q and k components add 0 to every q.k, the padded v
+    components are 0 and meet zero columns of to_out.0 -- as long as the softmax scale stays 1/sqrt(d) of the TRUE head dim."""
+    hd, cin = w.shape
+    d = hd // heads
+    out = torch.zeros((heads, dpad, cin), dtype=w.dtype, device=w.device)
+    out[:, :d] = w.view(heads, d, cin)
+    return out.view(heads * dpad, cin)
+
+
+def pad_head_cols(w, heads, dpad):
+    """to_out.0 weight [cout, heads*d] -> [cout, heads*dpad] (zero columns where the padded value channels arrive)"""
+    cout, hd = w.shape
+    d = hd // heads
+    out = torch.zeros((cout, heads, dpad), dtype=w.dtype, device=w.device)
+    out[:, :, :d] = w.view(cout, heads, d)
+    return out.view(cout, heads * dpad)
+
+
+class SDUNet:
+    def __init__(self, state_dict, block_out_channels=(320, 640, 1280, 1280), attention_head_dim=8, cross_attention_dim=768,
+                 layers_per_block=2, sample_size=64, device='cuda', dtype=torch.float16):
+        """attention_head_dim: the NUMBER of heads of every transformer block (diffusers' historical name for it, unet_2d_condition.py:
+        `num_attention_heads = num_attention_heads or attention_head_dim`)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError('SDUNet (HIP) needs a GPU: there is no CPU fallback in this package')
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError('SDUNet: activations are float16 or bfloat16')
+        self.device, self.dtype = torch.device(device), dtype
+        self.boc, self.heads, self.ctx_dim, self.lpb = tuple(block_out_channels), int(attention_head_dim), int(cross_attention_dim), int(layers_per_block)
+        self.groups, self.eps = 32, 1e-5
+        self.config = types.SimpleNamespace(in_channels=4, out_channels=4, sample_size=sample_size, time_cond_proj_dim=None,
+                                            addition_embed_type=None, block_out_channels=list(block_out_channels),
+                                            attention_head_dim=self.heads, cross_attention_dim=self.ctx_dim, layers_per_block=self.lpb)
+        self.rows = 0
+        self._load(state_dict)
+
+    @classmethod
+    def from_pretrained(cls, path, device='cuda', dtype=torch.float16):
+        """Reads a diffusers `unet/` directory: `config.json` for the shape and `diffusion_pytorch_model[.fp16].safetensors` for the
+        parameters -- the on-disk format of SD-1.5's U-Net.  A `.bin` pickle is not read."""
+        import json
+        import os
+        cfg_file = os.path.join(path, 'config.json')
+        if not os.path.exists(cfg_file):
+            raise FileNotFoundError(f'{path}: no config.json (the configuration is not guessed: only a stock SD-1.x U-Net is accepted, by name)')
+        with open(cfg_file) as f:
+            cfg = json.load(f)
+        check_config(cfg)
+        names = [n for n in ('diffusion_pytorch_model.safetensors', 'diffusion_pytorch_model.fp16.safetensors') if
+                 os.path.exists(os.path.join(path, n))]
+        if not names:
+            raise FileNotFoundError(f'{path}: no diffusion_pytorch_model[.fp16].safetensors (a .bin pickle is not read: convert it to safetensors)')
+        from safetensors import safe_open
+        sd = {}
+        with safe_open(os.path.join(path, names[0]), framework='pt', device='cpu') as f:
+            for k in f.keys():
+                sd[k] = f.get_tensor(k)
+        kw = {k: cfg[k] for k in ('attention_head_dim', 'cross_attention_dim', 'layers_per_block', 'sample_size') if k in cfg}
+        if 'block_out_channels' in cfg:
+            kw['block_out_channels'] = tuple(cfg['block_out_channels'])
+        return cls(sd, device=device, dtype=dtype, **kw)
+
+    # ---- parameters ----------------------------------------------------------------------------
+    def _f(self, t):
+        return t.detach().to(self.device, torch.float32).contiguous()
+
+    def _pack(self, w, b=None, pad_in=None, pad_out=None):
+        """f32 weight [O, I] / [O, I, k, k] (+ bias) on the device -> (packed [O][k][k][I] in the activation dtype, f32 bias)"""
+        if w.dim() == 2:
+            w = w[:, :, None, None]
+        if pad_in is not None and w.shape[1] < pad_in:
+            w = torch.cat([w, torch.zeros(w.shape[0], pad_in - w.shape[1], *w.shape[2:], device=w.device)], 1)
+        if pad_out is not None and w.shape[0] < pad_out:
+            w = torch.cat([w, torch.zeros(pad_out - w.shape[0], *w.shape[1:], device=w.device)], 0)
+            if b is not None:
+                b = torch.cat([b, torch.zeros(pad_out - b.shape[0], device=b.device)])
+        return ops.pack_conv_weight(w.contiguous(), self.dtype), (None if b is None else b.contiguous())
+
+    def _conv(self, sd, key, **kw):
+        return self._pack(self._f(sd[key + '.weight']), self._f(sd[key + '.bias']), **kw)
+
+    def _resnet_params(self, sd, key):
+        P = types.SimpleNamespace()
+        P.g1, P.b1 = self._f(sd[key + '.norm1.weight']), self._f(sd[key + '.norm1.bias'])
+        P.w1, P.c1 = self._conv(sd, key + '.conv1')
+        P.g2, P.b2 = self._f(sd[key + '.norm2.weight']), self._f(sd[key + '.norm2.bias'])
+        P.w2, P.c2 = self._conv(sd, key + '.conv2')
+        P.ws = P.cs = None
+        if key + '.conv_shortcut.weight' in sd:
+            P.ws, P.cs = self._conv(sd, key + '.conv_shortcut')
+        # time_emb_proj of every block is one row block of a single f32 matrix: one dts_linear per forward instead of 22
+        P.cout = P.w1.shape[0]
+        P.toff = self._tcols
+        self._tw.append(self._f(sd[key + '.time_emb_proj.weight']))
+        self._tb.append(self._f(sd[key + '.time_emb_proj.bias']))
+        self._tcols += P.cout
+        return P
+
+    def _transformer_params(self, sd, key, c):
+        H = self.heads
+        if c % H:
+            raise ValueError(f'SDUNet: {c} channels do not split into {H} heads')
+        d = c // H
+        dp = padded_head_dim(d)
+        A = types.SimpleNamespace(heads=H, scale=1.0 / math.sqrt(d), hp=H * dp)
+        A.g, A.b = self._f(sd[key + '.norm.weight']), self._f(sd[key + '.norm.bias'])
+        if sd[key + '.proj_in.weight'].dim() != 4:
+            raise ValueError('SDUNet: use_linear_projection=True (a Linear proj_in) is not the stock SD-1.x U-Net')
+        A.w_in, A.b_in = self._conv(sd, key + '.proj_in')
+        A.w_out, A.b_out = self._conv(sd, key + '.proj_out')
+        t = key + '.transformer_blocks.0'
+        if key + '.transformer_blocks.1.norm1.weight' in sd:
+            raise ValueError('SDUNet: transformer_layers_per_block > 1 is not the stock SD-1.x U-Net')
+        A.ln = [(self._f(sd[f'{t}.norm{i}.weight']), self._f(sd[f'{t}.norm{i}.bias'])) for i in (1, 2, 3)]
+        rows = lambda name: pad_head_rows(self._f(sd[f'{t}.{name}.weight']), H, dp)
+        A.w_qkv, _ = self._pack(torch.cat([rows('attn1.to_q'), rows('attn1.to_k'), rows('attn1.to_v')], 0))      # q | k | v blocks
+        A.w_o1, A.b_o1 = self._pack(pad_head_cols(self._f(sd[f'{t}.attn1.to_out.0.weight']), H, dp), self._f(sd[f'{t}.attn1.to_out.0.bias']))
+        A.w_q2, _ = self._pack(rows('attn2.to_q'))
+        A.w_kv2, _ = self._pack(torch.cat([rows('attn2.to_k'), rows('attn2.to_v')], 0))                           # k | v blocks, cin = text width
+        A.w_o2, A.b_o2 = self._pack(pad_head_cols(self._f(sd[f'{t}.attn2.to_out.0.weight']), H, dp), self._f(sd[f'{t}.attn2.to_out.0.bias']))
+        A.w_ff1, A.b_ff1 = self._conv(sd, f'{t}.ff.net.0.proj')
+        A.w_ff2, A.b_ff2 = self._conv(sd, f'{t}.ff.net.2')
+        A.index = len(self._tfm)
+        self._tfm.append(A)
+        return A
+
+    def _check_shapes(self, sd):
+        """the parameters must be those of the configuration this object was given: a mismatch is named here, not met as a reshape error"""
+        boc, temb = self.boc, 4 * self.boc[0]
+        want = {'conv_in.weight': (boc[0], 4, 3, 3), 'conv_out.weight': (4, boc[0], 3, 3), 'time_embedding.linear_1.weight': (temb, boc[0]),
+                'mid_block.resnets.0.conv1.weight': (boc[-1], boc[-1], 3, 3),
+                'mid_block.attentions.0.transformer_blocks.0.attn2.to_k.weight': (boc[-1], self.ctx_dim),
+                f'up_blocks.{len(boc) - 1}.resnets.{self.lpb}.conv2.weight': (boc[0], boc[0], 3, 3)}
+        for i, c in enumerate(boc):
+            want[f'down_blocks.{i}.resnets.{self.lpb - 1}.conv2.weight'] = (c, c, 3, 3)
+            if i != len(boc) - 1:
+                want[f'down_blocks.{i}.attentions.0.transformer_blocks.0.attn1.to_q.weight'] = (c, c)
+            if c % self.heads:
+                raise ValueError(f'SDUNet: block_out_channels {boc} do not split into attention_head_dim={self.heads} heads')
+        for key, shape in want.items():
+            if key not in sd:
+                raise ValueError(f'SDUNet: the state dict has no {key!r} (block_out_channels={boc}, layers_per_block={self.lpb})')
+            if tuple(sd[key].shape) != shape:
+                raise ValueError(f'SDUNet: {key} has shape {tuple(sd[key].shape)}, but block_out_channels={boc}, '
+                                 f'cross_attention_dim={self.ctx_dim} ask for {shape}')
+        extra = f'down_blocks.0.resnets.{self.lpb}.conv1.weight'
+        if extra in sd:
+            raise ValueError(f'SDUNet: the state dict has {extra!r}: more than layers_per_block={self.lpb} resnets per block')
+
+    def _load(self, sd):
+        self._check_shapes(sd)
+        boc, lpb = self.boc, self.lpb
+        self._tw, self._tb, self._tcols, self._tfm = [], [], 0, []
+        half = boc[0] // 2
+        self.freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half).to(self.device)    # freq_shift = 0
+        self.t1 = (self._f(sd['time_embedding.linear_1.weight']), self._f(sd['time_embedding.linear_1.bias']))
+        self.t2 = (self._f(sd['time_embedding.linear_2.weight']), self._f(sd['time_embedding.linear_2.bias']))
+        self.conv_in = self._conv(sd, 'conv_in', pad_in=64)
+        self.down = []
+        for i, c in enumerate(boc):
+            cross = i != len(boc) - 1
+            layers = []
+            for j in range(lpb):
+                layers.append((self._resnet_params(sd, f'down_blocks.{i}.resnets.{j}'),
+                               self._transformer_params(sd, f'down_blocks.{i}.attentions.{j}', c) if cross else None))
+            ds = None
+            if i != len(boc) - 1:
+                w = ops.stride2_conv_weight(self._f(sd[f'down_blocks.{i}.downsamplers.0.conv.weight']))
+                ds = self._pack(w, self._f(sd[f'down_blocks.{i}.downsamplers.0.conv.bias']))
+            self.down.append((layers, ds))
+        self.mid = (self._resnet_params(sd, 'mid_block.resnets.0'), self._transformer_params(sd, 'mid_block.attentions.0', boc[-1]),
+                    self._resnet_params(sd, 'mid_block.resnets.1'))
+        self.up = []
+        rev = boc[::-1]
+        for i, c in enumerate(rev):
+            cross = i != 0
+            layers = []
+            for j in range(lpb + 1):
+                layers.append((self._resnet_params(sd, f'up_blocks.{i}.resnets.{j}'),
+                               self._transformer_params(sd, f'up_blocks.{i}.attentions.{j}', c) if cross else None))
+            us = self._conv(sd, f'up_blocks.{i}.upsamplers.0.conv') if i != len(rev) - 1 else None
+            self.up.append((layers, us))
+        self.out_g, self.out_b = self._f(sd['conv_norm_out.weight']), self._f(sd['conv_norm_out.bias'])
+        self.conv_out = self._conv(sd, 'conv_out', pad_out=64)
+        self.tproj = (torch.cat(self._tw, 0).contiguous(), torch.cat(self._tb).contiguous())
+        del self._tw, self._tb
+        torch.cuda.synchronize(self.device)
+
+    # ---- forward -------------------------------------------------------------------------------
+    def _resnet(self, x, P, temb, skip=None):
+        """ResnetBlock2D.forward (resnet.py): norm1-silu-conv1 (+ time_emb_proj(silu(emb)) per sample and channel)-norm2-silu-conv2,
+        + the input or its 1x1 shortcut.  skip: the second half of the up blocks' torch.cat([x, skip], 1), read in place."""
+        G = self.groups
+        h = ops.group_norm(x, G, self.eps, P.g1, P.b1, x2=skip, silu=True)
+        h = ops.conv2d(h, P.w1, P.c1, bias_nc=temb[:, P.toff:P.toff + P.cout], gn_stats=True)
+        h = ops.group_norm(h, G, self.eps, P.g2, P.b2, silu=True)
+        if P.ws is not None:
+            sk = ops.conv2d(x, P.ws, P.cs, x2=skip)
+        elif skip is None:
+            sk = x
+        else:
+            raise ValueError('SDUNet: a resnet over concatenated inputs needs its conv_shortcut')
+        return ops.conv2d(h, P.w2, P.c2, residual=sk, gn_stats=True)
+
+    def _context_kv(self, ehs):
+        """The k | v projections of the text tokens for every transformer block: they do not depend on the latents, and the 2N rows of a
+        search step hold two distinct contexts -- projected once per DISTINCT row; dts_cross_attention reads them through the row map."""
+        n, L, cd = ehs.shape
+        if cd != self.ctx_dim:
+            raise ValueError(f'SDUNet: encoder_hidden_states has width {cd}, the model {self.ctx_dim}')
+        bits = ehs.reshape(n, L * cd).view(torch.int16)
+        uniq, inverse = torch.unique(bits, dim=0, return_inverse=True)
+        ctx = uniq.view(self.dtype).view(uniq.shape[0], L, 1, cd).contiguous()
+        kv = [ops.conv2d(ctx, A.w_kv2).view(ctx.shape[0], L, 2 * A.hp) for A in self._tfm]
+        return kv, inverse.to(torch.int32).contiguous()
+
+    def _transformer(self, x, A, kv, kv_rows):
+        """Transformer2DModel.forward with one BasicTransformerBlock (transformer_2d.py, attention.py): tokens stay in NHWC, every
+        Linear is a 1x1 convolution with the residual add in its epilogue."""
+        n, hh, ww, c = x.shape
+        t = hh * ww
+        h = ops.group_norm(x, self.groups, 1e-6, A.g, A.b, silu=False)
+        h = ops.conv2d(h, A.w_in, A.b_in)
+        y = ops.layer_norm(h, *A.ln[0])
+        qkv = ops.conv2d(y, A.w_qkv)
+        a = ops.attention(qkv.view(n, t, 3 * A.hp), A.heads, A.scale)
+        h = ops.conv2d(a.view(n, hh, ww, A.hp), A.w_o1, A.b_o1, residual=h)
+        y = ops.layer_norm(h, *A.ln[1])
+        q = ops.conv2d(y, A.w_q2)
+        a = ops.cross_attention(q.view(n, t, A.hp), kv[A.index], A.heads, A.scale, kv_rows=kv_rows)
+        h = ops.conv2d(a.view(n, hh, ww, A.hp), A.w_o2, A.b_o2, residual=h)
+        y = ops.layer_norm(h, *A.ln[2])
+        f = ops.geglu(ops.conv2d(y, A.w_ff1, A.b_ff1))
+        h = ops.conv2d(f, A.w_ff2, A.b_ff2, residual=h)
+        return ops.conv2d(h, A.w_out, A.b_out, residual=x, gn_stats=True)
+
+    @torch.no_grad()
+    def __call__(self, sample, timestep, encoder_hidden_states=None, return_dict=False, **unused):
+        """sample [n, 4, h, w], timestep a number / 0-d tensor / [n] tensor, encoder_hidden_states [n, L <= 128, cross_attention_dim]
+        -> ([n, 4, h, w] in `dtype`,)."""
+        for k, v in unused.items():
+            if v is not None:
+                raise ValueError(f'SDUNet: argument {k} is not supported (stock SD-1.x call surface only)')
+        if encoder_hidden_states is None:
+            raise ValueError('SDUNet: encoder_hidden_states is required')
+        sample = sample.to(self.device)
+        n, cin, hh, ww = sample.shape
+        if cin != 4 or hh % 8 or ww % 8:
+            raise ValueError(f'SDUNet: sample {tuple(sample.shape)}: 4 channels and a height / width divisible by 8 (three 2x levels)')
+        ehs = encoder_hidden_states.to(self.device, self.dtype)
+        if ehs.shape[0] != n:
+            raise ValueError(f'SDUNet: {ehs.shape[0]} encoder_hidden_states rows for {n} samples')
+        tt = torch.as_tensor(timestep, dtype=torch.float32, device=self.device).reshape(-1)
+        if tt.numel() not in (1, n):
+            raise ValueError(f'SDUNet: {tt.numel()} timesteps for {n} samples')
+        tt = tt.expand(n).contiguous()
+        emb = ops.pos_embedding(tt, self.freqs)                                        # cos | sin (flip_sin_to_cos)
+        emb = ops.linear(emb, *self.t1, act_out=True)
+        emb = ops.linear(emb, *self.t2)
+        temb = ops.cast_from_f32(ops.linear(emb, *self.tproj, act_in=True), self.dtype)      # every block's time_emb_proj(silu(emb))
+        kv, kv_rows = self._context_kv(ehs.contiguous())
+
+        x = ops.nchw_to_nhwc_pad(sample.float().contiguous(), self.dtype, 64)
+        x = ops.conv2d(x, *self.conv_in, gn_stats=True)
+        skips = [x]
+        for layers, ds in self.down:
+            for P, A in layers:
+                x = self._resnet(x, P, temb)
+                if A is not None:
+                    x = self._transformer(x, A, kv, kv_rows)
+                skips.append(x)
+            if ds is not None:
+                x = ops.conv2d(ops.space_to_depth2(x, self.dtype), *ds, gn_stats=True)
+                skips.append(x)
+        x = self._resnet(x, self.mid[0], temb)
+        x = self._transformer(x, self.mid[1], kv, kv_rows)
+        x = self._resnet(x, self.mid[2], temb)
+        for layers, us in self.up:
+            for P, A in layers:
+                x = self._resnet(x, P, temb, skip=skips.pop())
+                if A is not None:
+                    x = self._transformer(x, A, kv, kv_rows)
+            if us is not None:
+                x = ops.conv2d(x, *us, up=True, gn_stats=True)                         # Upsample2D: nearest-2x fused into the conv's gather
+        h = ops.group_norm(x, self.groups, self.eps, self.out_g, self.out_b, silu=True)
+        y = ops.conv2d(h, *self.conv_out)                                              # 4 live output channels of 64
+        out = y[..., :4].permute(0, 3, 1, 2).contiguous()
+        self.rows += n
+        if return_dict:
+            return types.SimpleNamespace(sample=out)
+        return (out,)
+
+    forward = __call__

@@ -42,13 +42,14 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 112        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 113        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
                                      110: dts_candidate_noise_sd takes the three scalars of the reference's product separately (scale [n][3]);
                                      111: dts_conv_args.skip_* (a block's 1x1 skip convolution folded into its second 3x3), dts_conv_folds_skip;
-                                     112: dts_resample_fir, dts_space_to_depth2 (the NCSN++ options of SongUNet)) */
+                                     112: dts_resample_fir, dts_space_to_depth2 (the NCSN++ options of SongUNet);
+                                     113: dts_cross_attention, dts_layer_norm, dts_geglu (the SD U-Net's transformer blocks)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -183,6 +184,23 @@ int dts_attention(const void* qkv, void* out, int dtype, int n, int t, int heads
  * image [n][t][2*heads*d] (per 32 channels hi | lo * 2^11: dts_split3_f16's arithmetic and layout) the proj convolution reads.  Q.K^T and P.V on the 16-bit matrix cores with hi/lo operand pairs (the lo*lo term,
  * 2^-22, dropped), softmax in f32: the f32 kernel's accuracy without the f32 matrix instruction's 1/16 rate. */
 int dts_attention_x3(const void* qkv_split, void* out, int out_split3, int n, int t, int heads, int d, float scale, dts_stream s);
+
+/* ---- K15-K17: the SD U-Net's transformer blocks (diffusers BasicTransformerBlock: attention.py, attention_processor.py) ---- */
+/* Attention of tq queries over a SHORT foreign sequence (the text tokens): q [n][tq][heads*d], kv [kv_n][tk][2*heads*d] laid out
+ * k[heads][d] | v[heads][d], out [n][tq][heads*d]; DTS_BF16 / DTS_F16; softmax(q.k * scale) in f32, Q.K^T and P.V on the 16-bit matrix
+ * cores.  1 <= tk <= 128 (any length: the tail is masked): K and V of a (sample, head) sit in LDS at once, one pass over the keys, no online
+ * rescale; a longer tk returns DTS_ERR_UNSUPPORTED.  d in {64, 128, 256}; any tq >= 1; scale > 0.
+ * kv_rows (device int32 [n], nullable): sample i attends to kv row kv_rows[i] (the 2N rows of the search loop share two text contexts:
+ * their k|v projections are computed once each and never expanded); NULL: kv_n == n and sample i reads row i.  Entries must lie in
+ * [0, kv_n); the kernel clamps them for memory safety only. */
+int dts_cross_attention(const void* q, const void* kv, const int32_t* kv_rows, int kv_n, void* out, int dtype, int n, int tq, int tk,
+                        int heads, int d, float scale, dts_stream s);
+/* out[r][:] = (x[r][:] - mean_r) / sqrt(var_r + eps) * gamma + beta over rows of c channels (biased variance, as torch.nn.LayerNorm);
+ * DTS_BF16 / DTS_F16 in and out, statistics in f32 (two passes over the row in registers), gamma / beta f32 [c]; c % 8 == 0, c <= 2048. */
+int dts_layer_norm(const void* x, void* out, int dtype, int64_t rows, int c, float eps, const float* gamma, const float* beta, dts_stream s);
+/* GEGLU (diffusers activations.py GEGLU): x [rows][2*inner] -> out[r][j] = x[r][j] * gelu(x[r][inner + j]), the exact (erf) GELU;
+ * DTS_BF16 / DTS_F16 storage, f32 arithmetic; inner % 8 == 0. */
+int dts_geglu(const void* x, void* out, int dtype, int64_t rows, int inner, dts_stream s);
 
 /* ---- K7/K8: embedding MLP pieces and EDM preconditioning (networks.py:200-206,437-447,654-668) ---- */
 /* y[m][n] = act_out( act_in(x[m][:]) . w[n][:] + bias[n] (+ y[m][n] if accumulate) ); all f32; act: 0 none, 1 SiLU */

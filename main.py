@@ -16,6 +16,8 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
     --dtype     : f16x3 (default: split precision on the 16-bit matrix cores -- the reference's fp32 rewards and therefore its selected
                   candidates on the same seed, ~2.6x the f32 mode's speed) | f32 (parity mode, f32 matrix instruction) | bf16 | f16
                   (throughput modes: ~2.8x faster again, but a near-tied pick differs after ~10 decisions and the result is another sample)
+    --unet      : SD backend: diffusers (default: the stock UNet2DConditionModel) | hip (sd_unet.SDUNet on this build's kernels, read from
+                  $DTS_SD_UNET_DIR or the cached snapshot's unet/; no fallback).  --vae hip|diffusers likewise (default hip)
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`; the N candidates of every
@@ -66,17 +68,41 @@ def load_sd_vae(model_id, dev, kind='hip'):
     return VAEDecoder.from_pretrained(path, device=dev, dtype=torch.float16)
 
 
+def load_sd_unet(model_id, dev, kind='diffusers'):
+    """The SD U-Net of the search loop, the twin of load_sd_vae.  kind='hip' (`--unet hip`): this build's HIP U-Net (sd_unet.SDUNet, drop-in
+    for `unet(sample, t, encoder_hidden_states=...)`) read from the safetensors `unet/` directory of the locally cached SD-1.5 snapshot (or
+    $DTS_SD_UNET_DIR) -- and an error when that directory cannot be found or read: there is no silent fallback.  kind='diffusers' (the
+    default): the stock UNet2DConditionModel module."""
+    if kind == 'diffusers':
+        from diffusers import UNet2DConditionModel
+        return UNet2DConditionModel.from_pretrained(model_id, subfolder='unet', torch_dtype=torch.float16, local_files_only=True).to(dev)
+    if kind != 'hip':
+        raise ValueError(f"--unet must be 'hip' or 'diffusers', got {kind!r}")
+    from diffusion_tts_amd.sd_unet import SDUNet
+    path = os.environ.get('DTS_SD_UNET_DIR')
+    if path is None:
+        from huggingface_hub import snapshot_download
+        path = os.path.join(snapshot_download(model_id, local_files_only=True, allow_patterns=['unet/*']), 'unet')
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f'SD U-Net directory {path!r} not found (set DTS_SD_UNET_DIR, or pass --unet diffusers for the stock module)')
+    return SDUNet.from_pretrained(path, device=dev, dtype=torch.float16)
+
+
 def main_sd(args):
     """SD backend (reference main.py:111-147).  The search loop, the fused DDIM candidate step and candidate batching are
-    this build's (diffusion_tts_amd/sd_pipeline.py); the U-Net / VAE / text encoder are the stock diffusers / transformers
-    modules on PyTorch-ROCm, which must be importable and have SD-1.5 weights in the local HF cache (no network here)."""
+    this build's (diffusion_tts_amd/sd_pipeline.py), and so are the VAE decoder (`--vae hip`, the default) and, with `--unet hip`, the
+    U-Net (diffusion_tts_amd/sd_unet.py): `--unet hip --vae hip` needs transformers (text encoder, tokenizer) and SD-1.5 weights in the
+    local HF cache only.  `--unet diffusers` (the default) / `--vae diffusers` take the stock diffusers modules on PyTorch-ROCm."""
+    unet_kind, vae_kind = getattr(args, 'unet', 'diffusers'), getattr(args, 'vae', 'hip')
     try:
-        from diffusers import AutoencoderKL, UNet2DConditionModel          # noqa: F401
-        from transformers import CLIPTextModel, CLIPTokenizer              # noqa: F401
+        if 'diffusers' in (unet_kind, vae_kind):                           # only the parts that are asked for need diffusers
+            import diffusers                                               # noqa: F401
+        from transformers import CLIPTextModel, CLIPTokenizer
     except Exception as e:      # pragma: no cover
-        raise RuntimeError('--backend sd needs `diffusers` (U-Net/VAE) and SD-1.5 weights in the local cache; neither is '
-                           'available in this image.  Drive diffusion_tts_amd.sd_pipeline.SDSearchPipeline(unet, vae) directly '
-                           '(tests/test_gpu_sd.py shows the call).') from e
+        raise RuntimeError('--backend sd needs `transformers` (text encoder) and, for --unet diffusers / --vae diffusers, `diffusers`, '
+                           'with SD-1.5 weights in the local cache; that import failed.  `--unet hip --vae hip` runs without diffusers; '
+                           'or drive diffusion_tts_amd.sd_pipeline.SDSearchPipeline(unet, vae) directly (tests/test_gpu_sd_unet.py '
+                           'shows the call).') from e
     from diffusion_tts_amd.sd_pipeline import SDSearchPipeline
     import torch.distributed as dist
     model_id = 'runwayml/stable-diffusion-v1-5'
@@ -86,8 +112,8 @@ def main_sd(args):
         torch.cuda.set_device(local)
         dist.init_process_group('nccl', device_id=torch.device('cuda', local))
     dev = torch.device('cuda', local) if world > 1 else torch.device(args.device)
-    unet = UNet2DConditionModel.from_pretrained(model_id, subfolder='unet', torch_dtype=torch.float16, local_files_only=True).to(dev)
-    vae = load_sd_vae(model_id, dev, getattr(args, 'vae', 'hip'))
+    unet = load_sd_unet(model_id, dev, unet_kind)
+    vae = load_sd_vae(model_id, dev, vae_kind)
     tok = CLIPTokenizer.from_pretrained(model_id, subfolder='tokenizer', local_files_only=True)
     te = CLIPTextModel.from_pretrained(model_id, subfolder='text_encoder', torch_dtype=torch.float16, local_files_only=True).to(dev)
 
@@ -106,7 +132,7 @@ def main_sd(args):
     outname = args.output or f'sd_{args.method}_{args.scorer}.png'
     if int(os.environ.get('RANK', '0')) == 0:
         best.images[0].save(outname)
-        print(f'\n[SD] Saved: {outname}\nBest score: {best_score}  (VAE: {type(vae).__name__}, reward collectives: {best.collectives})\n')
+        print(f'\n[SD] Saved: {outname}\nBest score: {best_score}  (U-Net: {type(unet).__name__}, VAE: {type(vae).__name__}, reward collectives: {best.collectives})\n')
     if world > 1:
         dist.destroy_process_group()
     return best
@@ -134,6 +160,8 @@ def main(argv=None):
     parser.add_argument('--dtype', type=str, default='f16x3', choices=['bf16', 'f16', 'f32', 'f16x3'], help='compute mode (see the module docstring)')
     parser.add_argument('--vae', type=str, default='hip', choices=['hip', 'diffusers'],
                         help="SD backend: 'hip' = this build's VAE decoder (an error if its safetensors cannot be read), 'diffusers' = the stock module")
+    parser.add_argument('--unet', type=str, default='diffusers', choices=['hip', 'diffusers'],
+                        help="SD backend: 'hip' = this build's U-Net on the HIP kernels (an error if its safetensors cannot be read), 'diffusers' = the stock module")
     parser.add_argument('--seeds', type=str, default=None, help='bulk mode: seeds, e.g. 0-63 or 1,2,5-10 (one image per seed)')
     parser.add_argument('--outdir', type=str, default='out', help='bulk mode: output directory')
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')

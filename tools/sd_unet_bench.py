@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""First measurement of the SD-1.5 U-Net on the HIP kernels (diffusion_tts_amd/sd_unet.py): one forward over the 2N = 32 rows of BASELINE
+config 4 ([32,4,64,64] latents, two distinct [77,768] contexts), random-init weights of SD-1.5's shape, float16 and bfloat16.  GPU only.
+
+Prints ONE JSON line: per dtype ms per forward (median of the timed forwards, device events around each forward, after warm-up), rows/s,
+the algorithmic FLOPs of a forward counted from the layer shapes (true head dims and the strided form of the three downsample
+convolutions: what the model asks for, not what the zero-padded heads / space-to-depth form execute), the whole-forward rate as a fraction of
+the dense 16-bit matrix peak (an END-TO-END figure, not any kernel's share of peak), and the share of the forward's time per op
+family from one extra, instrumented forward: a device-event pair is recorded around every ops.* call of the module, nothing synchronises
+until the end, so each span is the stream time between the two records (the op's kernels plus whatever gap precedes the closing record) and
+"other" is the forward's total minus the summed spans, i.e. stream time outside any ops.* call (torch glue kernels such as unique / slicing,
+and host launch gaps when the stream runs dry).  No pass/fail threshold."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from diffusion_tts_amd import init as dinit
+from diffusion_tts_amd import ops
+from diffusion_tts_amd.sd_unet import SDUNet
+
+PEAK_16BIT_DENSE = 2.5e15          # MI355X dense f16 / bf16 matrix peak, FLOP/s
+
+
+def forward_flops(boc=(320, 640, 1280, 1280), heads=8, ctx_dim=768, ctx_len=77, lpb=2, res=64, distinct_contexts=2):
+    """multiply-adds x 2 of one row's forward (+ the context projections of the distinct contexts, spread over the batch by the caller)"""
+    per_row, per_ctx = 0, 0
+    temb = 4 * boc[0]
+
+    def conv(cin, cout, k, hw):
+        return 2 * cin * cout * k * k * hw
+
+    def resnet(cin, cout, hw):
+        f = conv(cin, cout, 3, hw) + conv(cout, cout, 3, hw) + 2 * temb * cout
+        return f + (conv(cin, cout, 1, hw) if cin != cout else 0)
+
+    def transformer(c, hw):
+        nonlocal per_ctx
+        per_ctx += 2 * 2 * ctx_dim * c * ctx_len                                     # to_k, to_v of the text tokens
+        f = 2 * conv(c, c, 1, hw)                                                    # proj_in, proj_out
+        f += 4 * conv(c, c, 1, hw) + 2 * 2 * hw * hw * c                             # attn1: q, k, v, out + Q.K^T, P.V
+        f += 2 * conv(c, c, 1, hw) + 2 * 2 * hw * ctx_len * c                        # attn2: q, out + Q.K^T, P.V over the tokens
+        return f + conv(c, 8 * c, 1, hw) + conv(4 * c, c, 1, hw)                     # GEGLU feed-forward
+
+    hw = res * res
+    per_row += conv(4, boc[0], 3, hw) + 2 * boc[0] * temb + 2 * temb * temb
+    skips, prev = [boc[0]], boc[0]
+    for i, c in enumerate(boc):
+        last = i == len(boc) - 1
+        for _ in range(lpb):
+            per_row += resnet(prev, c, hw) + (0 if last else transformer(c, hw))
+            prev = c
+            skips.append(c)
+        if not last:
+            hw //= 4
+            per_row += conv(c, c, 3, hw)
+            skips.append(c)
+    per_row += 2 * resnet(prev, prev, hw) + transformer(prev, hw)
+    for i, c in enumerate(boc[::-1]):
+        for _ in range(lpb + 1):
+            per_row += resnet(prev + skips.pop(), c, hw) + (0 if i == 0 else transformer(c, hw))
+            prev = c
+        if i != len(boc) - 1:
+            hw *= 4
+            per_row += conv(c, c, 3, hw)
+    per_row += conv(boc[0], 4, 3, hw)
+    return per_row, per_ctx * distinct_contexts
+
+
+FAMILY = {'conv2d': 'conv', 'group_norm': 'group_norm', 'attention': 'self_attention', 'cross_attention': 'cross_attention',
+          'layer_norm': 'layer_norm', 'geglu': 'geglu', 'linear': 'time_embedding', 'pos_embedding': 'time_embedding',
+          'cast_from_f32': 'time_embedding', 'space_to_depth2': 'layout', 'nchw_to_nhwc_pad': 'layout'}
+
+
+def op_shares(unet, x, t, ehs):
+    """one forward with device events around every ops.* call of the module"""
+    spans, saved = [], {}
+    for name, fam in FAMILY.items():
+        fn = saved[name] = getattr(ops, name)
+
+        def timed(*a, _fn=fn, _fam=fam, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = _fn(*a, **kw)
+            e1.record()
+            spans.append((_fam, e0, e1))
+            return r
+        setattr(ops, name, timed)
+    try:
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        unet(x, t, encoder_hidden_states=ehs)
+        e1.record()
+        torch.cuda.synchronize()
+    finally:
+        for name, fn in saved.items():
+            setattr(ops, name, fn)
+    fam_ms = {}
+    for fam, a, b in spans:
+        fam_ms[fam] = fam_ms.get(fam, 0.0) + a.elapsed_time(b)
+    total = e0.elapsed_time(e1)
+    fam_ms['other (torch glue, launch gaps)'] = max(0.0, total - sum(fam_ms.values()))
+    return {k: round(v / total, 4) for k, v in sorted(fam_ms.items(), key=lambda kv: -kv[1])}, len(spans)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rows', type=int, default=32)
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--dtypes', default='f16,bf16')
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('sd_unet_bench: needs a GPU (no CPU fallback, nothing is measured without one)')
+    per_row, ctx = forward_flops()
+    flops = a.rows * per_row + ctx
+    sd = dinit.sd_unet_state_dict(seed=0)
+    g = torch.Generator().manual_seed(0)
+    res = {'what': 'SDUNet forward, SD-1.5 configuration, random-init weights', 'rows': a.rows, 'latent': [4, 64, 64], 'context': [77, 768],
+           'distinct_contexts': 2, 'algorithmic_flops_per_forward': flops, 'algorithmic_flops_per_row': per_row,
+           'peak_flops_16bit_dense': PEAK_16BIT_DENSE, 'device': torch.cuda.get_device_name(0), 'iters': a.iters, 'warmup': a.warmup, 'dtypes': {}}
+    x32 = torch.randn(a.rows, 4, 64, 64, generator=g)
+    c2 = torch.randn(2, 77, 768, generator=g)
+    for name in a.dtypes.split(','):
+        dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[name]
+        unet = SDUNet(sd, device='cuda', dtype=dt)
+        x = x32.to('cuda', dt)
+        ehs = torch.cat([c2[:1].expand(a.rows // 2, -1, -1), c2[1:].expand(a.rows - a.rows // 2, -1, -1)]).to('cuda', dt).contiguous()
+        t = torch.tensor(501, device='cuda')
+        for _ in range(a.warmup):
+            out = unet(x, t, encoder_hidden_states=ehs)[0]
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(a.iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = unet(x, t, encoder_hidden_states=ehs)[0]
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1))
+        ms = statistics.median(times)
+        shares, launches = op_shares(unet, x, t, ehs)
+        res['dtypes'][name] = {'ms_per_forward': round(ms, 3), 'ms_min': round(min(times), 3), 'ms_max': round(max(times), 3),
+                               'rows_per_s': round(a.rows / ms * 1e3, 1), 'tflops_algorithmic': round(flops / ms / 1e9, 1),
+                               'fraction_of_dense_16bit_peak_end_to_end': round(flops / (ms * 1e-3) / PEAK_16BIT_DENSE, 4),
+                               'time_share_by_op_family': shares, 'op_calls_per_forward': launches, 'output_finite': bool(torch.isfinite(out).all())}
+        del unet
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
