@@ -47,6 +47,10 @@ SIGNATURES = {
     'dts_cross_attention': [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p],
     'dts_layer_norm': [_p, _p, _i, _i64, _i, _f, _p, _p, _p],
     'dts_geglu': [_p, _p, _i, _i64, _i, _p],
+    'dts_patchify': [_p, _p, _i, _i, _i, _i, _i, _p],
+    'dts_vit_tokens': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'dts_gelu': [_p, _p, _i, _i64, _i, _p],
+    'dts_vit_head': [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p],
     'dts_linear': [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     'dts_pos_embedding': [_p, _p, _p, _i, _i, _i, _p],
     'dts_edm_precond_in': [_p, _p, _i, _f, _p, _p, _i, _i, _p],
@@ -76,7 +80,7 @@ SIGNATURES = {
 OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 113              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 114              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

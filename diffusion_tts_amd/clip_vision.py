@@ -1,0 +1,237 @@
+"""The image tower of CLIP on the HIP kernels: drop-in for `CLIPModel.get_image_features(pixel_values=...)` in the scorer of the SD
+search loop (scorers.CLIPScorer, sd/scorers.py:175-183 of the reference), i.e. for CLIPVisionTransformer.forward + visual_projection of
+transformers (models/clip/modeling_clip.py: CLIPVisionEmbeddings, CLIPEncoderLayer, CLIPAttention, CLIPMLP).
+
+Every decoded candidate of a search passes through these 24 layers at 257 tokens (ViT-L/14); here they run on this build's kernels:
+  patch embedding Conv2d(3, hidden, p, stride p) -> dts_patchify (patch rows) + one 1x1 dts_conv2d (weight flattened, zero-padded to 64 columns)
+  class token + position table               -> dts_vit_tokens
+  pre_layrnorm, layer_norm1 / 2              -> dts_layer_norm
+  q_proj | k_proj | v_proj                   -> ONE 1x1 dts_conv2d (rows and biases stacked at load time)
+  softmax(q k^T / sqrt d) v                  -> dts_attention
+  out_proj, fc2                              -> 1x1 dts_conv2d with the bias and the residual add in the epilogue
+  fc1 + activation                           -> 1x1 dts_conv2d + dts_gelu (quick-GELU or erf GELU, in place)
+  post_layernorm(token 0), visual_projection -> dts_vit_head + dts_linear (f32)
+Activations are [n, tokens, 1, channels] in `dtype` (float16 or bfloat16): this is a 16-bit THROUGHPUT mode of the scorer.  The reference
+scores in float32; there is no float32 or split-precision form of this tower (full-precision CLIP stays the transformers module).
+
+Parameters: a state dict with transformers' key names (`vision_model.*`, `visual_projection.weight`).  Shapes the kernels do not take are
+refused by name at construction (check_config).  The forward makes no device-to-host synchronisation and no data-dependent step.
+"""
+import types
+
+import torch
+
+from . import ops
+
+PREFIX = 'vision_model.'
+PROJECTION = 'visual_projection.weight'
+# transformers' CLIPVisionConfig defaults: config.json stores only what differs from them
+CONFIG_DEFAULTS = {'hidden_size': 768, 'intermediate_size': 3072, 'num_hidden_layers': 12, 'num_attention_heads': 12, 'image_size': 224,
+                   'patch_size': 32, 'hidden_act': 'quick_gelu', 'layer_norm_eps': 1e-5, 'projection_dim': 512}
+
+
+def check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim=None):
+    """Raises ValueError naming every setting of a CLIP vision configuration that this build's kernels do not take, with its value."""
+    bad = []
+    if dtype not in (torch.float16, torch.bfloat16):
+        bad.append(f'dtype={dtype} (float16 or bfloat16: there is no float32 form of this tower)')
+    if hidden_size <= 0 or hidden_size % 64:
+        bad.append(f'hidden_size={hidden_size} is not a multiple of 64 (the channel granularity of dts_conv2d)')
+    if hidden_size > 2048:
+        bad.append(f'hidden_size={hidden_size} exceeds 2048 (the row dts_layer_norm holds in registers)')
+    if num_attention_heads <= 0 or hidden_size % num_attention_heads or hidden_size // num_attention_heads not in (64, 128, 256):
+        hd = hidden_size / num_attention_heads if num_attention_heads > 0 else float('nan')
+        bad.append(f'head dim {hd:g} (hidden_size={hidden_size} / num_attention_heads={num_attention_heads}) is not one of '
+                   f'dts_attention\'s 64 / 128 / 256')
+    if intermediate_size <= 0 or intermediate_size % 64:
+        bad.append(f'intermediate_size={intermediate_size} is not a multiple of 64')
+    if patch_size <= 0 or image_size <= 0 or image_size % patch_size:
+        bad.append(f'image_size={image_size} is not a multiple of patch_size={patch_size}')
+    if hidden_act not in ops.GELU_KINDS:
+        bad.append(f'hidden_act={hidden_act!r} (dts_gelu computes {sorted(ops.GELU_KINDS)})')
+    if projection_dim is not None and projection_dim <= 0:
+        bad.append(f'projection_dim={projection_dim}')
+    if bad:
+        raise ValueError('CLIPVisionTower: ' + '; '.join(bad))
+
+
+def patch_weight_matrix(w, kpad=None):
+    """patch_embedding.weight [hidden, 3, p, p] -> [hidden, kpad]: each filter flattened in (c, py, px) order -- the column order of
+    ops.patchify -- followed by zero columns up to kpad (default ops.patch_kpad(p))."""
+    hidden, cin, p, p2 = w.shape
+    if cin != 3 or p != p2:
+        raise ValueError(f'CLIPVisionTower: patch_embedding.weight {tuple(w.shape)} is not [hidden, 3, p, p]')
+    kpad = ops.patch_kpad(p) if kpad is None else kpad
+    out = torch.zeros((hidden, kpad), dtype=w.dtype, device=w.device)
+    out[:, :3 * p * p] = w.reshape(hidden, 3 * p * p)
+    return out
+
+
+def stack_qkv(sd, key):
+    """(weight [3C, C], bias [3C]) of one projection whose output is q | k | v blocks, from `key`.{q,k,v}_proj.{weight,bias}"""
+    w = torch.cat([sd[f'{key}.{n}_proj.weight'] for n in 'qkv'], 0)
+    b = torch.cat([sd[f'{key}.{n}_proj.bias'] for n in 'qkv'], 0)
+    return w, b
+
+
+def vision_config(cfg):
+    """the vision settings of a config.json dict (a CLIPModel's, with `vision_config` nested, or a CLIPVisionModelWithProjection's own),
+    absent keys taking transformers' defaults; projection_dim is the top-level one of a CLIPModel (the shape of visual_projection)"""
+    vc = cfg.get('vision_config') or cfg
+    out = {k: vc.get(k, d) for k, d in CONFIG_DEFAULTS.items()}
+    if 'vision_config' in cfg and 'projection_dim' in cfg:
+        out['projection_dim'] = cfg['projection_dim']
+    return out
+
+
+def read_vision_tensors(path):
+    """(vision settings, state dict) of a local directory holding `config.json` + `model.safetensors` (what `save_pretrained` writes):
+    only `vision_model.*` and `visual_projection.weight` are read -- the text tower never leaves disk.  Host tensors; no GPU needed."""
+    import json
+    import os
+    from safetensors import safe_open
+    cfg_file, st_file = os.path.join(path, 'config.json'), os.path.join(path, 'model.safetensors')
+    if not os.path.exists(cfg_file):
+        raise FileNotFoundError(f'{path}: no config.json')
+    if not os.path.exists(st_file):
+        raise FileNotFoundError(f'{path}: no model.safetensors (a .bin pickle is not read: convert it to safetensors)')
+    with open(cfg_file) as f:
+        cfg = vision_config(json.load(f))
+    sd = {}
+    with safe_open(st_file, framework='pt', device='cpu') as f:
+        for k in f.keys():
+            if k.startswith(PREFIX) or k == PROJECTION:
+                sd[k] = f.get_tensor(k)
+    if not sd:
+        raise ValueError(f'{st_file}: no {PREFIX}* tensors')
+    return cfg, sd
+
+
+class CLIPVisionTower:
+    def __init__(self, state_dict, hidden_size=1024, num_attention_heads=16, intermediate_size=4096, num_hidden_layers=24, image_size=224,
+                 patch_size=14, hidden_act='quick_gelu', layer_norm_eps=1e-5, projection_dim=None, device='cuda', dtype=torch.float16):
+        """The defaults are ViT-L/14's (openai/clip-vit-large-patch14, the reference's scorer).  projection_dim None: taken from
+        visual_projection.weight."""
+        check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim)
+        if not torch.cuda.is_available():
+            raise RuntimeError('CLIPVisionTower (HIP) needs a GPU: there is no CPU fallback in this package')
+        self.device, self.dtype = torch.device(device), dtype
+        self.hidden, self.heads, self.inter, self.layers_n = int(hidden_size), int(num_attention_heads), int(intermediate_size), int(num_hidden_layers)
+        self.image_size, self.patch, self.act, self.eps = int(image_size), int(patch_size), hidden_act, float(layer_norm_eps)
+        self.grid = self.image_size // self.patch
+        self.tokens = self.grid * self.grid + 1
+        self.scale = (self.hidden // self.heads) ** -0.5
+        self.kpad = ops.patch_kpad(self.patch)
+        self.proj_dim = projection_dim
+        self.config = types.SimpleNamespace(hidden_size=self.hidden, num_attention_heads=self.heads, intermediate_size=self.inter,
+                                            num_hidden_layers=self.layers_n, image_size=self.image_size, patch_size=self.patch,
+                                            hidden_act=self.act, layer_norm_eps=self.eps, projection_dim=projection_dim)
+        self.rows = 0
+        self._load(state_dict)
+
+    @classmethod
+    def from_clip_model(cls, model, dtype=torch.float16, device='cuda'):
+        """From a `transformers.CLIPModel` or `CLIPVisionModelWithProjection`: only its state dict and configuration are read, no reference
+        to the module is kept."""
+        vc = getattr(model.config, 'vision_config', None) or model.config
+        sd = {k: v for k, v in model.state_dict().items() if k.startswith(PREFIX) or k == PROJECTION}
+        return cls(sd, hidden_size=vc.hidden_size, num_attention_heads=vc.num_attention_heads, intermediate_size=vc.intermediate_size,
+                   num_hidden_layers=vc.num_hidden_layers, image_size=vc.image_size, patch_size=vc.patch_size, hidden_act=vc.hidden_act,
+                   layer_norm_eps=vc.layer_norm_eps, device=device, dtype=dtype)
+
+    @classmethod
+    def from_pretrained(cls, path, dtype=torch.float16, device='cuda'):
+        """Reads a local directory of `config.json` + `model.safetensors` (read_vision_tensors: the vision tensors only)."""
+        cfg, sd = read_vision_tensors(path)
+        cfg.pop('projection_dim')                     # the tensor's own shape decides
+        return cls(sd, device=device, dtype=dtype, **cfg)
+
+    # ---- parameters ----------------------------------------------------------------------------
+    def _f(self, t):
+        return t.detach().to(self.device, torch.float32).contiguous()
+
+    def _pack(self, w, b=None):
+        """f32 weight [O, I] (+ bias) on the device -> (packed [O][1][1][I] in the activation dtype, f32 bias)"""
+        return ops.pack_conv_weight(w[:, :, None, None].contiguous(), self.dtype), (None if b is None else b.contiguous())
+
+    def _check_shapes(self, sd):
+        """the parameters must be those of the configuration this object was given: a mismatch is named here, not met as a reshape error"""
+        C, I, L, p, T = self.hidden, self.inter, self.layers_n, self.patch, self.tokens
+        last = f'{PREFIX}encoder.layers.{L - 1}'
+        want = {f'{PREFIX}embeddings.class_embedding': (C,), f'{PREFIX}embeddings.patch_embedding.weight': (C, 3, p, p),
+                f'{PREFIX}embeddings.position_embedding.weight': (T, C), f'{PREFIX}pre_layrnorm.weight': (C,),
+                f'{PREFIX}post_layernorm.weight': (C,), f'{last}.self_attn.q_proj.weight': (C, C), f'{last}.mlp.fc1.weight': (I, C),
+                f'{last}.mlp.fc2.weight': (C, I)}
+        for key, shape in want.items():
+            if key not in sd:
+                raise ValueError(f'CLIPVisionTower: the state dict has no {key!r} (num_hidden_layers={L})')
+            if tuple(sd[key].shape) != shape:
+                raise ValueError(f'CLIPVisionTower: {key} has shape {tuple(sd[key].shape)}, but hidden_size={C}, intermediate_size={I}, '
+                                 f'image_size={self.image_size}, patch_size={p} ask for {shape}')
+        if f'{PREFIX}encoder.layers.{L}.layer_norm1.weight' in sd:
+            raise ValueError(f'CLIPVisionTower: the state dict has more than num_hidden_layers={L} layers')
+        if f'{PREFIX}embeddings.patch_embedding.bias' in sd:
+            raise ValueError('CLIPVisionTower: a patch embedding with a bias is not CLIP\'s')
+        if PROJECTION not in sd:
+            raise ValueError(f'CLIPVisionTower: the state dict has no {PROJECTION!r} (a CLIPModel or CLIPVisionModelWithProjection is needed)')
+        proj = tuple(sd[PROJECTION].shape)
+        if len(proj) != 2 or proj[1] != C or (self.proj_dim is not None and proj[0] != self.proj_dim):
+            raise ValueError(f'CLIPVisionTower: {PROJECTION} has shape {proj}, but hidden_size={C}, projection_dim={self.proj_dim}')
+
+    def _load(self, sd):
+        self._check_shapes(sd)
+        e = PREFIX + 'embeddings.'
+        self.w_patch, _ = self._pack(patch_weight_matrix(self._f(sd[e + 'patch_embedding.weight']), self.kpad))
+        self.cls, self.pos = self._f(sd[e + 'class_embedding']), self._f(sd[e + 'position_embedding.weight'])
+        ln = lambda key: (self._f(sd[key + '.weight']), self._f(sd[key + '.bias']))
+        self.pre_ln, self.post_ln = ln(PREFIX + 'pre_layrnorm'), ln(PREFIX + 'post_layernorm')
+        self.layers = []
+        for i in range(self.layers_n):
+            key = f'{PREFIX}encoder.layers.{i}'
+            P = types.SimpleNamespace(ln1=ln(key + '.layer_norm1'), ln2=ln(key + '.layer_norm2'))
+            wq, bq = stack_qkv(sd, key + '.self_attn')
+            P.w_qkv, P.b_qkv = self._pack(self._f(wq), self._f(bq))
+            P.w_o, P.b_o = self._pack(self._f(sd[key + '.self_attn.out_proj.weight']), self._f(sd[key + '.self_attn.out_proj.bias']))
+            P.w_fc1, P.b_fc1 = self._pack(self._f(sd[key + '.mlp.fc1.weight']), self._f(sd[key + '.mlp.fc1.bias']))
+            P.w_fc2, P.b_fc2 = self._pack(self._f(sd[key + '.mlp.fc2.weight']), self._f(sd[key + '.mlp.fc2.bias']))
+            self.layers.append(P)
+        self.w_proj = self._f(sd[PROJECTION])                            # f32 [projection_dim, hidden], no bias
+        self.proj_dim = self.config.projection_dim = self.w_proj.shape[0]
+        torch.cuda.synchronize(self.device)
+
+    # ---- forward -------------------------------------------------------------------------------
+    @torch.no_grad()
+    def __call__(self, pixel_values):
+        """pixel_values [n, 3, image_size, image_size] (what CLIPImageProcessor / clip_preprocess.DevicePreprocessor make)
+        -> float32 [n, projection_dim], the `image_embeds` before normalisation (CLIPModel.get_image_features)."""
+        S, C, T, g = self.image_size, self.hidden, self.tokens, self.grid
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
+            raise ValueError(f'CLIPVisionTower: pixel_values {tuple(pixel_values.shape)} is not [n, 3, {S}, {S}]')
+        n = pixel_values.shape[0]
+        x = pixel_values.to(self.device, torch.float32).contiguous()
+        rows = ops.patchify(x, self.patch, self.dtype, self.kpad)                                  # [n, g*g, kpad]
+        emb = ops.conv2d(rows.view(n, g, g, self.kpad), self.w_patch)                              # the patch embedding has no bias
+        h = ops.vit_tokens(emb.view(n, g * g, C), self.cls, self.pos)
+        h = ops.layer_norm(h, *self.pre_ln, eps=self.eps).view(n, T, 1, C)
+        for P in self.layers:
+            # CLIPEncoderLayer.forward: x + out_proj(attention(layer_norm1(x))), then x + fc2(act(fc1(layer_norm2(x))))
+            y = ops.layer_norm(h, *P.ln1, eps=self.eps)
+            qkv = ops.conv2d(y, P.w_qkv, P.b_qkv)
+            a = ops.attention(qkv.view(n, T, 3 * C), self.heads, self.scale)
+            h = ops.conv2d(a.view(n, T, 1, C), P.w_o, P.b_o, residual=h)
+            y = ops.layer_norm(h, *P.ln2, eps=self.eps)
+            f = ops.conv2d(y, P.w_fc1, P.b_fc1)
+            ops.gelu(f, self.act, out=f)
+            h = ops.conv2d(f, P.w_fc2, P.b_fc2, residual=h)
+        pooled = ops.vit_head(h.view(n, T, C), *self.post_ln, eps=self.eps)                        # f32 [n, C]: the class token only
+        self.rows += n
+        return ops.linear(pooled, self.w_proj)
+
+    forward = __call__
+
+    def flops(self, n=1):
+        """algorithmic FLOPs (2 per multiply-add) of a forward over n images, counted from the layer shapes: the matrix products of the patch
+        embedding, the four projections, the two attention products, the MLP and the output projection"""
+        C, I, T, L = self.hidden, self.inter, self.tokens, self.layers_n
+        per_layer = 2 * T * C * 3 * C + 2 * T * C * C + 2 * 2 * T * T * C + 2 * 2 * T * C * I
+        return n * (2 * (T - 1) * 3 * self.patch * self.patch * C + L * per_layer + 2 * C * self.proj_dim)

@@ -554,6 +554,71 @@ def geglu(x):
     return out
 
 
+# ---- CLIP vision tower ----------------------------------------------------------------------------
+def patch_kpad(patch):
+    """columns of a patch row: 3*patch*patch rounded up to conv2d's 64-channel granularity (588 -> 640 at patch 14, 3072 at patch 32)"""
+    return (3 * patch * patch + 63) // 64 * 64
+
+
+def patchify(x, patch, dtype, kpad=None, out=None):
+    """pixel_values float32 NCHW [n, 3, S, S] -> patch rows [n, (S/patch)^2, kpad] in float16 / bfloat16: column (c*patch + py)*patch + px of
+    row gy*(S/patch) + gx is x[n, c, gy*patch + py, gx*patch + px] rounded once, columns from 3*patch*patch on are zero (dts_patchify).
+    kpad defaults to patch_kpad(patch)."""
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError(f'patchify: x {tuple(x.shape)} is not [n, 3, S, S]')
+    n, _, S, _ = x.shape
+    if patch <= 0 or S % patch:
+        raise ValueError(f'patchify: image size {S} is not a multiple of the patch size {patch}')
+    kpad = patch_kpad(patch) if kpad is None else int(kpad)
+    g = S // patch
+    if out is None:
+        out = torch.empty((n, g * g, kpad), dtype=dtype, device=x.device)
+    elif tuple(out.shape) != (n, g * g, kpad):
+        raise ValueError(f'patchify: out {tuple(out.shape)} != {(n, g * g, kpad)}')
+    _call('dts_patchify', _ptr(x, 'x', torch.float32), _ptr(out, 'out', dtype), dt_code(dtype), n, S, patch, kpad)
+    return out
+
+
+def vit_tokens(patches, cls, pos):
+    """patches [n, t-1, c] float16 / bfloat16, cls float32 [c], pos float32 [t, c] -> tokens [n, t, c]: row 0 = cls + pos[0], row 1 + p =
+    patches[:, p] + pos[1 + p], summed in float32 and rounded once (dts_vit_tokens)."""
+    n, tp, c = patches.shape
+    if tuple(cls.shape) != (c,) or tuple(pos.shape) != (tp + 1, c):
+        raise ValueError(f'vit_tokens: cls {tuple(cls.shape)} / pos {tuple(pos.shape)} for patches {tuple(patches.shape)}')
+    out = torch.empty((n, tp + 1, c), dtype=patches.dtype, device=patches.device)
+    _call('dts_vit_tokens', _ptr(patches, 'patches'), _ptr(cls, 'cls', torch.float32), _ptr(pos, 'pos', torch.float32), _ptr(out),
+          dt_code(patches.dtype), n, tp + 1, c)
+    return out
+
+
+GELU_KINDS = {'quick_gelu': 0, 'gelu': 1}
+
+
+def gelu(x, kind='quick_gelu', out=None):
+    """Elementwise over a contiguous float16 / bfloat16 tensor whose element count is a multiple of 8 (dts_gelu).  kind 'quick_gelu':
+    x * sigmoid(1.702 x); 'gelu': the exact (erf) GELU.  out may be x itself (in place)."""
+    if kind not in GELU_KINDS:
+        raise ValueError(f'gelu: kind {kind!r} (one of {sorted(GELU_KINDS)})')
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape:
+        raise ValueError(f'gelu: out {tuple(out.shape)} != x {tuple(x.shape)}')
+    _call('dts_gelu', _ptr(x, 'x'), _ptr(out, 'out', x.dtype), dt_code(x.dtype), x.numel(), GELU_KINDS[kind])
+    return out
+
+
+def vit_head(tokens, gamma, beta, eps=1e-5):
+    """tokens [n, t, c] float16 / bfloat16 -> float32 [n, c] = LayerNorm(tokens[:, 0]) * gamma + beta: the class token only, the other
+    tokens are not read (dts_vit_head); gamma, beta float32 [c].  The projection follows as ops.linear."""
+    n, t, c = tokens.shape
+    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
+        raise ValueError(f'vit_head: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} for {c} channels')
+    out = torch.empty((n, c), dtype=torch.float32, device=tokens.device)
+    _call('dts_vit_head', _ptr(tokens, 'tokens'), _ptr(out), dt_code(tokens.dtype), n, t, c, float(eps), _ptr(gamma, 'gamma', torch.float32),
+          _ptr(beta, 'beta', torch.float32))
+    return out
+
+
 def stride2_conv_weight(w, cpad=None):
     """The weight of Conv2d(kernel 3, stride 2, padding 1) (diffusers Downsample2D) as a 3x3 padding-1 stride-1 convolution over
     space_to_depth2(x): output pixel (i, j) reads input rows 2i - 1, 2i, 2i + 1 = phase 1 of pixel block i - 1 and phases 0, 1 of block i, so

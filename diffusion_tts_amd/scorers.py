@@ -7,7 +7,8 @@
   CompressibilityScorer edm/scorers.py:176-243 -> host PIL JPEG byte length, unchanged: entropy coding is a CPU
                        codec and an opaque callable to the search loop.
   CLIPScorer           sd/scorers.py:149-213   -> HF CLIP image/text towers (third-party arithmetic, run as PyTorch-ROCm
-                       modules on the GPU) + dts_cosine_rows (HIP) for the normalise-and-dot tail.  The reference fetches
+                       modules on the GPU) + dts_cosine_rows (HIP) for the normalise-and-dot tail; with vision_tower='hip' the
+                       image tower is clip_vision.CLIPVisionTower on the HIP kernels (16-bit; the text tower stays transformers).  The reference fetches
                        `openai/clip-vit-large-patch14`; there is no network here, so the model / image processor / tokenizer
                        can be injected (random-init `CLIPModel(CLIPConfig)` for BASELINE config 4).
 """
@@ -185,8 +186,13 @@ class CLIPScorer(Scorer):
     batched = True        # one call scores a whole list / batch of images (the SD loop then calls it once per decoded batch)
 
     def __init__(self, model_id='openai/clip-vit-large-patch14', dtype=torch.float32, model=None, image_processor=None,
-                 tokenizer=None, processor=None, device='cuda', device_preprocess=True):
-        """device_preprocess: run the image processor's resize / rescale / normalise on the GPU (clip_preprocess.DevicePreprocessor:
+                 tokenizer=None, processor=None, device='cuda', device_preprocess=True, vision_tower='transformers',
+                 tower_dtype=torch.float16):
+        """vision_tower: 'transformers' (default: `model.get_image_features`, the reference's arithmetic in the model's own precision) |
+        'hip' (clip_vision.CLIPVisionTower built from `model`: the image tower on this build's kernels with `tower_dtype` = float16 /
+        bfloat16 activations -- a 16-bit THROUGHPUT mode of the scorer, where the reference scores in float32; a configuration the kernels
+        do not take is refused by name, there is no fallback).  The text branch, its cache and the pre-processing are the same either way.
+        device_preprocess: run the image processor's resize / rescale / normalise on the GPU (clip_preprocess.DevicePreprocessor:
         Pillow's integer bicubic + the processor's own value table, identical pixel_values) whenever the images are square uint8 GPU
         tensors and the processor has the stock configuration; False keeps the reference's host path (images.cpu() + PIL) always."""
         super().__init__(dtype)
@@ -214,7 +220,13 @@ class CLIPScorer(Scorer):
             tokenizer = ByteTokenizer(tc.vocab_size, getattr(tc, 'bos_token_id', None), getattr(tc, 'eos_token_id', None))
             if not (0 <= tokenizer.bos < tc.vocab_size and 0 <= tokenizer.eos < tc.vocab_size):
                 tokenizer = ByteTokenizer(tc.vocab_size)
+        if vision_tower not in ('transformers', 'hip'):
+            raise ValueError(f"CLIPScorer: vision_tower must be 'transformers' or 'hip', got {vision_tower!r}")
         self.clip = model.to(self.device).eval()
+        self.vision_tower, self._tower = vision_tower, None
+        if vision_tower == 'hip':
+            from .clip_vision import CLIPVisionTower
+            self._tower = CLIPVisionTower.from_clip_model(self.clip, dtype=tower_dtype, device=self.device)
         self.image_processor, self.tokenizer = image_processor, tokenizer
         self._text_cache = {}
         self.device_preprocessed = 0                                   # images whose pixel_values were built on the GPU
@@ -238,7 +250,10 @@ class CLIPScorer(Scorer):
             elif isinstance(images, torch.Tensor):
                 images = images.cpu()
             pix = self.image_processor(images=images, return_tensors='pt', do_rescale=do_rescale)['pixel_values']
-        img_emb = _features(self.clip.get_image_features(pixel_values=pix.to(self.dtype).to(dev))).float().contiguous()
+        if self._tower is not None:
+            img_emb = self._tower(pix.to(dev))                         # f32 [n, projection_dim] from 16-bit activations
+        else:
+            img_emb = _features(self.clip.get_image_features(pixel_values=pix.to(self.dtype).to(dev))).float().contiguous()
         n = img_emb.shape[0]
         if prompts is None:
             return torch.zeros(n, device=dev)                          # :186-188

@@ -42,14 +42,15 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 113        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 114        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
                                      110: dts_candidate_noise_sd takes the three scalars of the reference's product separately (scale [n][3]);
                                      111: dts_conv_args.skip_* (a block's 1x1 skip convolution folded into its second 3x3), dts_conv_folds_skip;
                                      112: dts_resample_fir, dts_space_to_depth2 (the NCSN++ options of SongUNet);
-                                     113: dts_cross_attention, dts_layer_norm, dts_geglu (the SD U-Net's transformer blocks)) */
+                                     113: dts_cross_attention, dts_layer_norm, dts_geglu (the SD U-Net's transformer blocks);
+                                     114: dts_patchify, dts_vit_tokens, dts_gelu, dts_vit_head (the CLIP scorer's vision tower)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -201,6 +202,27 @@ int dts_layer_norm(const void* x, void* out, int dtype, int64_t rows, int c, flo
 /* GEGLU (diffusers activations.py GEGLU): x [rows][2*inner] -> out[r][j] = x[r][j] * gelu(x[r][inner + j]), the exact (erf) GELU;
  * DTS_BF16 / DTS_F16 storage, f32 arithmetic; inner % 8 == 0. */
 int dts_geglu(const void* x, void* out, int dtype, int64_t rows, int inner, dts_stream s);
+
+/* ---- K18-K21: the CLIP scorer's vision tower (transformers models/clip/modeling_clip.py: CLIPVisionEmbeddings, CLIPMLP, the pooled head) ---- */
+/* Patch rows for the patch embedding Conv2d(3, hidden, patch, stride = patch, bias = False): x f32 NCHW [n][3][size][size] (pixel_values) ->
+ * out [n][g*g][kpad] in DTS_BF16 / DTS_F16, g = size / patch; column (c*patch + py)*patch + px = x[n][c][gy*patch + py][gx*patch + px] rounded
+ * once (nearest-even) -- the flattening order of the conv weight [hidden][3][patch][patch] -- and columns 3*patch*patch .. kpad-1 are written
+ * as zeros.  kpad % 8 == 0 (in use: 3*patch*patch rounded up to dts_conv2d's 64-channel granularity, 588 -> 640 at patch 14), size % patch == 0.
+ * The source is read element-wise (a patch row of 14 floats is not 16-byte aligned); out is stored in whole 16-byte vectors.  The embedding
+ * itself is one 1x1 dts_conv2d over [n][g][g][kpad] with the weight flattened and zero-padded the same way. */
+int dts_patchify(const float* x, void* out, int dtype, int n, int size, int patch, int kpad, dts_stream s);
+/* tokens [n][t][c]: tokens[n][0] = cls + pos[0], tokens[n][1 + p] = patches[n][p] + pos[1 + p]; patches [n][t-1][c] and tokens in DTS_BF16 /
+ * DTS_F16, cls f32 [c], pos f32 [t][c] (CLIPVisionEmbeddings: class_embedding, position_embedding.weight); the sum is formed in f32 and rounded
+ * once.  c % 8 == 0, t >= 2. */
+int dts_vit_tokens(const void* patches, const float* cls, const float* pos, void* tokens, int dtype, int n, int t, int c, dts_stream s);
+/* Elementwise GELU over `count` 16-bit values (count % 8 == 0; out may be x): kind 0 = quick-GELU x * sigmoid(1.702 x) (hidden_act of the OpenAI
+ * CLIP checkpoints), kind 1 = the exact (erf) GELU x * erfc(-x / sqrt 2) / 2 (the LAION towers).  f32 arithmetic; finite over the whole storage
+ * range (the most negative finite input gives -0, not inf * 0). */
+int dts_gelu(const void* x, void* out, int dtype, int64_t count, int kind, dts_stream s);
+/* Pooled head, first half: out f32 [n][c] = LayerNorm(tokens[n][0][:]) * gamma + beta (CLIPVisionTransformer post_layernorm of the class token;
+ * biased variance, statistics in f32 as dts_layer_norm) -- token 0 only, the other t - 1 tokens are never read.  tokens [n][t][c] DTS_BF16 /
+ * DTS_F16; c % 8 == 0, c <= 2048.  visual_projection follows as dts_linear on the f32 rows. */
+int dts_vit_head(const void* tokens, float* out, int dtype, int n, int t, int c, float eps, const float* gamma, const float* beta, dts_stream s);
 
 /* ---- K7/K8: embedding MLP pieces and EDM preconditioning (networks.py:200-206,437-447,654-668) ---- */
 /* y[m][n] = act_out( act_in(x[m][:]) . w[n][:] + bias[n] (+ y[m][n] if accumulate) ); all f32; act: 0 none, 1 SiLU */

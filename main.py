@@ -18,6 +18,8 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   (throughput modes: ~2.8x faster again, but a near-tied pick differs after ~10 decisions and the result is another sample)
     --unet      : SD backend: diffusers (default: the stock UNet2DConditionModel) | hip (sd_unet.SDUNet on this build's kernels, read from
                   $DTS_SD_UNET_DIR or the cached snapshot's unet/; no fallback).  --vae hip|diffusers likewise (default hip)
+    --clip-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel image tower, float32 like the reference) | hip
+                  (clip_vision.CLIPVisionTower on this build's kernels, float16 activations: a 16-bit throughput mode of the scorer; no fallback)
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`; the N candidates of every
@@ -34,9 +36,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def get_scorer(backend, scorer_name, device, compute_dtype=None):
+def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='transformers', clip_model=None):
     """main.py:60-71 of the reference.  compute_dtype: the search's --dtype; the ImageNet classifier runs in the search's own mode for the two parity
-    modes (float32, f16x3) and in float16 otherwise (also beside a bfloat16 denoiser: scorers.ImageNetScorer)."""
+    modes (float32, f16x3) and in float16 otherwise (also beside a bfloat16 denoiser: scorers.ImageNetScorer).  clip_tower: --clip-tower;
+    clip_model: a transformers.CLIPModel to score with instead of the cached checkpoint (scorers.CLIPScorer model=)."""
     from diffusion_tts_amd import scorers as S
     if scorer_name == 'brightness':
         return S.BrightnessScorer(dtype=torch.float32)
@@ -45,7 +48,7 @@ def get_scorer(backend, scorer_name, device, compute_dtype=None):
     if scorer_name == 'imagenet' and backend == 'edm':
         return S.ImageNetScorer(dtype=torch.float32, device=device, compute_dtype=compute_dtype if compute_dtype in (torch.float32, 'f16x3') else torch.float16)
     if scorer_name == 'clip' and backend == 'sd':
-        return S.CLIPScorer(dtype=torch.float32, device=device)        # local HF cache only; raises with instructions otherwise
+        return S.CLIPScorer(dtype=torch.float32, device=device, model=clip_model, vision_tower=clip_tower)    # local HF cache only; raises with instructions otherwise
     raise ValueError(f"Unknown or invalid scorer '{scorer_name}' for backend '{backend}'")
 
 
@@ -117,7 +120,7 @@ def main_sd(args):
     tok = CLIPTokenizer.from_pretrained(model_id, subfolder='tokenizer', local_files_only=True)
     te = CLIPTextModel.from_pretrained(model_id, subfolder='text_encoder', torch_dtype=torch.float16, local_files_only=True).to(dev)
 
-    scorer = get_scorer('sd', args.scorer, dev)
+    scorer = get_scorer('sd', args.scorer, dev, clip_tower=getattr(args, 'clip_tower', 'transformers'))
     pipe = SDSearchPipeline(unet, vae, device=dev, text_encoder=te, tokenizer=tok)     # encodes the prompt itself (pipeline...:976-992)
     params = {'N': args.N, 'lambda': args.lambda_, 'eps': args.eps, 'K': args.K, 'B': args.B, 'S': args.S}
     torch.manual_seed(args.seed)                                                       # same host RNG stream on every rank
@@ -138,7 +141,7 @@ def main_sd(args):
     return best
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser(description='Unified Diffusion Image Generator (EDM/SD), MI355X-native hot path',
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument('--backend', type=str, choices=['edm', 'sd'], required=True, help='Backend: edm or sd')
@@ -162,11 +165,18 @@ def main(argv=None):
                         help="SD backend: 'hip' = this build's VAE decoder (an error if its safetensors cannot be read), 'diffusers' = the stock module")
     parser.add_argument('--unet', type=str, default='diffusers', choices=['hip', 'diffusers'],
                         help="SD backend: 'hip' = this build's U-Net on the HIP kernels (an error if its safetensors cannot be read), 'diffusers' = the stock module")
+    parser.add_argument('--clip-tower', dest='clip_tower', type=str, default='transformers', choices=['transformers', 'hip'],
+                        help="SD backend, --scorer clip: 'hip' = the CLIP image tower on this build's kernels in float16 (a 16-bit throughput mode: the "
+                             "reference scores in float32; an error if the kernels do not take the model's shape), 'transformers' = the stock module")
     parser.add_argument('--seeds', type=str, default=None, help='bulk mode: seeds, e.g. 0-63 or 1,2,5-10 (one image per seed)')
     parser.add_argument('--outdir', type=str, default='out', help='bulk mode: output directory')
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')
     parser.add_argument('--class', dest='class_idx', type=int, default=None, help='bulk mode: class label (default: per-seed random)')
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     if args.backend == 'sd' and args.scorer == 'imagenet':
         raise ValueError('imagenet scorer is only available for edm backend')
