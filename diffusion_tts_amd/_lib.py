@@ -68,6 +68,7 @@ SIGNATURES = {
     'dts_u8_to_unit_f32': [_p, _p, _i64, _p],
     'dts_resample_u8': [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p],
     'dts_lut_u8_f32': [_p, _p, _p, _i, _i, _i, _p],
+    'dts_jpeg_size': [_p, _p, _i, _i, _i, _p, _p, _i64, _p, _p],
     'dts_cosine_rows': [_p, _p, _i, _p, _i, _i, _p],
     'dts_attnpool_tokens': [_p, _p, _p, _i, _i, _i, _i, _p],
     'dts_take_token': [_p, _i, _p, _i, _i, _i, _i, _p],
@@ -77,10 +78,11 @@ SIGNATURES = {
     'dts_cfg_combine': [_p, _p, _f, _p, _i, _i64, _p],
     'dts_ddim_candidates': [_p, _p, _p, _p, _p, _i, _f, _f, _f, _i, _i64, _p],
 }
-OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64)}
+OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64),
+         'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 114              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 115              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

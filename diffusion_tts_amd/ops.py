@@ -772,6 +772,70 @@ def lut_u8_f32(img, lut):
     return out
 
 
+# ---- JPEG byte length (the compressibility reward) -------------------------------------------------
+# ITU T.81 Annex K.1 / K.2: the luminance and chrominance quantisation tables a quality setting scales, natural (row-major) order
+_JPEG_BASE_LUMA = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                   18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99]
+_JPEG_BASE_CHROMA = [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32
+_JPEG_QTAB, _JPEG_WS = {}, {}
+
+
+def _jpeg_quality(quality):
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f'jpeg: quality must be an integer in [1, 100], got quality={quality!r}')
+    return quality
+
+
+def jpeg_quant_tables(quality):
+    """(luma, chroma): the two 64-entry quantisation tables (natural order, ints in [1, 255]) a baseline JPEG encoder derives from
+    `quality` in [1, 100]: the Annex K tables times 5000/q % below 50, (200 - 2q) % from 50 on, rounded, clamped."""
+    q = _jpeg_quality(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple([min(255, max(1, (b * scale + 50) // 100)) for b in base] for base in (_JPEG_BASE_LUMA, _JPEG_BASE_CHROMA))
+
+
+def jpeg_header_bytes():
+    """Bytes of a Pillow-written baseline JPEG file in front of its entropy-coded data: SOI, APP0 (JFIF), two DQT, SOF0, four DHT (the
+    standard tables: 12 DC symbols, 162 AC symbols), SOS; every segment = marker (2) + length field (2) + payload."""
+    soi, app0, dqt, sof0, sos = 2, 4 + 14, 4 + 1 + 64, 4 + 6 + 3 * 3, 4 + 1 + 3 * 2 + 3
+    dht_dc, dht_ac = 4 + 1 + 16 + 12, 4 + 1 + 16 + 162
+    return soi + app0 + 2 * dqt + sof0 + 2 * dht_dc + 2 * dht_ac + sos
+
+
+def jpeg_size(img_u8, quality=80, return_coefficients=False):
+    """Byte length of the JPEG file `PIL.Image.save(format='JPEG', quality=quality)` writes for each image -- exact, computed on the GPU
+    without writing the file (dts_jpeg_size).  img_u8: uint8 GPU tensor [n, 3, h, w], h and w multiples of 16; anything else raises
+    ValueError (no fallback: score such images with the host codec).  Returns int32 [n] on the images' device; with
+    return_coefficients also the quantised DCT coefficients, int16 [n, h/16 * w/16 * 6, 64]: zigzag order, blocks in scan order (per
+    16x16 MCU: four Y blocks, Cb, Cr)."""
+    q = _jpeg_quality(quality)
+    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8:
+        raise ValueError(f'jpeg_size: expected a uint8 tensor, got {getattr(img_u8, "dtype", type(img_u8))}')
+    if not img_u8.is_cuda:
+        raise ValueError(f'jpeg_size: the image tensor is on {img_u8.device}; the HIP codec takes GPU tensors (no CPU fallback)')
+    if img_u8.dim() != 4 or img_u8.shape[1] != 3:
+        raise ValueError(f'jpeg_size: expected [n, 3, h, w] (3 channels), got shape {tuple(img_u8.shape)}')
+    n, _, h, w = img_u8.shape
+    if n < 1 or h < 16 or w < 16 or h % 16 or w % 16:
+        raise ValueError(f'jpeg_size: shape {tuple(img_u8.shape)}: height and width must be multiples of 16 (whole MCUs) and n >= 1')
+    lib = L.load()
+    need = lib.dts_jpeg_workspace_bytes(n, h, w)
+    if need <= 0:
+        raise ValueError(f'jpeg_size: shape {tuple(img_u8.shape)} is beyond what one call takes')
+    dev = img_u8.device
+    key = (dev.type, dev.index)
+    ws = _JPEG_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _JPEG_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    qtab = _JPEG_QTAB.get(key + (q,))
+    if qtab is None:
+        qtab = _JPEG_QTAB[key + (q,)] = torch.tensor(jpeg_quant_tables(q), dtype=torch.int16).to(dev)     # <= 255: the bits of a uint16 table
+    sizes = torch.empty((n,), dtype=torch.int32, device=dev)
+    coef = torch.empty((n, (h // 16) * (w // 16) * 6, 64), dtype=torch.int16, device=dev) if return_coefficients else None
+    _call('dts_jpeg_size', _ptr(img_u8, 'img', torch.uint8), _ptr(sizes), n, h, w, _ptr(qtab), _ptr(ws), ws.numel(), _ptr(coef))
+    return (sizes, coef) if return_coefficients else sizes
+
+
 def cosine_rows(a, b):
     """a [n,d] f32, b [n,d] or [1,d] f32 -> [n] f32: cosine similarity of the L2-normalised rows (CLIP reward tail)."""
     n, d = a.shape

@@ -4,8 +4,10 @@
   BrightnessScorer     edm/scorers.py:25-54    -> dts_brightness  (HIP, on the images' device)
   ImageNetScorer       edm/scorers.py:56-174   -> classifier.EncoderUNetModel + dts_softmax_gather (HIP).
                        The reference keeps this scorer on the CPU (main.py:69); here it runs beside the denoiser.
-  CompressibilityScorer edm/scorers.py:176-243 -> host PIL JPEG byte length, unchanged: entropy coding is a CPU
-                       codec and an opaque callable to the search loop.
+  CompressibilityScorer edm/scorers.py:176-243 -> codec='pil' (default): host PIL JPEG byte length, unchanged (N serial encodes
+                       of images copied to the host).  codec='hip': the same byte count from dts_jpeg_size (csrc/jpeg.hip: colour,
+                       4:2:0, integer DCT, quantisation, Huffman bit counts and byte stuffing on the GPU, exact to Pillow) -- one
+                       launch sequence per batch and one copy of n int32 back; the reward expression is the same host code.
   CLIPScorer           sd/scorers.py:149-213   -> HF CLIP image/text towers (third-party arithmetic, run as PyTorch-ROCm
                        modules on the GPU) + dts_cosine_rows (HIP) for the normalise-and-dot tail; with vision_tower='hip' the
                        image tower is clip_vision.CLIPVisionTower on the HIP kernels (16-bit; the text tower stays transformers).  The reference fetches
@@ -110,9 +112,37 @@ class ImageNetScorer(Scorer):
 
 
 class CompressibilityScorer(Scorer):
-    def __init__(self, quality=80, min_size=0, max_size=3000, dtype=torch.float32):
+    def __init__(self, quality=80, min_size=0, max_size=3000, dtype=torch.float32, codec='pil'):
+        """codec: 'pil' (default: the reference's path, every image copied to the host and encoded by `PIL.Image.save`) | 'hip' (the
+        same byte count from ops.jpeg_size: uint8 GPU images [n,3,H,W], or the SD loop's list of [1,3,H,W] tensors of one shape, with H
+        and W multiples of 16 and 1 <= quality <= 100 -- every resolution the search loops produce; the rewards are bit-identical to
+        'pil').  Anything else is refused by name, there is no fallback: score other sizes / layouts with codec='pil'.  A 'hip'
+        instance is `batched`: the SD loop makes one call per decoded batch."""
         super().__init__(dtype)
-        self.quality, self.min_size, self.max_size = quality, min_size, max_size
+        if codec not in ('pil', 'hip'):
+            raise ValueError(f"CompressibilityScorer: codec must be 'pil' or 'hip', got {codec!r}")
+        if codec == 'hip':
+            ops.jpeg_quant_tables(quality)                   # refuses a quality outside [1, 100] here, not at the first call
+            self.batched = True
+        self.quality, self.min_size, self.max_size, self.codec = quality, min_size, max_size, codec
+
+    def _reward(self, size):
+        return 1.0 - min(1.0, max(0.0, (size - self.min_size) / (self.max_size - self.min_size)))
+
+    def _score_hip(self, images):
+        if isinstance(images, (list, tuple)):
+            if not images or not all(isinstance(im, torch.Tensor) for im in images):
+                raise ValueError("CompressibilityScorer(codec='hip'): a list must hold uint8 GPU tensors (use codec='pil' for PIL images)")
+            parts = [im if im.dim() == 4 else im.unsqueeze(0) for im in images]
+            if any(p.shape[1:] != parts[0].shape[1:] for p in parts):
+                raise ValueError(f"CompressibilityScorer(codec='hip'): images of different shapes {sorted({tuple(p.shape) for p in parts})}")
+            images = torch.cat(parts, dim=0) if len(parts) > 1 else parts[0]
+        if not isinstance(images, torch.Tensor):
+            raise ValueError(f"CompressibilityScorer(codec='hip'): unsupported image container {type(images)} (use codec='pil')")
+        if images.dim() == 3:
+            images = images.unsqueeze(0)
+        sizes = ops.jpeg_size(images.contiguous() if images.is_cuda else images, self.quality).cpu().tolist()
+        return torch.tensor([self._reward(size) for size in sizes])
 
     def _score(self, image):
         from PIL import Image
@@ -127,11 +157,12 @@ class CompressibilityScorer(Scorer):
             image = (image * 255).astype(np.uint8) if image.max() <= 1.0 else image.astype(np.uint8)
         buf = io.BytesIO()
         Image.fromarray(image).save(buf, format='JPEG', quality=self.quality)
-        size = len(buf.getvalue())
-        return 1.0 - min(1.0, max(0.0, (size - self.min_size) / (self.max_size - self.min_size)))
+        return self._reward(len(buf.getvalue()))
 
     @torch.no_grad()
     def __call__(self, images, prompts, timesteps):
+        if self.codec == 'hip':
+            return self._score_hip(images)
         if isinstance(images, torch.Tensor):
             if images.dim() == 4:
                 return torch.tensor([self._score(im.cpu().numpy()) for im in images])

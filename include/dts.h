@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 114        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 115        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -50,7 +50,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      111: dts_conv_args.skip_* (a block's 1x1 skip convolution folded into its second 3x3), dts_conv_folds_skip;
                                      112: dts_resample_fir, dts_space_to_depth2 (the NCSN++ options of SongUNet);
                                      113: dts_cross_attention, dts_layer_norm, dts_geglu (the SD U-Net's transformer blocks);
-                                     114: dts_patchify, dts_vit_tokens, dts_gelu, dts_vit_head (the CLIP scorer's vision tower)) */
+                                     114: dts_patchify, dts_vit_tokens, dts_gelu, dts_vit_head (the CLIP scorer's vision tower);
+                                     115: dts_jpeg_workspace_bytes, dts_jpeg_size (the compressibility scorer's JPEG byte length)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -276,6 +277,21 @@ int dts_resample_u8(const uint8_t* src, uint8_t* dst, int planes, int h, int w, 
 int dts_lut_u8_f32(const uint8_t* img, const float* lut, float* out, int n, int c, int hw, dts_stream s);
 /* f32 NCHW = u8 / 255.0f (scorers.py:153) */
 int dts_u8_to_unit_f32(const uint8_t* img, float* out, int64_t count, dts_stream s);
+
+/* ---- K22: JPEG byte length, the compressibility reward (edm/scorers.py:176-243: len of PIL's JPEG bytes at quality q) ---- */
+/* sizes[i] = length in bytes of the baseline JPEG file Pillow / libjpeg-turbo write for image i with quality q, 4:2:0 chroma and the standard
+ * (non-optimised) Huffman tables -- computed without writing the file: quantised DCT coefficients, the bits of every 8x8 block, their prefix sum,
+ * the entropy-coded bytes in a scratch bit buffer (for the count of 0xFF bytes, each of which the file follows with a stuffed 0x00), plus the
+ * fixed header and the EOI marker.  Integer arithmetic throughout: the result is exact, not an estimate.
+ * img uint8 NCHW [n][3][h][w] (what dts_quantize_u8 writes); h and w multiples of 16 (whole MCUs; other sizes return DTS_ERR_ARG: a partial MCU
+ * is completed by libjpeg with dummy blocks, a rule this entry does not implement), 1 <= n <= 65535.
+ * qtab: device uint16 [2][64], the luma and chroma quantisation tables for q in natural (row-major) order.
+ * workspace: device scratch of at least dts_jpeg_workspace_bytes(n, h, w) bytes, 16-byte aligned; the query returns 0 for a refused shape.
+ * coef_out (nullable): int16 [n][blocks][64], the quantised coefficients in zigzag order, blocks in scan order (per 16x16 MCU, row-major over
+ * MCUs: Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr; blocks = h/16 * w/16 * 6) -- lets a wrong size be traced to the transform or to the entropy stage. */
+int64_t dts_jpeg_workspace_bytes(int n, int h, int w);
+int dts_jpeg_size(const uint8_t* img, int32_t* sizes, int n, int h, int w, const uint16_t* qtab, void* workspace, int64_t workspace_bytes,
+                  int16_t* coef_out, dts_stream s);
 
 /* ---- K12 tail: attention pool + softmax-gather (unet.py:61-69; scorers.py:162-172) ---------------- */
 /* tokens[n][hw+1][c]: token 0 = mean_hw(x) + pos[:,0]; token 1+p = x[n][p] + pos[:,1+p]; pos f32 [c][hw+1] */

@@ -20,6 +20,8 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   $DTS_SD_UNET_DIR or the cached snapshot's unet/; no fallback).  --vae hip|diffusers likewise (default hip)
     --clip-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel image tower, float32 like the reference) | hip
                   (clip_vision.CLIPVisionTower on this build's kernels, float16 activations: a 16-bit throughput mode of the scorer; no fallback)
+    --jpeg-codec: --scorer compressibility: pil (default: the reference's host encode per image) | hip (the same byte count computed on the
+                  GPU, identical rewards; image sides must be multiples of 16; no fallback)
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`; the N candidates of every
@@ -36,15 +38,15 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='transformers', clip_model=None):
+def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='transformers', clip_model=None, jpeg_codec='pil'):
     """main.py:60-71 of the reference.  compute_dtype: the search's --dtype; the ImageNet classifier runs in the search's own mode for the two parity
     modes (float32, f16x3) and in float16 otherwise (also beside a bfloat16 denoiser: scorers.ImageNetScorer).  clip_tower: --clip-tower;
-    clip_model: a transformers.CLIPModel to score with instead of the cached checkpoint (scorers.CLIPScorer model=)."""
+    clip_model: a transformers.CLIPModel to score with instead of the cached checkpoint (scorers.CLIPScorer model=).  jpeg_codec: --jpeg-codec."""
     from diffusion_tts_amd import scorers as S
     if scorer_name == 'brightness':
         return S.BrightnessScorer(dtype=torch.float32)
     if scorer_name == 'compressibility':                               # sd/scorers.py:79 normalises by 150000 bytes, edm/scorers.py:177 by 3000
-        return S.CompressibilityScorer(dtype=torch.float32, max_size=150000 if backend == 'sd' else 3000)
+        return S.CompressibilityScorer(dtype=torch.float32, max_size=150000 if backend == 'sd' else 3000, codec=jpeg_codec)
     if scorer_name == 'imagenet' and backend == 'edm':
         return S.ImageNetScorer(dtype=torch.float32, device=device, compute_dtype=compute_dtype if compute_dtype in (torch.float32, 'f16x3') else torch.float16)
     if scorer_name == 'clip' and backend == 'sd':
@@ -120,7 +122,8 @@ def main_sd(args):
     tok = CLIPTokenizer.from_pretrained(model_id, subfolder='tokenizer', local_files_only=True)
     te = CLIPTextModel.from_pretrained(model_id, subfolder='text_encoder', torch_dtype=torch.float16, local_files_only=True).to(dev)
 
-    scorer = get_scorer('sd', args.scorer, dev, clip_tower=getattr(args, 'clip_tower', 'transformers'))
+    scorer = get_scorer('sd', args.scorer, dev, clip_tower=getattr(args, 'clip_tower', 'transformers'),
+                        jpeg_codec=getattr(args, 'jpeg_codec', 'pil'))
     pipe = SDSearchPipeline(unet, vae, device=dev, text_encoder=te, tokenizer=tok)     # encodes the prompt itself (pipeline...:976-992)
     params = {'N': args.N, 'lambda': args.lambda_, 'eps': args.eps, 'K': args.K, 'B': args.B, 'S': args.S}
     torch.manual_seed(args.seed)                                                       # same host RNG stream on every rank
@@ -168,6 +171,9 @@ def build_parser():
     parser.add_argument('--clip-tower', dest='clip_tower', type=str, default='transformers', choices=['transformers', 'hip'],
                         help="SD backend, --scorer clip: 'hip' = the CLIP image tower on this build's kernels in float16 (a 16-bit throughput mode: the "
                              "reference scores in float32; an error if the kernels do not take the model's shape), 'transformers' = the stock module")
+    parser.add_argument('--jpeg-codec', dest='jpeg_codec', type=str, default='pil', choices=['pil', 'hip'],
+                        help="--scorer compressibility: 'hip' = the JPEG byte length computed on the GPU (identical rewards; image sides must be "
+                             "multiples of 16, an error otherwise), 'pil' = the reference's host encode of every image")
     parser.add_argument('--seeds', type=str, default=None, help='bulk mode: seeds, e.g. 0-63 or 1,2,5-10 (one image per seed)')
     parser.add_argument('--outdir', type=str, default='out', help='bulk mode: output directory')
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')
@@ -201,7 +207,7 @@ def main(argv=None):
     from diffusion_tts_amd.sampler import SamplingMethod, generate_image_grid, load_network
     from diffusion_tts_amd.ops import F16X3
     dtype = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32, 'f16x3': F16X3}[args.dtype]
-    scorer = get_scorer('edm', args.scorer, device, compute_dtype=dtype)
+    scorer = get_scorer('edm', args.scorer, device, compute_dtype=dtype, jpeg_codec=getattr(args, 'jpeg_codec', 'pil'))
     net = load_network(args.network, device=device, dtype=dtype)
     if args.seeds is not None:                                                        # bulk mode: seeds sharded over the ranks
         from diffusion_tts_amd.bulk import generate_seeds
