@@ -131,8 +131,8 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
       qf[qt][s] = make_uint4(0, 0, 0, 0);
       if (qrow < p.t) qf[qt][s] = *reinterpret_cast<const uint4*>(base + (size_t)qrow * rowstride + (lg + 4 * s) * 16);
     }
-  // softmax(q.k*scale) == softmax2((q*scale*log2e).k): one multiply per S element saved in the tile loop.  For exact
-  // powers of two (d = 64, 256: scale = 1/8, 1/16) the product q*scale is exact in bf16/f16; log2e is applied in f32 below.
+  // softmax(q.k*scale) == softmax2(q.k * scale*log2e): q stays as stored, S = q.k accumulates un-scaled in f32, and sc2 = scale*log2e
+  // is applied in f32 inside the exponent's fused multiply-add, exp2(fma(s, sc2, -m*sc2)) (see the online softmax below).
   const float sc2 = p.scale_log2e;
   f32x4_t o[QT][DT];
   // The softmax denominator comes off the matrix core too: an all-ones A operand against P^T gives, in every row of a 16x16 tile,

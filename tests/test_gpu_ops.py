@@ -641,7 +641,7 @@ def test_attention(ops, dtype, shape):
 
 
 @pytest.mark.parametrize('shape,spread', [(sh, sp) for sp in (1.0, 4.0, 0.01) for sh in [(2, 64, 2), (1, 256, 3), (2, 65, 2), (3, 1, 1), (1, 1024, 2), (2, 130, 12)]] +
-                         [((16, 1024, 4), 1.0), ((32, 300, 6), 1.0)])      # the last two: grids large enough for two query tiles per wave (full and ragged)
+                         [((16, 1024, 4), 1.0), ((32, 300, 6), 1.0)])      # (16, 1024, 4): t >= 512 and 512 blocks -- the launcher takes two query tiles per wave; (32, 300, 6): ragged, one tile by the launcher's rule (t < 512), two when forced below
 def test_attention_split_precision(ops, shape, spread):
     """ops.attention(..., x3=True) (dts_split2_f16 + dts_attention_x3, head dim 64): Q.K^T and P.V on the 16-bit matrix cores with hi/lo
     operand pairs.  Against an f64 reference it must be as close as the f32 kernel (not f16's 2^-11): full, ragged and one-token
@@ -670,6 +670,15 @@ def test_attention_split_precision(ops, shape, spread):
     e3, e32 = float((got3 - ref).abs().max()) / scale, float((got32 - ref).abs().max()) / scale
     print(f'split-precision attention n={n} t={t} heads={heads} spread={spread}: rel err {e3:.2e} (f32 kernel {e32:.2e})')
     assert e3 < max(1e-6, 1.25 * e32), (e3, e32)      # (measured: 0.4x ... 0.7x the f32 kernel's error everywhere; sharp softmaxes amplify both)
+    if shape == (32, 300, 6):       # the ragged sequence on attention_x3_kernel<2> (every form and ragged length: tests/test_gpu_attention.py)
+        from diffusion_tts_amd import _lib
+        try:
+            _lib.set_tuning('att_qt', 2)
+            e3 = float((ops.attention(x, heads, 1.0 / math.sqrt(d), x3=True).double().cpu() - ref).abs().max()) / scale
+        finally:
+            _lib.set_tuning('att_qt', -1)
+        print(f'  two query tiles per wave forced: rel err {e3:.2e}')
+        assert e3 < max(1e-6, 1.25 * e32), (e3, e32)
 
 
 def test_split_precision_attention_block_without_f32_tensors(ops):
