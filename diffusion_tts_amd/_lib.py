@@ -47,6 +47,7 @@ SIGNATURES = {
     'dts_cross_attention': [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p],
     'dts_layer_norm': [_p, _p, _i, _i64, _i, _f, _p, _p, _p],
     'dts_geglu': [_p, _p, _i, _i64, _i, _p],
+    'dts_group_rows': [_p, _i, _i64, _p, _p, _p, _p, _p],
     'dts_patchify': [_p, _p, _i, _i, _i, _i, _i, _p],
     'dts_vit_tokens': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     'dts_gelu': [_p, _p, _i, _i64, _i, _p],
@@ -82,7 +83,7 @@ OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 115              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 116              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

@@ -533,6 +533,28 @@ def cross_attention(q, kv, heads, scale, kv_rows=None):
     return out
 
 
+GROUP_ROWS_MAX = 1024
+
+
+def group_rows(x):
+    """Groups of bitwise-identical rows of a contiguous device tensor [n, ...], numbered in order of first occurrence (dts_group_rows):
+    (slot int32 [n]: the group of row i; reps int32 [n]: the first row of group g for g < count, -1 beyond; count int32 [1]), all on the
+    device -- nothing is read back here.  1 <= n <= 1024, bytes per row a multiple of 16."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ValueError('group_rows: a GPU tensor (the HIP path has no CPU fallback)')
+    if x.dim() < 1 or not x.is_contiguous():
+        raise ValueError('group_rows: a contiguous tensor [n, ...]')
+    n = x.shape[0]
+    row_bytes = (x.numel() // n) * x.element_size() if n else 0
+    if not 1 <= n <= GROUP_ROWS_MAX or row_bytes == 0 or row_bytes % 16:
+        raise ValueError(f'group_rows: {n} rows of {row_bytes} bytes (1 .. {GROUP_ROWS_MAX} rows, a multiple of 16 bytes each)')
+    ws = torch.empty((n, 4), dtype=torch.int32, device=x.device)
+    out = torch.empty((2 * n + 1,), dtype=torch.int32, device=x.device)
+    slot, reps, count = out[:n], out[n:2 * n], out[2 * n:]
+    _call('dts_group_rows', x.data_ptr(), n, row_bytes, ws.data_ptr(), slot.data_ptr(), reps.data_ptr(), count.data_ptr())
+    return slot, reps, count
+
+
 def layer_norm(x, gamma, beta, eps=1e-5):
     """LayerNorm over the last dimension of a contiguous float16 / bfloat16 tensor; gamma, beta float32 [c] (dts_layer_norm)."""
     c = x.shape[-1]

@@ -120,6 +120,7 @@ class SDSearchPipeline:
         self.mcts_dead_compute = mcts_dead_compute
         self.mcts_backprop = mcts_backprop
         self.text_encoder, self.tokenizer = text_encoder, tokenizer
+        self._context_rows = {}                       # n -> int32 device map [0]*n + [1]*n (U-Nets with takes_context_rows)
         self.unet_rows = 0
         self.decoded = 0                              # images through the VAE decoder on THIS rank
         self.scorer_calls = 0
@@ -151,8 +152,17 @@ class SDSearchPipeline:
     def _eps(self, x, t, embeds_u, embeds_c, guidance):
         """CFG noise prediction for a batch of latents: one 2n-row U-Net call (reference: n calls of 2 rows)."""
         n = x.shape[0]
-        ehs = torch.cat([embeds_u.expand(n, -1, -1), embeds_c.expand(n, -1, -1)])
-        out = self.unet(torch.cat([x, x]), t, encoder_hidden_states=ehs, return_dict=False)[0].contiguous()
+        if getattr(self.unet, 'takes_context_rows', False) and embeds_u.shape[0] == 1 and embeds_c.shape[0] == 1:
+            # sd_unet.SDUNet: the two distinct contexts and the row map of the 2n rows (built once per n) instead of 2n expanded contexts --
+            # nothing for the U-Net to group and no host synchronisation in the call
+            rows = self._context_rows.get(n)
+            if rows is None:
+                rows = self._context_rows[n] = torch.tensor([0] * n + [1] * n, dtype=torch.int32).to(self.device)
+            out = self.unet(torch.cat([x, x]), t, encoder_hidden_states=torch.cat([embeds_u, embeds_c]), context_rows=rows,
+                            return_dict=False)[0].contiguous()
+        else:
+            ehs = torch.cat([embeds_u.expand(n, -1, -1), embeds_c.expand(n, -1, -1)])
+            out = self.unet(torch.cat([x, x]), t, encoder_hidden_states=ehs, return_dict=False)[0].contiguous()
         self.unet_rows += 2 * n
         return ops.cfg_combine(out[:n].contiguous(), out[n:].contiguous(), guidance)
 

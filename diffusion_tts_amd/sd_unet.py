@@ -13,6 +13,9 @@ and the VAE decoder, plus the three the transformer blocks need:
   LayerNorm, GEGLU                   -> dts_layer_norm, dts_geglu
   time embedding                     -> dts_pos_embedding, dts_linear (f32)
   Downsample2D (3x3, stride 2)       -> dts_space_to_depth2 + a 3x3 stride-1 conv over 4C channels (ops.stride2_conv_weight)
+  torch.unique(dim=0) over the contexts -> dts_group_rows (which rows carry the same text context, in order of first occurrence, no sort)
+The forward is a host part (argument checks, the timestep, grouping) and a fixed-shape device part (_device_forward: the distinct contexts and
+a row map in, no host read) that graphs.GraphCache captures once per shape and replays, like the EDM denoisers' forwards.
 Activations are NHWC in `dtype` (float16 like the reference pipeline, or bfloat16).  The 4 latent channels are zero-padded to 64 for the
 MFMA conv (cin % 64 == 0) and conv_out's 4 output channels likewise (cout % 64 == 0).  SD-1.5's head dims 40 / 80 / 160 are zero-padded to
 64 / 128 / 256 at load time (rows of to_q / to_k / to_v, columns of to_out.0; scale = 1/sqrt(true dim)): exact, see pad_head_rows.
@@ -26,6 +29,7 @@ import types
 import torch
 
 from . import ops
+from .graphs import GraphCache
 
 STOCK = {
     '_class_name': 'UNet2DConditionModel',
@@ -92,6 +96,8 @@ def pad_head_cols(w, heads, dpad):
 
 
 class SDUNet:
+    takes_context_rows = True       # __call__(..., context_rows=): the distinct contexts and a row map instead of one context per row
+
     def __init__(self, state_dict, block_out_channels=(320, 640, 1280, 1280), attention_head_dim=8, cross_attention_dim=768,
                  layers_per_block=2, sample_size=64, device='cuda', dtype=torch.float16):
         """attention_head_dim: the NUMBER of heads of every transformer block (diffusers' historical name for it, unet_2d_condition.py:
@@ -108,6 +114,7 @@ class SDUNet:
                                             attention_head_dim=self.heads, cross_attention_dim=self.ctx_dim, layers_per_block=self.lpb)
         self.rows = 0
         self._load(state_dict)
+        self._graphs = GraphCache(self._device_forward)      # one capture per (rows, latent size, number of distinct contexts)
 
     @classmethod
     def from_pretrained(cls, path, device='cuda', dtype=torch.float16):
@@ -277,18 +284,6 @@ class SDUNet:
             raise ValueError('SDUNet: a resnet over concatenated inputs needs its conv_shortcut')
         return ops.conv2d(h, P.w2, P.c2, residual=sk, gn_stats=True)
 
-    def _context_kv(self, ehs):
-        """The k | v projections of the text tokens for every transformer block: they do not depend on the latents, and the 2N rows of a
-        search step hold two distinct contexts -- projected once per DISTINCT row; dts_cross_attention reads them through the row map."""
-        n, L, cd = ehs.shape
-        if cd != self.ctx_dim:
-            raise ValueError(f'SDUNet: encoder_hidden_states has width {cd}, the model {self.ctx_dim}')
-        bits = ehs.reshape(n, L * cd).view(torch.int16)
-        uniq, inverse = torch.unique(bits, dim=0, return_inverse=True)
-        ctx = uniq.view(self.dtype).view(uniq.shape[0], L, 1, cd).contiguous()
-        kv = [ops.conv2d(ctx, A.w_kv2).view(ctx.shape[0], L, 2 * A.hp) for A in self._tfm]
-        return kv, inverse.to(torch.int32).contiguous()
-
     def _transformer(self, x, A, kv, kv_rows):
         """Transformer2DModel.forward with one BasicTransformerBlock (transformer_2d.py, attention.py): tokens stay in NHWC, every
         Linear is a 1x1 convolution with the residual add in its epilogue."""
@@ -309,31 +304,19 @@ class SDUNet:
         h = ops.conv2d(f, A.w_ff2, A.b_ff2, residual=h)
         return ops.conv2d(h, A.w_out, A.b_out, residual=x, gn_stats=True)
 
-    @torch.no_grad()
-    def __call__(self, sample, timestep, encoder_hidden_states=None, return_dict=False, **unused):
-        """sample [n, 4, h, w], timestep a number / 0-d tensor / [n] tensor, encoder_hidden_states [n, L <= 128, cross_attention_dim]
-        -> ([n, 4, h, w] in `dtype`,)."""
-        for k, v in unused.items():
-            if v is not None:
-                raise ValueError(f'SDUNet: argument {k} is not supported (stock SD-1.x call surface only)')
-        if encoder_hidden_states is None:
-            raise ValueError('SDUNet: encoder_hidden_states is required')
-        sample = sample.to(self.device)
-        n, cin, hh, ww = sample.shape
-        if cin != 4 or hh % 8 or ww % 8:
-            raise ValueError(f'SDUNet: sample {tuple(sample.shape)}: 4 channels and a height / width divisible by 8 (three 2x levels)')
-        ehs = encoder_hidden_states.to(self.device, self.dtype)
-        if ehs.shape[0] != n:
-            raise ValueError(f'SDUNet: {ehs.shape[0]} encoder_hidden_states rows for {n} samples')
-        tt = torch.as_tensor(timestep, dtype=torch.float32, device=self.device).reshape(-1)
-        if tt.numel() not in (1, n):
-            raise ValueError(f'SDUNet: {tt.numel()} timesteps for {n} samples')
-        tt = tt.expand(n).contiguous()
+    def _device_forward(self, sample, tt, ctx, kv_rows):
+        """The fixed-shape device part of the forward, what self._graphs captures and replays: sample [n, 4, h, w] (float32 or `dtype`),
+        tt float32 [n], ctx [G, L, cross_attention_dim] in `dtype` (the DISTINCT contexts), kv_rows int32 [n] with entries in [0, G)
+        -> [n, 4, h, w] in `dtype`.  No host read, no shape that depends on data, no copy from host memory."""
         emb = ops.pos_embedding(tt, self.freqs)                                        # cos | sin (flip_sin_to_cos)
         emb = ops.linear(emb, *self.t1, act_out=True)
         emb = ops.linear(emb, *self.t2)
         temb = ops.cast_from_f32(ops.linear(emb, *self.tproj, act_in=True), self.dtype)      # every block's time_emb_proj(silu(emb))
-        kv, kv_rows = self._context_kv(ehs.contiguous())
+        # The k | v projections of the text tokens for every transformer block: they do not depend on the latents, and the 2N rows of a
+        # search step hold two distinct contexts -- projected once per DISTINCT row; dts_cross_attention reads them through the row map.
+        G, L, cd = ctx.shape
+        ctx = ctx.view(G, L, 1, cd)
+        kv = [ops.conv2d(ctx, A.w_kv2).view(G, L, 2 * A.hp) for A in self._tfm]
 
         x = ops.nchw_to_nhwc_pad(sample.float().contiguous(), self.dtype, 64)
         x = ops.conv2d(x, *self.conv_in, gn_stats=True)
@@ -359,7 +342,63 @@ class SDUNet:
                 x = ops.conv2d(x, *us, up=True, gn_stats=True)                         # Upsample2D: nearest-2x fused into the conv's gather
         h = ops.group_norm(x, self.groups, self.eps, self.out_g, self.out_b, silu=True)
         y = ops.conv2d(h, *self.conv_out)                                              # 4 live output channels of 64
-        out = y[..., :4].permute(0, 3, 1, 2).contiguous()
+        return y[..., :4].permute(0, 3, 1, 2).contiguous()
+
+    def _timesteps(self, timestep, n):
+        """float32 [n] on the device.  A number, a 0-d or a one-element host tensor becomes a fill kernel (no copy from pageable memory); a
+        device tensor is converted and broadcast on the device."""
+        if torch.is_tensor(timestep) and timestep.is_cuda:
+            tt = timestep.to(self.device, torch.float32).reshape(-1)
+        elif (timestep.numel() == 1) if torch.is_tensor(timestep) else not hasattr(timestep, '__len__'):
+            return torch.full((n,), float(timestep), dtype=torch.float32, device=self.device)
+        else:                                                                          # a host tensor / sequence of n values: one upload
+            tt = torch.as_tensor(timestep, dtype=torch.float32, device=self.device).reshape(-1)
+        if tt.numel() not in (1, n):
+            raise ValueError(f'SDUNet: {tt.numel()} timesteps for {n} samples')
+        return tt.expand(n).contiguous()
+
+    @torch.no_grad()
+    def __call__(self, sample, timestep, encoder_hidden_states=None, return_dict=False, context_rows=None, **unused):
+        """sample [n, 4, h, w], timestep a number / 0-d tensor / [n] tensor, encoder_hidden_states [n, L <= 128, cross_attention_dim]
+        -> ([n, 4, h, w] in `dtype`,).
+
+        The stock call surface groups identical encoder_hidden_states rows on the device (ops.group_rows) and reads back their number, 4
+        bytes: the one host synchronisation of a call.  context_rows (this build's keyword; `takes_context_rows` announces it) removes it:
+        encoder_hidden_states then holds the G <= n DISTINCT contexts [G, L, cross_attention_dim] and context_rows -- an int32 [n] device
+        tensor, or a sequence of n integers that is uploaded here -- names the context of every sample.  Its VALUES are never read back:
+        the caller vouches that they lie in [0, G) (the attention kernel clamps them for memory safety only)."""
+        for k, v in unused.items():
+            if v is not None:
+                raise ValueError(f'SDUNet: argument {k} is not supported (stock SD-1.x call surface only)')
+        if encoder_hidden_states is None:
+            raise ValueError('SDUNet: encoder_hidden_states is required')
+        sample = sample.to(self.device)
+        n, cin, hh, ww = sample.shape
+        if cin != 4 or hh % 8 or ww % 8:
+            raise ValueError(f'SDUNet: sample {tuple(sample.shape)}: 4 channels and a height / width divisible by 8 (three 2x levels)')
+        ehs = encoder_hidden_states.to(self.device, self.dtype).contiguous()
+        if ehs.dim() != 3 or ehs.shape[2] != self.ctx_dim:
+            raise ValueError(f'SDUNet: encoder_hidden_states {tuple(ehs.shape)}: [rows, tokens, {self.ctx_dim}]')
+        if context_rows is None:
+            if ehs.shape[0] != n:
+                raise ValueError(f'SDUNet: {ehs.shape[0]} encoder_hidden_states rows for {n} samples')
+            tt = self._timesteps(timestep, n)
+            kv_rows, reps, count = ops.group_rows(ehs)
+            ctx = ehs.index_select(0, reps[:int(count)])                               # the call's one host synchronisation: 4 bytes
+        else:
+            if not 1 <= ehs.shape[0] <= n:
+                raise ValueError(f'SDUNet: {ehs.shape[0]} distinct contexts for {n} samples (context_rows: 1 .. n of them)')
+            if torch.is_tensor(context_rows):
+                if context_rows.dtype != torch.int32 or not context_rows.is_cuda:
+                    raise ValueError(f'SDUNet: context_rows is an int32 device tensor (or a sequence of integers), got {context_rows.dtype} on {context_rows.device}')
+                kv_rows = context_rows.to(self.device).contiguous()
+            else:
+                kv_rows = torch.tensor([int(r) for r in context_rows], dtype=torch.int32).to(self.device)
+            if tuple(kv_rows.shape) != (n,):
+                raise ValueError(f'SDUNet: context_rows has shape {tuple(kv_rows.shape)}, expected ({n},)')
+            tt = self._timesteps(timestep, n)
+            ctx = ehs
+        out = self._graphs(sample if sample.dtype == self.dtype else sample.float(), tt, ctx, kv_rows)
         self.rows += n
         if return_dict:
             return types.SimpleNamespace(sample=out)

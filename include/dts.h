@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 115        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 116        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -51,7 +51,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      112: dts_resample_fir, dts_space_to_depth2 (the NCSN++ options of SongUNet);
                                      113: dts_cross_attention, dts_layer_norm, dts_geglu (the SD U-Net's transformer blocks);
                                      114: dts_patchify, dts_vit_tokens, dts_gelu, dts_vit_head (the CLIP scorer's vision tower);
-                                     115: dts_jpeg_workspace_bytes, dts_jpeg_size (the compressibility scorer's JPEG byte length)) */
+                                     115: dts_jpeg_workspace_bytes, dts_jpeg_size (the compressibility scorer's JPEG byte length);
+                                     116: dts_group_rows (the SD U-Net's distinct text contexts, grouped on the device)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -203,6 +204,15 @@ int dts_layer_norm(const void* x, void* out, int dtype, int64_t rows, int c, flo
 /* GEGLU (diffusers activations.py GEGLU): x [rows][2*inner] -> out[r][j] = x[r][j] * gelu(x[r][inner + j]), the exact (erf) GELU;
  * DTS_BF16 / DTS_F16 storage, f32 arithmetic; inner % 8 == 0. */
 int dts_geglu(const void* x, void* out, int dtype, int64_t rows, int inner, dts_stream s);
+/* Groups of bitwise-identical rows, numbered in order of first occurrence: what torch.unique(rows, dim=0, return_inverse=True) over the int16
+ * view of encoder_hidden_states gave SDUNet._context_kv (sd_unet.py), without its row sort and without a host synchronisation of its own.
+ * rows: n contiguous rows of row_bytes bytes; 1 <= n <= 1024, row_bytes % 16 == 0 (anything else returns DTS_ERR_UNSUPPORTED); 16-byte aligned.
+ * slot int32 [n]: the group of row i (slot[0] == 0); reps int32 [n]: reps[g] = the first row of group g for g < count, -1 from count on;
+ * count int32 [1]: the number of distinct rows.  workspace: 16 * n bytes, 16-byte aligned (one 128-bit fingerprint per row).
+ * Equality is equality of the bytes (+0.0 and -0.0 differ, equal NaN payloads are equal).  Two launches: a fingerprint per row, then one block
+ * that compares every row with the earlier rows of the same fingerprint, byte for byte, until one matches -- a fingerprint match is never
+ * taken as equality, so the result is exact for any input.  Integer arithmetic only: two runs give the same bits. */
+int dts_group_rows(const void* rows, int n, int64_t row_bytes, void* workspace, int32_t* slot, int32_t* reps, int32_t* count, dts_stream s);
 
 /* ---- K18-K21: the CLIP scorer's vision tower (transformers models/clip/modeling_clip.py: CLIPVisionEmbeddings, CLIPMLP, the pooled head) ---- */
 /* Patch rows for the patch embedding Conv2d(3, hidden, patch, stride = patch, bias = False): x f32 NCHW [n][3][size][size] (pixel_values) ->

@@ -139,6 +139,8 @@ def main_sd(args):
     if int(os.environ.get('RANK', '0')) == 0:
         best.images[0].save(outname)
         print(f'\n[SD] Saved: {outname}\nBest score: {best_score}  (U-Net: {type(unet).__name__}, VAE: {type(vae).__name__}, reward collectives: {best.collectives})\n')
+        if unet_kind == 'hip':
+            print(f'[SD] U-Net forwards: {unet._graphs.path_report()}\n')
     if world > 1:
         dist.destroy_process_group()
     return best

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""First measurement of the SD-1.5 U-Net on the HIP kernels (diffusion_tts_amd/sd_unet.py): one forward over the 2N = 32 rows of BASELINE
+"""Measurement of the SD-1.5 U-Net on the HIP kernels (diffusion_tts_amd/sd_unet.py): one forward over the 2N = 32 rows of BASELINE
 config 4 ([32,4,64,64] latents, two distinct [77,768] contexts), random-init weights of SD-1.5's shape, float16 and bfloat16.  GPU only.
 
 Prints ONE JSON line: per dtype ms per forward (median of the timed forwards, device events around each forward, after warm-up), rows/s,
@@ -9,14 +9,25 @@ the dense 16-bit matrix peak (an END-TO-END figure, not any kernel's share of pe
 family from one extra, instrumented forward: a device-event pair is recorded around every ops.* call of the module, nothing synchronises
 until the end, so each span is the stream time between the two records (the op's kernels plus whatever gap precedes the closing record) and
 "other" is the forward's total minus the summed spans, i.e. stream time outside any ops.* call (torch glue kernels such as unique / slicing,
-and host launch gaps when the stream runs dry).  No pass/fail threshold."""
+and host launch gaps when the stream runs dry; taken with graph replay off, a replayed forward makes no ops.* call).
+
+The forward is captured once per shape and replayed (SDUNet._graphs), so each dtype is timed four ways in ONE process on the same inputs,
+alternating forward by forward: eager launches (`_graphs.enabled = False`) and graph replay, each through the stock call surface (32
+encoder_hidden_states rows, grouped on the device, one 4-byte readback) and through `context_rows=` (the two distinct contexts and a row
+map, no host synchronisation).  `ms_per_forward` stays what it was before replay existed -- eager launches, stock surface -- so records
+of different commits compare.  `grouping` times ops.group_rows plus the readback of its count against torch.unique(dim=0,
+return_inverse=True), which waits for the size of its own result, on the same [32, 59136] 16-bit rows (host clock around work that ends in a
+synchronise).
+--replay-only N: nothing but N replayed context_rows forwards after the warm-up, for a kernel trace of its own.  No pass/fail threshold."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ.setdefault('DTS_GRAPHS_STRICT', '1')      # a refused capture is an error here: eager figures must not appear under the replay name
 import torch
 from diffusion_tts_amd import init as dinit
 from diffusion_tts_amd import ops
@@ -107,12 +118,41 @@ def op_shares(unet, x, t, ehs):
     return {k: round(v / total, 4) for k, v in sorted(fam_ms.items(), key=lambda kv: -kv[1])}, len(spans)
 
 
+def grouping(ehs, reps=20):
+    """us per call, host clock, each ending in the readback the U-Net's host part waits for: ops.group_rows + its count, against
+    torch.unique over the int16 view (what SDUNet ran before), which waits for the size of its own result"""
+    n = ehs.shape[0]
+    bits = ehs.reshape(n, -1).view(torch.int16)
+
+    def ours():
+        slot, reps_, count = ops.group_rows(ehs)
+        return int(count)
+
+    def unique():
+        uniq, inverse = torch.unique(bits, dim=0, return_inverse=True)      # synchronises by itself: the size of its result is data
+        return uniq.shape[0]
+    out = {'rows': n, 'row_bytes': bits.shape[1] * 2}
+    for name, f in (('group_rows_plus_readback_us', ours), ('torch_unique_plus_readback_us', unique)):
+        for _ in range(3):
+            f()
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            ts.append((time.perf_counter() - t0) * 1e6)
+        out[name] = {'median': round(statistics.median(ts), 1), 'min': round(min(ts), 1), 'max': round(max(ts), 1)}
+    out['groups'] = ours()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=32)
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtypes', default='f16,bf16')
+    ap.add_argument('--replay-only', type=int, default=0, help='only this many replayed context_rows forwards after the warm-up (for a kernel trace)')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('sd_unet_bench: needs a GPU (no CPU fallback, nothing is measured without one)')
@@ -131,22 +171,49 @@ def main():
         x = x32.to('cuda', dt)
         ehs = torch.cat([c2[:1].expand(a.rows // 2, -1, -1), c2[1:].expand(a.rows - a.rows // 2, -1, -1)]).to('cuda', dt).contiguous()
         t = torch.tensor(501, device='cuda')
-        for _ in range(a.warmup):
-            out = unet(x, t, encoder_hidden_states=ehs)[0]
+        ctx = c2.to('cuda', dt).contiguous()
+        rmap = torch.tensor([0] * (a.rows // 2) + [1] * (a.rows - a.rows // 2), dtype=torch.int32).to('cuda')
+        forms = {'stock': lambda: unet(x, t, encoder_hidden_states=ehs)[0],
+                 'context_rows': lambda: unet(x, t, encoder_hidden_states=ctx, context_rows=rmap)[0]}
+        for _ in range(max(a.warmup, 3)):                  # both forms have the same shapes, hence one graph: captured on the third call
+            for f in forms.values():
+                out = f()
         torch.cuda.synchronize()
-        times = []
-        for _ in range(a.iters):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = unet(x, t, encoder_hidden_states=ehs)[0]
-            e1.record()
+        assert unet._graphs.captures == 1 and unet._graphs.replays > 0, unet._graphs.path_report()
+        if a.replay_only:
+            for _ in range(a.replay_only):
+                out = forms['context_rows']()
             torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1))
-        ms = statistics.median(times)
+            res['dtypes'][name] = {'replay_only_forwards': a.replay_only, 'path': unet._graphs.path_report()}
+            del unet
+            torch.cuda.empty_cache()
+            continue
+        times = {(mode, form): [] for mode in ('eager', 'replay') for form in forms}
+        outs = {}
+        for _ in range(a.iters):
+            for mode in ('eager', 'replay'):
+                unet._graphs.enabled = mode == 'replay'
+                for form, f in forms.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    out = f()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times[mode, form].append(e0.elapsed_time(e1))
+                    outs[mode, form] = out
+        same = all(torch.equal(o, outs['eager', 'stock']) for o in outs.values())
+        unet._graphs.enabled = False                       # the per-op spans need the ops.* calls of an eager forward
         shares, launches = op_shares(unet, x, t, ehs)
-        res['dtypes'][name] = {'ms_per_forward': round(ms, 3), 'ms_min': round(min(times), 3), 'ms_max': round(max(times), 3),
+        unet._graphs.enabled = True
+        ms = statistics.median(times['eager', 'stock'])
+        stat = lambda v: {'ms_median': round(statistics.median(v), 3), 'ms_min': round(min(v), 3), 'ms_max': round(max(v), 3)}
+        res['dtypes'][name] = {'ms_per_forward': round(ms, 3), 'ms_min': round(min(times['eager', 'stock']), 3), 'ms_max': round(max(times['eager', 'stock']), 3),
                                'rows_per_s': round(a.rows / ms * 1e3, 1), 'tflops_algorithmic': round(flops / ms / 1e9, 1),
                                'fraction_of_dense_16bit_peak_end_to_end': round(flops / (ms * 1e-3) / PEAK_16BIT_DENSE, 4),
+                               'eager': {form: stat(times['eager', form]) for form in forms},
+                               'replay': {form: stat(times['replay', form]) for form in forms},
+                               'replay_rows_per_s_context_rows': round(a.rows / statistics.median(times['replay', 'context_rows']) * 1e3, 1),
+                               'all_four_outputs_bit_identical': bool(same), 'path': unet._graphs.path_report(), 'grouping': grouping(ehs),
                                'time_share_by_op_family': shares, 'op_calls_per_forward': launches, 'output_finite': bool(torch.isfinite(out).all())}
         del unet
         torch.cuda.empty_cache()
