@@ -44,12 +44,14 @@ SIGNATURES = {
     'dts_resample_fir': [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     'dts_space_to_depth2': [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     'dts_attention': [_p, _p, _i, _i, _i, _i, _i, _f, _p],
+    'dts_attention_masked': [_p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p],
     'dts_cross_attention': [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p],
     'dts_layer_norm': [_p, _p, _i, _i64, _i, _f, _p, _p, _p],
     'dts_geglu': [_p, _p, _i, _i64, _i, _p],
     'dts_group_rows': [_p, _i, _i64, _p, _p, _p, _p, _p],
     'dts_patchify': [_p, _p, _i, _i, _i, _i, _i, _p],
     'dts_vit_tokens': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'dts_text_tokens': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'dts_gelu': [_p, _p, _i, _i64, _i, _p],
     'dts_vit_head': [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p],
     'dts_linear': [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
@@ -83,7 +85,7 @@ OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 116              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 117              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

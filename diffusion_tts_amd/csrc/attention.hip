@@ -794,6 +794,184 @@ __global__ __launch_bounds__(256) void attention32_kernel(const AttP p) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Masked self-attention (dts_attention_masked; head dim 64, 16-bit types): CLIP's text transformer (transformers modeling_clip.py,
+// CLIPTextTransformer: a causal mask, plus the tokenizer's attention_mask for the text encoders that use it).  Query i of sample b sees key
+// j iff (!causal || j <= i) && j < kend, kend = min(t, key_len[b]).  A kernel of its own beside attention16_kernel<T, 64, 1> -- one block
+// = 4 waves = 64 queries, key tiles of 64 through the register prefetch, the same fragments, LDS rows and arithmetic (f32 scores, exp2
+// with the scale in the fused multiply-add, P rounded to T, the denominator from the rounded P on the matrix core, one final rounding) --
+// so that the unmasked instantiations stay what they are.  What differs:
+//   * a block walks only the key tiles that hold a key some query of it may see: tiles below min(kend, end of the query block).  A tile
+//     wholly above the diagonal or wholly past kend is never staged -- with every score -inf and the running maximum still -inf the
+//     exponent would be -inf - (-inf) = NaN.  Every tile that IS walked starts at a key key0 <= the block's first query and key0 < kend,
+//     so every query has a finite score in every tile it meets and the running maximum is finite from tile 0 on.
+//   * the mask is a select to -inf on the f32 scores (where attention16_kernel masks the tail past t): exp2(-inf) = 0 exactly, so a
+//     disallowed key adds 0 * v to the numerator and 0 to the denominator -- nothing of it reaches the output as long as v is finite.
+//     Only the diagonal tile (causal) and the tile that holds kend pay for it.
+//   * key rows from kend on are staged as zeros, not read.
+struct AttMaskP {
+  const char* qkv; char* out;
+  const int32_t* key_len;        // [n] on the device, or null
+  int n, t, heads;
+  float scale_log2e;
+  int qblocks, xcd_remap, causal;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void attention_masked_kernel(const AttMaskP p) {
+  constexpr int D = 64, ES = 2, ROWB = D * ES + 32, CH = D / 8, KSTEPS = D / 32, DT = D / 16, NCH = (64 * CH) / 256;
+  __shared__ __attribute__((aligned(16))) char smem[2 * 64 * ROWB];
+  char* sK = smem;
+  char* sV = smem + 64 * ROWB;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int lq = lane & 15, lg = lane >> 4;
+  int bid = blockIdx.x;                              // att_block()'s order: the query blocks of a (sample, head) share an XCD
+  if (p.xcd_remap) {
+    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, j = bid >> 3;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+  }
+  const int nh = bid / p.qblocks, qblk = bid - nh * p.qblocks;
+  const int n = nh / p.heads, head = nh - n * p.heads;
+  const int C = p.heads * D;
+  const size_t rowstride = (size_t)3 * C * ES;
+  const char* base = p.qkv + (size_t)n * p.t * rowstride + (size_t)head * D * ES;
+  const char* const vbase = base + (size_t)2 * C * ES;
+  const int q0 = qblk * 64 + wid * 16;
+  const int qrow = q0 + lq;
+  int kend = p.t;                                    // keys of this sample: the caller vouches for 1 <= key_len <= t, clamped for memory safety only
+  if (p.key_len) kend = min(p.t, max(1, p.key_len[n]));
+  const int kblk = p.causal ? min(kend, qblk * 64 + 64) : kend;       // keys some query of this block may see
+  const int ntiles = (kblk + 63) / 64;
+  const int lim = p.causal ? min(kend, qrow + 1) : kend;              // this lane's query sees keys < lim (>= 1)
+
+  uint4 qf[KSTEPS];
+#pragma unroll
+  for (int s = 0; s < KSTEPS; ++s) {
+    qf[s] = make_uint4(0, 0, 0, 0);
+    if (qrow < p.t) qf[s] = *reinterpret_cast<const uint4*>(base + (size_t)qrow * rowstride + (lg + 4 * s) * 16);
+  }
+  const float sc2 = p.scale_log2e;
+  f32x4_t o[DT], ol = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const uint4 ones = make_uint4(AttMma<T>::ONES2, AttMma<T>::ONES2, AttMma<T>::ONES2, AttMma<T>::ONES2);
+  float m_run = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < DT; ++i) o[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  uint4 pk[NCH], pv[NCH];
+#define ATTM_LOAD_TILE(key0_)                                                                     \
+  _Pragma("unroll") for (int u = 0; u < NCH; ++u) {                                               \
+    const int idx = tid + 256 * u, r = idx / CH, c = idx - r * CH;                                \
+    pk[u] = pv[u] = make_uint4(0, 0, 0, 0);                                                       \
+    if ((key0_) + r < kend) {                                                                     \
+      pk[u] = *reinterpret_cast<const uint4*>(base + (size_t)((key0_) + r) * rowstride + c * 16 + (size_t)C * ES); \
+      pv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)((key0_) + r) * rowstride + c * 16); \
+    }                                                                                             \
+  }
+  ATTM_LOAD_TILE(0);
+  for (int kt = 0; kt < ntiles; ++kt) {              // ntiles is the same for the four waves: the barriers are block-uniform
+    const int key0 = kt * 64;
+    __syncthreads();                                 // the previous tile is consumed
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) {
+      const int idx = tid + 256 * u, r = idx / CH, c = idx - r * CH;
+      *reinterpret_cast<uint4*>(sK + r * ROWB + c * 16) = pk[u];
+      *reinterpret_cast<uint4*>(sV + r * ROWB + c * 16) = pv[u];
+    }
+    __syncthreads();
+    if (kt + 1 < ntiles) { ATTM_LOAD_TILE(key0 + 64); }
+
+    // ---- S^T tiles: 4 x (16 keys x 16 queries)
+    f32x4_t sacc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      sacc[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < KSTEPS; ++s) {
+        const uint4 ka = *reinterpret_cast<const uint4*>(sK + (j * 16 + lq) * ROWB + (lg + 4 * s) * 16);
+        sacc[j] = AttMma<T>::run(ka, qf[s], sacc[j]);
+      }
+    }
+    // ---- the mask: lane holds keys key0 + j*16 + lg*4 + r of query lq.  Wave-uniform test: the tile reaches past kend, or (causal) past
+    // the wave's first query -- the diagonal tile, the last one this block walks
+    if (key0 + 64 > kend || (p.causal && key0 + 63 > q0)) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (key0 + j * 16 + lg * 4 + r >= lim) sacc[j][r] = -INFINITY;
+    }
+    // ---- online softmax (attention16_kernel's)
+    float tmax = vmax3(sacc[0][0], sacc[0][1], sacc[0][2]);
+    tmax = vmax3(tmax, sacc[0][3], sacc[1][0]);
+    tmax = vmax3(tmax, sacc[1][1], sacc[1][2]);
+    tmax = vmax3(tmax, sacc[1][3], sacc[2][0]);
+    tmax = vmax3(tmax, sacc[2][1], sacc[2][2]);
+    tmax = vmax3(tmax, sacc[2][3], sacc[3][0]);
+    tmax = vmax3(tmax, sacc[3][1], sacc[3][2]);
+    tmax = vmax2(tmax, sacc[3][3]);
+    {
+      const float t16 = __shfl_xor(tmax, 16, 64), t32 = __shfl_xor(tmax, 32, 64), t48 = __shfl_xor(tmax, 48, 64);
+      tmax = vmax2(vmax3(tmax, t16, t32), t48);
+    }
+    const float m_new = vmax2(m_run, tmax);          // finite: key key0 of every walked tile is visible to every query of the block
+    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sc2);
+    const float mb = m_new * sc2;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sacc[j][r] = __builtin_amdgcn_exp2f(fmaf(sacc[j][r], sc2, -mb));       // masked: exp2(-inf) = 0
+    m_run = m_new;
+    if (!__all(alpha == 1.0f)) {
+#pragma unroll
+      for (int i = 0; i < DT; ++i) o[i] *= alpha;
+      ol[0] *= alpha;
+    }
+    uint4 pb[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      pb[kk].x = AttMma<T>::pack2(sacc[2 * kk][0], sacc[2 * kk][1]);
+      pb[kk].y = AttMma<T>::pack2(sacc[2 * kk][2], sacc[2 * kk][3]);
+      pb[kk].z = AttMma<T>::pack2(sacc[2 * kk + 1][0], sacc[2 * kk + 1][1]);
+      pb[kk].w = AttMma<T>::pack2(sacc[2 * kk + 1][2], sacc[2 * kk + 1][3]);
+    }
+    // ---- O^T += V^T . P^T, l += ones . P^T
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int rq = (lane & 15) >> 2, rp = lane & 3;
+      const char* va = sV + (32 * kk + 4 * lg + rq) * ROWB + rp * 8;
+      const char* vb = va + 16 * ROWB;
+      ol = AttMma<T>::run(ones, pb[kk], ol);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(va + dt * 32));
+        const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vb + dt * 32));
+        const uint2 lo2 = __builtin_bit_cast(uint2, lo), hi2 = __builtin_bit_cast(uint2, hi);
+        o[dt] = AttMma<T>::run(make_uint4(lo2.x, lo2.y, hi2.x, hi2.y), pb[kk], o[dt]);
+      }
+    }
+  }
+#undef ATTM_LOAD_TILE
+  if (qrow < p.t) {
+    const float inv = 1.f / ol[0];
+    T* orow = reinterpret_cast<T*>(p.out) + ((size_t)n * p.t + qrow) * C + head * D;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) st1<T>(orow + dt * 16 + lg * 4 + r, o[dt][r] * inv);
+  }
+}
+
+template <typename T>
+int att_masked(AttMaskP p, hipStream_t st) {
+  p.qblocks = (p.t + 63) / 64;
+  p.xcd_remap = dts_knob_get(DTS_KNOB_ATT_XCD) != 0;
+  const long long nblk = (long long)p.qblocks * p.n * p.heads;
+  DTS_CHECK_ARG(nblk < (1ll << 31), "dts_attention_masked: grid too large");
+  hipLaunchKernelGGL(attention_masked_kernel<T>, dim3((unsigned)nblk), dim3(256), 0, st, p);
+  DTS_CHECK_LAUNCH("dts_attention_masked");
+  return DTS_OK;
+}
+
 template <typename K>
 int launch_att(K kernel, const AttP& p0, size_t lds, hipStream_t st, int qblock = 64, int slices = 1) {
   {   // hipFuncSetAttribute once per (device, kernel): the attribute is per device, and every instantiation has the same pointer
@@ -873,6 +1051,25 @@ extern "C" int dts_attention_x3(const void* qkv_split, void* out, int out_split3
   if (var == 0) return X3_LAUNCH(0);      // DTS_ATT_DB=16: without the three latency changes of round 6 (A/B aid, tools/att_bench.py --x3-kernel --variants 0)
   return X3_LAUNCH(7);
 #undef X3_LAUNCH
+}
+
+extern "C" int dts_attention_masked(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, int causal,
+                                    const int32_t* key_len, dts_stream s) {
+  DTS_CHECK_ARG(qkv && out, "dts_attention_masked: null pointer");
+  DTS_CHECK_ARG(n > 0 && t > 0 && heads > 0, "dts_attention_masked: bad shape");
+  DTS_CHECK_ARG(dtype == DTS_F32 || dtype == DTS_BF16 || dtype == DTS_F16, "dts_attention_masked: bad dtype %d", dtype);
+  DTS_CHECK_ARG(scale > 0.f && scale <= 3.402823466e38f, "dts_attention_masked: scale must be positive and finite");
+  DTS_CHECK_ARG(((uintptr_t)qkv | (uintptr_t)out) % 16 == 0 && (uintptr_t)key_len % 4 == 0, "dts_attention_masked: pointers must be 16-byte aligned");
+  if (dtype == DTS_F32) {
+    dts_set_error("dts_attention_masked: dtype %d (DTS_F32) unsupported (DTS_BF16 / DTS_F16 only)", dtype);
+    return DTS_ERR_UNSUPPORTED;
+  }
+  if (d != 64) {
+    dts_set_error("dts_attention_masked: head dim %d unsupported (64, the head dim of every CLIP text width)", d);
+    return DTS_ERR_UNSUPPORTED;
+  }
+  AttMaskP p{(const char*)qkv, (char*)out, key_len, n, t, heads, scale * 1.4426950408889634f, 0, 1, causal ? 1 : 0};
+  return dtype == DTS_BF16 ? att_masked<bf16_t>(p, to_stream(s)) : att_masked<f16_t>(p, to_stream(s));
 }
 
 extern "C" int dts_attention(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, dts_stream s) {

@@ -1,7 +1,8 @@
 // The pieces of a CLIP vision tower (transformers models/clip/modeling_clip.py: CLIPVisionEmbeddings, CLIPMLP's activation, the pooled
 // head of CLIPVisionTransformer + CLIPModel.visual_projection) that the U-Nets never needed: non-overlapping patch rows for the patch
 // embedding, class token + position table, GELU as an op of its own, LayerNorm of the class token alone.  Everything else of the tower is
-// dts_layer_norm, dts_conv2d (1x1), dts_attention and dts_linear.  16-bit storage (bf16 / f16), f32 arithmetic, gfx950 only.
+// dts_layer_norm, dts_conv2d (1x1), dts_attention and dts_linear.  Also the one piece CLIP's TEXT tower adds (CLIPTextEmbeddings): token
+// embedding + position table.  16-bit storage (bf16 / f16), f32 arithmetic, gfx950 only.
 #include "dts_common.h"
 #include <math.h>
 
@@ -73,6 +74,28 @@ __global__ __launch_bounds__(256) void vit_tokens_kernel(const T* __restrict__ p
 #pragma unroll
   for (int e = 0; e < 8; ++e) y[e] = a[e] + b[e];
   reinterpret_cast<uint4*>(tokens)[idx] = pack16<T>(y);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Text token assembly (CLIPTextEmbeddings.forward: token_embedding(input_ids) + position_embedding): out [n][t][c] = tok[ids[n][t]] + pos[t],
+// both tables f32, the sum formed in f32 and rounded once -- the text counterpart of vit_tokens_kernel.  One thread = one 16-byte vector;
+// c % 8 == 0.  An id outside [0, vocab) cannot be reported from here: it is clamped, for memory safety only (the caller checks the ids on
+// the host, ops.text_tokens).
+template <typename T>
+__global__ __launch_bounds__(256) void text_tokens_kernel(const int32_t* __restrict__ ids, const float* __restrict__ tok,
+                                                           const float* __restrict__ pos, T* __restrict__ out, long long nvec, int t, int c, int vocab) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= nvec) return;
+  const int vpr = c >> 3;
+  const long long row = idx / vpr;                 // (sample, token)
+  const int v = (int)(idx - row * vpr);
+  const int pt = (int)(row % t);
+  const int id = min(max(ids[row], 0), vocab - 1);
+  const float4* tr = reinterpret_cast<const float4*>(tok + (long long)id * c);
+  const float4* pr = reinterpret_cast<const float4*>(pos + (long long)pt * c);
+  const float4 a0 = tr[2 * v], a1 = tr[2 * v + 1], p0 = pr[2 * v], p1 = pr[2 * v + 1];
+  const float y[8] = {a0.x + p0.x, a0.y + p0.y, a0.z + p0.z, a0.w + p0.w, a1.x + p1.x, a1.y + p1.y, a1.z + p1.z, a1.w + p1.w};
+  reinterpret_cast<uint4*>(out)[idx] = pack16<T>(y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -183,6 +206,23 @@ extern "C" int dts_vit_tokens(const void* patches, const float* cls, const float
   else
     hipLaunchKernelGGL(vit_tokens_kernel<f16_t>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), (const f16_t*)patches, cls, pos, (f16_t*)tokens, nvec, t, c);
   DTS_CHECK_LAUNCH("dts_vit_tokens");
+  return DTS_OK;
+}
+
+extern "C" int dts_text_tokens(const int32_t* ids, const float* tok, const float* pos, void* out, int dtype, int n, int t, int c, int vocab,
+                               dts_stream s) {
+  DTS_CHECK_ARG(ids && tok && pos && out, "dts_text_tokens: null pointer");
+  DTS_VIT_16BIT("dts_text_tokens", dtype);
+  DTS_CHECK_ARG(n > 0 && t > 0 && vocab > 0 && c > 0 && c % 8 == 0, "dts_text_tokens: %d x %d tokens x %d channels (a multiple of 8), vocabulary %d",
+                n, t, c, vocab);
+  DTS_CHECK_ARG(((uintptr_t)tok | (uintptr_t)pos | (uintptr_t)out) % 16 == 0 && (uintptr_t)ids % 4 == 0, "dts_text_tokens: pointers must be 16-byte aligned");
+  const long long nvec = (long long)n * t * (c / 8), grid = (nvec + 255) / 256;
+  DTS_CHECK_ARG(grid < (1ll << 31), "dts_text_tokens: grid too large");
+  if (dtype == DTS_BF16)
+    hipLaunchKernelGGL(text_tokens_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), ids, tok, pos, (bf16_t*)out, nvec, t, c, vocab);
+  else
+    hipLaunchKernelGGL(text_tokens_kernel<f16_t>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), ids, tok, pos, (f16_t*)out, nvec, t, c, vocab);
+  DTS_CHECK_LAUNCH("dts_text_tokens");
   return DTS_OK;
 }
 

@@ -514,6 +514,22 @@ def attention(qkv, heads, scale, x3=False, split_out=False):
     return out
 
 
+def attention_masked(qkv, heads, scale, causal=True, key_len=None):
+    """qkv [n, t, 3*heads*64] (q|k|v blocks; float16 / bfloat16) -> [n, t, heads*64] (dts_attention_masked): query i of sample b attends
+    key j iff (not causal or j <= i) and (key_len is None or j < key_len[b]).  key_len: int32 [n] on the device with 1 <= key_len[b] <= t --
+    the caller vouches for the range, it is not read back here.  causal=False with key_len=None is plain attention."""
+    if qkv.dim() != 3 or heads <= 0 or qkv.shape[-1] % (3 * heads):
+        raise ValueError(f'attention_masked: qkv {tuple(qkv.shape)} is not [n, t, 3 * {heads} heads * d]')
+    n, t, c3 = qkv.shape
+    c = c3 // 3
+    if key_len is not None and (tuple(key_len.shape) != (n,) or key_len.dtype != torch.int32):
+        raise ValueError(f'attention_masked: key_len {tuple(key_len.shape)} {key_len.dtype} is not int32 [{n}]')
+    out = torch.empty((n, t, c), dtype=qkv.dtype, device=qkv.device)
+    _call('dts_attention_masked', _ptr(qkv, 'qkv'), _ptr(out), dt_code(qkv.dtype), n, t, heads, c // heads, float(scale), int(bool(causal)),
+          _ptr(key_len, 'key_len', torch.int32))
+    return out
+
+
 def attention_x3_ok(t, d):
     """whether attention(..., x3=True) takes the split-precision kernel for this sequence length / head dim (so that the qkv projection may
     write its operand image directly and the proj convolution may read one)"""
@@ -610,6 +626,30 @@ def vit_tokens(patches, cls, pos):
     out = torch.empty((n, tp + 1, c), dtype=patches.dtype, device=patches.device)
     _call('dts_vit_tokens', _ptr(patches, 'patches'), _ptr(cls, 'cls', torch.float32), _ptr(pos, 'pos', torch.float32), _ptr(out),
           dt_code(patches.dtype), n, tp + 1, c)
+    return out
+
+
+def text_tokens(ids, tok, pos, dtype):
+    """ids integer [n, t], tok float32 [vocab, c], pos float32 [>= t, c] (both on the device) -> [n, t, c] in float16 / bfloat16:
+    tok[ids] + pos[:t], summed in float32 and rounded once (dts_text_tokens).  The kernel cannot report a bad id, so 0 <= id < vocab is
+    checked HERE, on the host, before the upload: a ValueError names the offending value.  The ids come from the tokenizer as a host
+    tensor; one that is already on the device is copied back for the check -- one synchronisation, acceptable where this runs (once per
+    prompt)."""
+    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.numel() == 0:
+        raise ValueError(f'text_tokens: ids must be an integer tensor [n, t], got {tuple(ids.shape) if torch.is_tensor(ids) else type(ids).__name__}'
+                         + (f' {ids.dtype}' if torch.is_tensor(ids) else ''))
+    n, t = ids.shape
+    if tok.dim() != 2 or pos.dim() != 2 or pos.shape[1] != tok.shape[1] or pos.shape[0] < t:
+        raise ValueError(f'text_tokens: tok {tuple(tok.shape)} / pos {tuple(pos.shape)} for ids {tuple(ids.shape)}')
+    vocab, c = tok.shape
+    host = ids.detach().cpu()
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 0 or hi >= vocab:
+        raise ValueError(f'text_tokens: token id {lo if lo < 0 else hi} is outside [0, {vocab}) (the rows of the token table)')
+    dev_ids = host.to(torch.int32).to(tok.device).contiguous()
+    out = torch.empty((n, t, c), dtype=dtype, device=tok.device)
+    _call('dts_text_tokens', _ptr(dev_ids, 'ids', torch.int32), _ptr(tok, 'tok', torch.float32), _ptr(pos, 'pos', torch.float32), _ptr(out),
+          dt_code(dtype), n, t, c, vocab)
     return out
 
 

@@ -218,11 +218,14 @@ class CLIPScorer(Scorer):
 
     def __init__(self, model_id='openai/clip-vit-large-patch14', dtype=torch.float32, model=None, image_processor=None,
                  tokenizer=None, processor=None, device='cuda', device_preprocess=True, vision_tower='transformers',
-                 tower_dtype=torch.float16):
+                 tower_dtype=torch.float16, text_tower='transformers'):
         """vision_tower: 'transformers' (default: `model.get_image_features`, the reference's arithmetic in the model's own precision) |
         'hip' (clip_vision.CLIPVisionTower built from `model`: the image tower on this build's kernels with `tower_dtype` = float16 /
         bfloat16 activations -- a 16-bit THROUGHPUT mode of the scorer, where the reference scores in float32; a configuration the kernels
         do not take is refused by name, there is no fallback).  The text branch, its cache and the pre-processing are the same either way.
+        text_tower: 'transformers' (default: `model.get_text_features`) | 'hip' (clip_text.CLIPTextTower built from `model`, `tower_dtype`
+        activations: the prompt's embedding from this build's kernels -- an opt-in 16-bit mode like vision_tower='hip'; the reference embeds
+        the text in float32).  The text-embedding cache and the cosine tail are unchanged.
         device_preprocess: run the image processor's resize / rescale / normalise on the GPU (clip_preprocess.DevicePreprocessor:
         Pillow's integer bicubic + the processor's own value table, identical pixel_values) whenever the images are square uint8 GPU
         tensors and the processor has the stock configuration; False keeps the reference's host path (images.cpu() + PIL) always."""
@@ -258,6 +261,12 @@ class CLIPScorer(Scorer):
         if vision_tower == 'hip':
             from .clip_vision import CLIPVisionTower
             self._tower = CLIPVisionTower.from_clip_model(self.clip, dtype=tower_dtype, device=self.device)
+        if text_tower not in ('transformers', 'hip'):
+            raise ValueError(f"CLIPScorer: text_tower must be 'transformers' or 'hip', got {text_tower!r}")
+        self.text_tower, self._text_tower = text_tower, None
+        if text_tower == 'hip':
+            from .clip_text import CLIPTextTower
+            self._text_tower = CLIPTextTower.from_text_model(self.clip, dtype=tower_dtype, device=self.device)
         self.image_processor, self.tokenizer = image_processor, tokenizer
         self._text_cache = {}
         self.device_preprocessed = 0                                   # images whose pixel_values were built on the GPU
@@ -296,7 +305,10 @@ class CLIPScorer(Scorer):
         txt_emb = self._text_cache.get(key)                            # the prompt is fixed over a search: encode it once
         if txt_emb is None:
             enc = self.tokenizer(prompts, padding=True, truncation=True, max_length=77, return_tensors='pt').to(dev)
-            txt_emb = _features(self.clip.get_text_features(**enc)).float().contiguous()
+            if self._text_tower is not None:
+                txt_emb = self._text_tower.get_text_features(**enc).contiguous()     # f32 [n, projection_dim] from 16-bit activations
+            else:
+                txt_emb = _features(self.clip.get_text_features(**enc)).float().contiguous()
             if len(self._text_cache) < 64:
                 self._text_cache[key] = txt_emb
         return ops.cosine_rows(img_emb, txt_emb).to(self.dtype)        # :182-183,205-211 (normalise both, row-wise dot)

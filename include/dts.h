@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 116        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 117        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -52,7 +52,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      113: dts_cross_attention, dts_layer_norm, dts_geglu (the SD U-Net's transformer blocks);
                                      114: dts_patchify, dts_vit_tokens, dts_gelu, dts_vit_head (the CLIP scorer's vision tower);
                                      115: dts_jpeg_workspace_bytes, dts_jpeg_size (the compressibility scorer's JPEG byte length);
-                                     116: dts_group_rows (the SD U-Net's distinct text contexts, grouped on the device)) */
+                                     116: dts_group_rows (the SD U-Net's distinct text contexts, grouped on the device);
+                                     117: dts_attention_masked, dts_text_tokens (the CLIP text tower: SD's text encoder and the CLIP scorer's text side)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -187,6 +188,16 @@ int dts_attention(const void* qkv, void* out, int dtype, int n, int t, int heads
  * image [n][t][2*heads*d] (per 32 channels hi | lo * 2^11: dts_split3_f16's arithmetic and layout) the proj convolution reads.  Q.K^T and P.V on the 16-bit matrix cores with hi/lo operand pairs (the lo*lo term,
  * 2^-22, dropped), softmax in f32: the f32 kernel's accuracy without the f32 matrix instruction's 1/16 rate. */
 int dts_attention_x3(const void* qkv_split, void* out, int out_split3, int n, int t, int heads, int d, float scale, dts_stream s);
+/* Masked self-attention (CLIP's text transformer); layout as dts_attention.  Query i of sample b attends key j iff
+ * (!causal || j <= i) && (key_len == NULL || j < key_len[b]).  key_len: device int32 [n], nullable; the caller vouches for
+ * 1 <= key_len[b] <= t (the kernel clamps it for memory safety only), so every query has key 0 and no row is empty.  causal = 0 with
+ * key_len = NULL is plain attention.  DTS_BF16 / DTS_F16 with d = 64 (every CLIP text width: 512/8, 768/12, 1024/16, 1280/20); DTS_F32 and
+ * other head dims return DTS_ERR_UNSUPPORTED; any t >= 1; scale > 0.  The arithmetic is dts_attention's in the 16-bit types (f32 scores, f32
+ * softmax with exp2, P rounded to the storage type, the denominator summed from the rounded P, one final rounding).  The mask is a select to
+ * -inf on the scores, not an additive bias: a disallowed key has weight exactly 0, and finite k / v values there cannot change a bit of
+ * the output.  Key tiles wholly above a query block's diagonal or wholly past key_len are skipped, not computed and masked. */
+int dts_attention_masked(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, int causal,
+                         const int32_t* key_len, dts_stream s);
 
 /* ---- K15-K17: the SD U-Net's transformer blocks (diffusers BasicTransformerBlock: attention.py, attention_processor.py) ---- */
 /* Attention of tq queries over a SHORT foreign sequence (the text tokens): q [n][tq][heads*d], kv [kv_n][tk][2*heads*d] laid out
@@ -230,6 +241,11 @@ int dts_vit_tokens(const void* patches, const float* cls, const float* pos, void
  * CLIP checkpoints), kind 1 = the exact (erf) GELU x * erfc(-x / sqrt 2) / 2 (the LAION towers).  f32 arithmetic; finite over the whole storage
  * range (the most negative finite input gives -0, not inf * 0). */
 int dts_gelu(const void* x, void* out, int dtype, int64_t count, int kind, dts_stream s);
+/* The text counterpart of dts_vit_tokens (CLIPTextEmbeddings): out [n][t][c] in DTS_BF16 / DTS_F16 = tok[ids[n][t]][:] + pos[t][:], tok f32
+ * [vocab][c] (token_embedding.weight), pos f32 [>= t][c] (position_embedding.weight), ids device int32 [n][t]; the sum is formed in f32 and
+ * rounded once.  c % 8 == 0.  Ids must lie in [0, vocab): the kernel cannot report a bad one and clamps it for memory safety only -- check
+ * them on the host before the upload. */
+int dts_text_tokens(const int32_t* ids, const float* tok, const float* pos, void* out, int dtype, int n, int t, int c, int vocab, dts_stream s);
 /* Pooled head, first half: out f32 [n][c] = LayerNorm(tokens[n][0][:]) * gamma + beta (CLIPVisionTransformer post_layernorm of the class token;
  * biased variance, statistics in f32 as dts_layer_norm) -- token 0 only, the other t - 1 tokens are never read.  tokens [n][t][c] DTS_BF16 /
  * DTS_F16; c % 8 == 0, c <= 2048.  visual_projection follows as dts_linear on the f32 rows. */

@@ -18,6 +18,8 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   (throughput modes: ~2.8x faster again, but a near-tied pick differs after ~10 decisions and the result is another sample)
     --unet      : SD backend: diffusers (default: the stock UNet2DConditionModel) | hip (sd_unet.SDUNet on this build's kernels, read from
                   $DTS_SD_UNET_DIR or the cached snapshot's unet/; no fallback).  --vae hip|diffusers likewise (default hip)
+    --text-encoder: SD backend: transformers (default: the stock CLIPTextModel) | hip (clip_text.CLIPTextTower on this build's kernels, read
+                  from $DTS_SD_TEXT_ENCODER_DIR or the cached snapshot's text_encoder/; no fallback)
     --clip-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel image tower, float32 like the reference) | hip
                   (clip_vision.CLIPVisionTower on this build's kernels, float16 activations: a 16-bit throughput mode of the scorer; no fallback)
     --jpeg-codec: --scorer compressibility: pil (default: the reference's host encode per image) | hip (the same byte count computed on the
@@ -93,19 +95,44 @@ def load_sd_unet(model_id, dev, kind='diffusers'):
     return SDUNet.from_pretrained(path, device=dev, dtype=torch.float16)
 
 
+def load_sd_text_encoder(model_id, dev, kind='transformers'):
+    """The SD text encoder, the twin of load_sd_unet.  kind='hip' (`--text-encoder hip`): this build's HIP text tower
+    (clip_text.CLIPTextTower, drop-in for `text_encoder(input_ids, attention_mask=...)[0]`) read from the safetensors `text_encoder/`
+    directory of the locally cached SD-1.5 snapshot (or $DTS_SD_TEXT_ENCODER_DIR) -- and an error when that directory cannot be found or
+    read: there is no silent fallback.  kind='transformers' (the default): the stock CLIPTextModel module."""
+    if kind == 'transformers':
+        from transformers import CLIPTextModel
+        return CLIPTextModel.from_pretrained(model_id, subfolder='text_encoder', torch_dtype=torch.float16, local_files_only=True).to(dev)
+    if kind != 'hip':
+        raise ValueError(f"--text-encoder must be 'hip' or 'transformers', got {kind!r}")
+    from diffusion_tts_amd.clip_text import CLIPTextTower
+    path = os.environ.get('DTS_SD_TEXT_ENCODER_DIR')
+    if path is None:
+        from huggingface_hub import snapshot_download
+        path = os.path.join(snapshot_download(model_id, local_files_only=True, allow_patterns=['text_encoder/*']), 'text_encoder')
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f'SD text encoder directory {path!r} not found (set DTS_SD_TEXT_ENCODER_DIR, or pass --text-encoder '
+                                f'transformers for the stock module)')
+    return CLIPTextTower.from_pretrained(path, device=dev, dtype=torch.float16)
+
+
 def main_sd(args):
     """SD backend (reference main.py:111-147).  The search loop, the fused DDIM candidate step and candidate batching are
     this build's (diffusion_tts_amd/sd_pipeline.py), and so are the VAE decoder (`--vae hip`, the default) and, with `--unet hip`, the
-    U-Net (diffusion_tts_amd/sd_unet.py): `--unet hip --vae hip` needs transformers (text encoder, tokenizer) and SD-1.5 weights in the
-    local HF cache only.  `--unet diffusers` (the default) / `--vae diffusers` take the stock diffusers modules on PyTorch-ROCm."""
+    U-Net (diffusion_tts_amd/sd_unet.py) and, with `--text-encoder hip`, the text encoder (diffusion_tts_amd/clip_text.py):
+    `--unet hip --vae hip --text-encoder hip` needs of transformers the tokenizer only (CLIPTokenizer: host string processing and
+    vocabulary files) and SD-1.5 weights in the local HF cache.  `--unet diffusers` (the default) / `--vae diffusers` take the stock
+    diffusers modules on PyTorch-ROCm, `--text-encoder transformers` (the default) the stock CLIPTextModel."""
     unet_kind, vae_kind = getattr(args, 'unet', 'diffusers'), getattr(args, 'vae', 'hip')
+    te_kind = getattr(args, 'text_encoder', 'transformers')
     try:
         if 'diffusers' in (unet_kind, vae_kind):                           # only the parts that are asked for need diffusers
             import diffusers                                               # noqa: F401
-        from transformers import CLIPTextModel, CLIPTokenizer
+        from transformers import CLIPTokenizer                             # (--text-encoder hip: nothing else of transformers)
     except Exception as e:      # pragma: no cover
-        raise RuntimeError('--backend sd needs `transformers` (text encoder) and, for --unet diffusers / --vae diffusers, `diffusers`, '
-                           'with SD-1.5 weights in the local cache; that import failed.  `--unet hip --vae hip` runs without diffusers; '
+        raise RuntimeError('--backend sd needs `transformers` (the tokenizer; with --text-encoder transformers also the text encoder) and, '
+                           'for --unet diffusers / --vae diffusers, `diffusers`, with SD-1.5 weights in the local cache; that import '
+                           'failed.  `--unet hip --vae hip --text-encoder hip` runs without diffusers and with the tokenizer alone; '
                            'or drive diffusion_tts_amd.sd_pipeline.SDSearchPipeline(unet, vae) directly (tests/test_gpu_sd_unet.py '
                            'shows the call).') from e
     from diffusion_tts_amd.sd_pipeline import SDSearchPipeline
@@ -120,7 +147,7 @@ def main_sd(args):
     unet = load_sd_unet(model_id, dev, unet_kind)
     vae = load_sd_vae(model_id, dev, vae_kind)
     tok = CLIPTokenizer.from_pretrained(model_id, subfolder='tokenizer', local_files_only=True)
-    te = CLIPTextModel.from_pretrained(model_id, subfolder='text_encoder', torch_dtype=torch.float16, local_files_only=True).to(dev)
+    te = load_sd_text_encoder(model_id, dev, te_kind)
 
     scorer = get_scorer('sd', args.scorer, dev, clip_tower=getattr(args, 'clip_tower', 'transformers'),
                         jpeg_codec=getattr(args, 'jpeg_codec', 'pil'))
@@ -138,7 +165,7 @@ def main_sd(args):
     outname = args.output or f'sd_{args.method}_{args.scorer}.png'
     if int(os.environ.get('RANK', '0')) == 0:
         best.images[0].save(outname)
-        print(f'\n[SD] Saved: {outname}\nBest score: {best_score}  (U-Net: {type(unet).__name__}, VAE: {type(vae).__name__}, reward collectives: {best.collectives})\n')
+        print(f'\n[SD] Saved: {outname}\nBest score: {best_score}  (U-Net: {type(unet).__name__}, VAE: {type(vae).__name__}, text encoder: {type(te).__name__}, reward collectives: {best.collectives})\n')
         if unet_kind == 'hip':
             print(f'[SD] U-Net forwards: {unet._graphs.path_report()}\n')
     if world > 1:
@@ -170,6 +197,9 @@ def build_parser():
                         help="SD backend: 'hip' = this build's VAE decoder (an error if its safetensors cannot be read), 'diffusers' = the stock module")
     parser.add_argument('--unet', type=str, default='diffusers', choices=['hip', 'diffusers'],
                         help="SD backend: 'hip' = this build's U-Net on the HIP kernels (an error if its safetensors cannot be read), 'diffusers' = the stock module")
+    parser.add_argument('--text-encoder', dest='text_encoder', type=str, default='transformers', choices=['transformers', 'hip'],
+                        help="SD backend: 'hip' = this build's CLIP text tower on the HIP kernels in float16 (an error if its safetensors cannot be "
+                             "read), 'transformers' = the stock CLIPTextModel")
     parser.add_argument('--clip-tower', dest='clip_tower', type=str, default='transformers', choices=['transformers', 'hip'],
                         help="SD backend, --scorer clip: 'hip' = the CLIP image tower on this build's kernels in float16 (a 16-bit throughput mode: the "
                              "reference scores in float32; an error if the kernels do not take the model's shape), 'transformers' = the stock module")
