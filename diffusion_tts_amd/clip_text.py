@@ -20,8 +20,7 @@ import types
 
 import torch
 
-from . import ops
-from .clip_vision import stack_qkv
+from . import blocks, ops
 
 PREFIX = 'text_model.'
 PROJECTION = 'text_projection.weight'
@@ -34,24 +33,10 @@ CONFIG_DEFAULTS = {'vocab_size': 49408, 'hidden_size': 512, 'intermediate_size':
 def check_config(hidden_size, num_attention_heads, intermediate_size, hidden_act, dtype, vocab_size=49408, max_position_embeddings=77,
                  projection_dim=None):
     """Raises ValueError naming every setting of a CLIP text configuration that this build's kernels do not take, with its value."""
-    bad = []
-    if dtype not in (torch.float16, torch.bfloat16):
-        bad.append(f'dtype={dtype} (float16 or bfloat16: there is no float32 form of this tower)')
-    if hidden_size <= 0 or hidden_size % 64:
-        bad.append(f'hidden_size={hidden_size} is not a multiple of 64 (the channel granularity of dts_conv2d)')
-    if hidden_size > 2048:
-        bad.append(f'hidden_size={hidden_size} exceeds 2048 (the row dts_layer_norm holds in registers)')
-    if num_attention_heads <= 0 or hidden_size % num_attention_heads or hidden_size // num_attention_heads != 64:
-        hd = hidden_size / num_attention_heads if num_attention_heads > 0 else float('nan')
-        bad.append(f'head dim {hd:g} (hidden_size={hidden_size} / num_attention_heads={num_attention_heads}) is not dts_attention_masked\'s 64')
-    if intermediate_size <= 0 or intermediate_size % 64:
-        bad.append(f'intermediate_size={intermediate_size} is not a multiple of 64')
-    if hidden_act not in ops.GELU_KINDS:
-        bad.append(f'hidden_act={hidden_act!r} (dts_gelu computes {sorted(ops.GELU_KINDS)})')
+    bad = blocks.clip_config_errors(dtype, hidden_size, num_attention_heads, intermediate_size, hidden_act, projection_dim,
+                                    (64,), 'dts_attention_masked\'s 64')
     if vocab_size <= 0 or max_position_embeddings <= 0:
         bad.append(f'vocab_size={vocab_size}, max_position_embeddings={max_position_embeddings}')
-    if projection_dim is not None and projection_dim <= 0:
-        bad.append(f'projection_dim={projection_dim}')
     if bad:
         raise ValueError('CLIPTextTower: ' + '; '.join(bad))
 
@@ -99,11 +84,7 @@ def mask_key_len(attention_mask, n, t):
 def text_config(cfg):
     """the text settings of a config.json dict (a CLIPModel's, with `text_config` nested, or a CLIPTextModel's own), absent keys taking
     transformers' defaults; projection_dim is the top-level one of a CLIPModel (the shape of text_projection)"""
-    tc = cfg.get('text_config') or cfg
-    out = {k: tc.get(k, d) for k, d in CONFIG_DEFAULTS.items()}
-    if 'text_config' in cfg and 'projection_dim' in cfg:
-        out['projection_dim'] = cfg['projection_dim']
-    return out
+    return blocks.clip_section(cfg, 'text_config', CONFIG_DEFAULTS)
 
 
 def text_keys(keys):
@@ -126,23 +107,8 @@ def read_text_tensors(path):
     """(text settings, state dict) of a local directory holding `config.json` + `model.safetensors` (what `save_pretrained` writes: an SD
     checkpoint's text_encoder/ directory, or a CLIP directory): only `text_model.*` and `text_projection.weight` are read -- the vision
     tower never leaves disk.  Host tensors; no GPU needed."""
-    import json
-    import os
-    from safetensors import safe_open
-    cfg_file, st_file = os.path.join(path, 'config.json'), os.path.join(path, 'model.safetensors')
-    if not os.path.exists(cfg_file):
-        raise FileNotFoundError(f'{path}: no config.json')
-    if not os.path.exists(st_file):
-        raise FileNotFoundError(f'{path}: no model.safetensors (a .bin pickle is not read: convert it to safetensors)')
-    with open(cfg_file) as f:
-        cfg = text_config(json.load(f))
-    sd = {}
-    with safe_open(st_file, framework='pt', device='cpu') as f:
-        for k, name in text_keys(f.keys()).items():
-            sd[name] = f.get_tensor(k)
-    if not sd:
-        raise ValueError(f'{st_file}: no {PREFIX}* tensors')
-    return cfg, sd
+    cfg, st_file = blocks.clip_files(path)
+    return text_config(cfg), blocks.read_tensors(st_file, text_keys, PREFIX + '*')
 
 
 class TextOutput:
@@ -163,8 +129,7 @@ class CLIPTextTower:
         """The defaults are those of SD-1.5's text encoder (openai/clip-vit-large-patch14's text side).  projection_dim None: taken from
         text_projection.weight when the state dict has one (a CLIPTextModel has none: no `.text_embeds` then)."""
         check_config(hidden_size, num_attention_heads, intermediate_size, hidden_act, dtype, vocab_size, max_position_embeddings, projection_dim)
-        if not torch.cuda.is_available():
-            raise RuntimeError('CLIPTextTower (HIP) needs a GPU: there is no CPU fallback in this package')
+        blocks.require_gpu('CLIPTextTower')
         self.device, self.dtype = torch.device(device), dtype
         self.vocab, self.hidden, self.heads, self.inter = int(vocab_size), int(hidden_size), int(num_attention_heads), int(intermediate_size)
         self.layers_n, self.max_pos, self.act, self.eps = int(num_hidden_layers), int(max_position_embeddings), hidden_act, float(layer_norm_eps)
@@ -199,13 +164,6 @@ class CLIPTextTower:
         return cls(sd, device=device, dtype=dtype, **cfg)
 
     # ---- parameters ----------------------------------------------------------------------------
-    def _f(self, t):
-        return t.detach().to(self.device, torch.float32).contiguous()
-
-    def _pack(self, w, b):
-        """f32 weight [O, I] + bias on the device -> (packed [O][1][1][I] in the activation dtype, f32 bias)"""
-        return ops.pack_conv_weight(w[:, :, None, None].contiguous(), self.dtype), b.contiguous()
-
     def _check_shapes(self, sd):
         """the parameters must be those of the configuration this object was given: a mismatch is named here, not met as a reshape error"""
         C, I, L, V, P = self.hidden, self.inter, self.layers_n, self.vocab, self.max_pos
@@ -213,12 +171,8 @@ class CLIPTextTower:
         want = {f'{PREFIX}embeddings.token_embedding.weight': (V, C), f'{PREFIX}embeddings.position_embedding.weight': (P, C),
                 f'{PREFIX}final_layer_norm.weight': (C,), f'{last}.self_attn.q_proj.weight': (C, C), f'{last}.mlp.fc1.weight': (I, C),
                 f'{last}.mlp.fc2.weight': (C, I)}
-        for key, shape in want.items():
-            if key not in sd:
-                raise ValueError(f'CLIPTextTower: the state dict has no {key!r} (num_hidden_layers={L})')
-            if tuple(sd[key].shape) != shape:
-                raise ValueError(f'CLIPTextTower: {key} has shape {tuple(sd[key].shape)}, but vocab_size={V}, hidden_size={C}, '
-                                 f'intermediate_size={I}, max_position_embeddings={P} ask for {shape}')
+        blocks.check_shapes('CLIPTextTower', sd, want, f'num_hidden_layers={L}',
+                            f'vocab_size={V}, hidden_size={C}, intermediate_size={I}, max_position_embeddings={P}')
         if f'{PREFIX}encoder.layers.{L}.layer_norm1.weight' in sd:
             raise ValueError(f'CLIPTextTower: the state dict has more than num_hidden_layers={L} layers')
         if PROJECTION in sd:
@@ -230,21 +184,11 @@ class CLIPTextTower:
 
     def _load(self, sd):
         self._check_shapes(sd)
-        e = PREFIX + 'embeddings.'
-        self.tok, self.pos = self._f(sd[e + 'token_embedding.weight']), self._f(sd[e + 'position_embedding.weight'])
-        ln = lambda key: (self._f(sd[key + '.weight']), self._f(sd[key + '.bias']))
-        self.final_ln = ln(PREFIX + 'final_layer_norm')
-        self.layers = []
-        for i in range(self.layers_n):
-            key = f'{PREFIX}encoder.layers.{i}'
-            P = types.SimpleNamespace(ln1=ln(key + '.layer_norm1'), ln2=ln(key + '.layer_norm2'))
-            wq, bq = stack_qkv(sd, key + '.self_attn')
-            P.w_qkv, P.b_qkv = self._pack(self._f(wq), self._f(bq))
-            P.w_o, P.b_o = self._pack(self._f(sd[key + '.self_attn.out_proj.weight']), self._f(sd[key + '.self_attn.out_proj.bias']))
-            P.w_fc1, P.b_fc1 = self._pack(self._f(sd[key + '.mlp.fc1.weight']), self._f(sd[key + '.mlp.fc1.bias']))
-            P.w_fc2, P.b_fc2 = self._pack(self._f(sd[key + '.mlp.fc2.weight']), self._f(sd[key + '.mlp.fc2.bias']))
-            self.layers.append(P)
-        self.w_proj = self._f(sd[PROJECTION]) if PROJECTION in sd else None      # f32 [projection_dim, hidden], no bias
+        p, e = blocks.Params(self.device, self.dtype), PREFIX + 'embeddings.'
+        self.tok, self.pos = p.f32(sd[e + 'token_embedding.weight']), p.f32(sd[e + 'position_embedding.weight'])
+        self.final_ln = p.norm(sd, PREFIX + 'final_layer_norm')
+        self.layers = blocks.clip_layers(p, sd, PREFIX, self.layers_n)
+        self.w_proj = p.f32(sd[PROJECTION]) if PROJECTION in sd else None      # f32 [projection_dim, hidden], no bias
         self.proj_dim = self.config.projection_dim = None if self.w_proj is None else self.w_proj.shape[0]
         torch.cuda.synchronize(self.device)
 
@@ -264,16 +208,8 @@ class CLIPTextTower:
         key_len = None if lens is None else lens.to(self.device)
         pos = pooled_positions(ids, self.eos)
         h = ops.text_tokens(ids, self.tok, self.pos, self.dtype).view(n, t, 1, C)                  # checks 0 <= id < vocab on the host
-        for P in self.layers:
-            # CLIPEncoderLayer.forward: x + out_proj(attention(layer_norm1(x))), then x + fc2(act(fc1(layer_norm2(x))))
-            y = ops.layer_norm(h, *P.ln1, eps=self.eps)
-            qkv = ops.conv2d(y, P.w_qkv, P.b_qkv)
-            a = ops.attention_masked(qkv.view(n, t, 3 * C), self.heads, self.scale, causal=True, key_len=key_len)
-            h = ops.conv2d(a.view(n, t, 1, C), P.w_o, P.b_o, residual=h)
-            y = ops.layer_norm(h, *P.ln2, eps=self.eps)
-            f = ops.conv2d(y, P.w_fc1, P.b_fc1)
-            ops.gelu(f, self.act, out=f)
-            h = ops.conv2d(f, P.w_fc2, P.b_fc2, residual=h)
+        h = blocks.clip_encoder(h, self.layers, self.eps, self.act,
+                                lambda qkv: ops.attention_masked(qkv, self.heads, self.scale, causal=True, key_len=key_len))
         last = ops.layer_norm(h, *self.final_ln, eps=self.eps).view(n, t, C)                       # every token
         pooled = last[torch.arange(n, device=self.device), pos.to(self.device)].contiguous()
         embeds = None if self.w_proj is None else ops.linear(ops.cast_to_f32(pooled), self.w_proj)

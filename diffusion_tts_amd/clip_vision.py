@@ -21,7 +21,8 @@ import types
 
 import torch
 
-from . import ops
+from . import blocks, ops
+from .blocks import stack_qkv       # noqa: F401  (the rule lives in blocks; tests and callers read it here)
 
 PREFIX = 'vision_model.'
 PROJECTION = 'visual_projection.weight'
@@ -32,25 +33,10 @@ CONFIG_DEFAULTS = {'hidden_size': 768, 'intermediate_size': 3072, 'num_hidden_la
 
 def check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim=None):
     """Raises ValueError naming every setting of a CLIP vision configuration that this build's kernels do not take, with its value."""
-    bad = []
-    if dtype not in (torch.float16, torch.bfloat16):
-        bad.append(f'dtype={dtype} (float16 or bfloat16: there is no float32 form of this tower)')
-    if hidden_size <= 0 or hidden_size % 64:
-        bad.append(f'hidden_size={hidden_size} is not a multiple of 64 (the channel granularity of dts_conv2d)')
-    if hidden_size > 2048:
-        bad.append(f'hidden_size={hidden_size} exceeds 2048 (the row dts_layer_norm holds in registers)')
-    if num_attention_heads <= 0 or hidden_size % num_attention_heads or hidden_size // num_attention_heads not in (64, 128, 256):
-        hd = hidden_size / num_attention_heads if num_attention_heads > 0 else float('nan')
-        bad.append(f'head dim {hd:g} (hidden_size={hidden_size} / num_attention_heads={num_attention_heads}) is not one of '
-                   f'dts_attention\'s 64 / 128 / 256')
-    if intermediate_size <= 0 or intermediate_size % 64:
-        bad.append(f'intermediate_size={intermediate_size} is not a multiple of 64')
+    bad = blocks.clip_config_errors(dtype, hidden_size, num_attention_heads, intermediate_size, hidden_act, projection_dim,
+                                    (64, 128, 256), 'one of dts_attention\'s 64 / 128 / 256')
     if patch_size <= 0 or image_size <= 0 or image_size % patch_size:
         bad.append(f'image_size={image_size} is not a multiple of patch_size={patch_size}')
-    if hidden_act not in ops.GELU_KINDS:
-        bad.append(f'hidden_act={hidden_act!r} (dts_gelu computes {sorted(ops.GELU_KINDS)})')
-    if projection_dim is not None and projection_dim <= 0:
-        bad.append(f'projection_dim={projection_dim}')
     if bad:
         raise ValueError('CLIPVisionTower: ' + '; '.join(bad))
 
@@ -67,44 +53,18 @@ def patch_weight_matrix(w, kpad=None):
     return out
 
 
-def stack_qkv(sd, key):
-    """(weight [3C, C], bias [3C]) of one projection whose output is q | k | v blocks, from `key`.{q,k,v}_proj.{weight,bias}"""
-    w = torch.cat([sd[f'{key}.{n}_proj.weight'] for n in 'qkv'], 0)
-    b = torch.cat([sd[f'{key}.{n}_proj.bias'] for n in 'qkv'], 0)
-    return w, b
-
-
 def vision_config(cfg):
     """the vision settings of a config.json dict (a CLIPModel's, with `vision_config` nested, or a CLIPVisionModelWithProjection's own),
     absent keys taking transformers' defaults; projection_dim is the top-level one of a CLIPModel (the shape of visual_projection)"""
-    vc = cfg.get('vision_config') or cfg
-    out = {k: vc.get(k, d) for k, d in CONFIG_DEFAULTS.items()}
-    if 'vision_config' in cfg and 'projection_dim' in cfg:
-        out['projection_dim'] = cfg['projection_dim']
-    return out
+    return blocks.clip_section(cfg, 'vision_config', CONFIG_DEFAULTS)
 
 
 def read_vision_tensors(path):
     """(vision settings, state dict) of a local directory holding `config.json` + `model.safetensors` (what `save_pretrained` writes):
     only `vision_model.*` and `visual_projection.weight` are read -- the text tower never leaves disk.  Host tensors; no GPU needed."""
-    import json
-    import os
-    from safetensors import safe_open
-    cfg_file, st_file = os.path.join(path, 'config.json'), os.path.join(path, 'model.safetensors')
-    if not os.path.exists(cfg_file):
-        raise FileNotFoundError(f'{path}: no config.json')
-    if not os.path.exists(st_file):
-        raise FileNotFoundError(f'{path}: no model.safetensors (a .bin pickle is not read: convert it to safetensors)')
-    with open(cfg_file) as f:
-        cfg = vision_config(json.load(f))
-    sd = {}
-    with safe_open(st_file, framework='pt', device='cpu') as f:
-        for k in f.keys():
-            if k.startswith(PREFIX) or k == PROJECTION:
-                sd[k] = f.get_tensor(k)
-    if not sd:
-        raise ValueError(f'{st_file}: no {PREFIX}* tensors')
-    return cfg, sd
+    cfg, st_file = blocks.clip_files(path)
+    sd = blocks.read_tensors(st_file, lambda keys: {k: k for k in keys if k.startswith(PREFIX) or k == PROJECTION}, PREFIX + '*')
+    return vision_config(cfg), sd
 
 
 class CLIPVisionTower:
@@ -113,8 +73,7 @@ class CLIPVisionTower:
         """The defaults are ViT-L/14's (openai/clip-vit-large-patch14, the reference's scorer).  projection_dim None: taken from
         visual_projection.weight."""
         check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim)
-        if not torch.cuda.is_available():
-            raise RuntimeError('CLIPVisionTower (HIP) needs a GPU: there is no CPU fallback in this package')
+        blocks.require_gpu('CLIPVisionTower')
         self.device, self.dtype = torch.device(device), dtype
         self.hidden, self.heads, self.inter, self.layers_n = int(hidden_size), int(num_attention_heads), int(intermediate_size), int(num_hidden_layers)
         self.image_size, self.patch, self.act, self.eps = int(image_size), int(patch_size), hidden_act, float(layer_norm_eps)
@@ -147,13 +106,6 @@ class CLIPVisionTower:
         return cls(sd, device=device, dtype=dtype, **cfg)
 
     # ---- parameters ----------------------------------------------------------------------------
-    def _f(self, t):
-        return t.detach().to(self.device, torch.float32).contiguous()
-
-    def _pack(self, w, b=None):
-        """f32 weight [O, I] (+ bias) on the device -> (packed [O][1][1][I] in the activation dtype, f32 bias)"""
-        return ops.pack_conv_weight(w[:, :, None, None].contiguous(), self.dtype), (None if b is None else b.contiguous())
-
     def _check_shapes(self, sd):
         """the parameters must be those of the configuration this object was given: a mismatch is named here, not met as a reshape error"""
         C, I, L, p, T = self.hidden, self.inter, self.layers_n, self.patch, self.tokens
@@ -162,12 +114,8 @@ class CLIPVisionTower:
                 f'{PREFIX}embeddings.position_embedding.weight': (T, C), f'{PREFIX}pre_layrnorm.weight': (C,),
                 f'{PREFIX}post_layernorm.weight': (C,), f'{last}.self_attn.q_proj.weight': (C, C), f'{last}.mlp.fc1.weight': (I, C),
                 f'{last}.mlp.fc2.weight': (C, I)}
-        for key, shape in want.items():
-            if key not in sd:
-                raise ValueError(f'CLIPVisionTower: the state dict has no {key!r} (num_hidden_layers={L})')
-            if tuple(sd[key].shape) != shape:
-                raise ValueError(f'CLIPVisionTower: {key} has shape {tuple(sd[key].shape)}, but hidden_size={C}, intermediate_size={I}, '
-                                 f'image_size={self.image_size}, patch_size={p} ask for {shape}')
+        blocks.check_shapes('CLIPVisionTower', sd, want, f'num_hidden_layers={L}',
+                            f'hidden_size={C}, intermediate_size={I}, image_size={self.image_size}, patch_size={p}')
         if f'{PREFIX}encoder.layers.{L}.layer_norm1.weight' in sd:
             raise ValueError(f'CLIPVisionTower: the state dict has more than num_hidden_layers={L} layers')
         if f'{PREFIX}embeddings.patch_embedding.bias' in sd:
@@ -180,22 +128,12 @@ class CLIPVisionTower:
 
     def _load(self, sd):
         self._check_shapes(sd)
-        e = PREFIX + 'embeddings.'
-        self.w_patch, _ = self._pack(patch_weight_matrix(self._f(sd[e + 'patch_embedding.weight']), self.kpad))
-        self.cls, self.pos = self._f(sd[e + 'class_embedding']), self._f(sd[e + 'position_embedding.weight'])
-        ln = lambda key: (self._f(sd[key + '.weight']), self._f(sd[key + '.bias']))
-        self.pre_ln, self.post_ln = ln(PREFIX + 'pre_layrnorm'), ln(PREFIX + 'post_layernorm')
-        self.layers = []
-        for i in range(self.layers_n):
-            key = f'{PREFIX}encoder.layers.{i}'
-            P = types.SimpleNamespace(ln1=ln(key + '.layer_norm1'), ln2=ln(key + '.layer_norm2'))
-            wq, bq = stack_qkv(sd, key + '.self_attn')
-            P.w_qkv, P.b_qkv = self._pack(self._f(wq), self._f(bq))
-            P.w_o, P.b_o = self._pack(self._f(sd[key + '.self_attn.out_proj.weight']), self._f(sd[key + '.self_attn.out_proj.bias']))
-            P.w_fc1, P.b_fc1 = self._pack(self._f(sd[key + '.mlp.fc1.weight']), self._f(sd[key + '.mlp.fc1.bias']))
-            P.w_fc2, P.b_fc2 = self._pack(self._f(sd[key + '.mlp.fc2.weight']), self._f(sd[key + '.mlp.fc2.bias']))
-            self.layers.append(P)
-        self.w_proj = self._f(sd[PROJECTION])                            # f32 [projection_dim, hidden], no bias
+        p, e = blocks.Params(self.device, self.dtype), PREFIX + 'embeddings.'
+        self.w_patch, _ = p.pack(patch_weight_matrix(p.f32(sd[e + 'patch_embedding.weight']), self.kpad))
+        self.cls, self.pos = p.f32(sd[e + 'class_embedding']), p.f32(sd[e + 'position_embedding.weight'])
+        self.pre_ln, self.post_ln = p.norm(sd, PREFIX + 'pre_layrnorm'), p.norm(sd, PREFIX + 'post_layernorm')
+        self.layers = blocks.clip_layers(p, sd, PREFIX, self.layers_n)
+        self.w_proj = p.f32(sd[PROJECTION])                            # f32 [projection_dim, hidden], no bias
         self.proj_dim = self.config.projection_dim = self.w_proj.shape[0]
         torch.cuda.synchronize(self.device)
 
@@ -213,16 +151,7 @@ class CLIPVisionTower:
         emb = ops.conv2d(rows.view(n, g, g, self.kpad), self.w_patch)                              # the patch embedding has no bias
         h = ops.vit_tokens(emb.view(n, g * g, C), self.cls, self.pos)
         h = ops.layer_norm(h, *self.pre_ln, eps=self.eps).view(n, T, 1, C)
-        for P in self.layers:
-            # CLIPEncoderLayer.forward: x + out_proj(attention(layer_norm1(x))), then x + fc2(act(fc1(layer_norm2(x))))
-            y = ops.layer_norm(h, *P.ln1, eps=self.eps)
-            qkv = ops.conv2d(y, P.w_qkv, P.b_qkv)
-            a = ops.attention(qkv.view(n, T, 3 * C), self.heads, self.scale)
-            h = ops.conv2d(a.view(n, T, 1, C), P.w_o, P.b_o, residual=h)
-            y = ops.layer_norm(h, *P.ln2, eps=self.eps)
-            f = ops.conv2d(y, P.w_fc1, P.b_fc1)
-            ops.gelu(f, self.act, out=f)
-            h = ops.conv2d(f, P.w_fc2, P.b_fc2, residual=h)
+        h = blocks.clip_encoder(h, self.layers, self.eps, self.act, lambda qkv: ops.attention(qkv, self.heads, self.scale))
         pooled = ops.vit_head(h.view(n, T, C), *self.post_ln, eps=self.eps)                        # f32 [n, C]: the class token only
         self.rows += n
         return ops.linear(pooled, self.w_proj)

@@ -206,32 +206,44 @@ def checksum(sd):
     return dict(sum=s, abs_sum=a, numel=n)
 
 
+class _DiffusersBuilder:
+    """The seeded initialiser behind vae_decoder_state_dict and sd_unet_state_dict: every tensor is one draw of a generator of its own, in
+    call order (the goldens were made from these state dicts: the order of the draws is the contract).  Fan-in scaled weights, small biases,
+    norms near identity.  Keys in construction order."""
+
+    def __init__(self, seed):
+        self.g, self.sd = torch.Generator().manual_seed(seed), OrderedDict()
+
+    def conv(self, key, cout, cin, k, gain=1.0):
+        self.sd[key + '.weight'] = torch.randn(cout, cin, k, k, generator=self.g) * (gain / math.sqrt(cin * k * k))
+        self.sd[key + '.bias'] = torch.randn(cout, generator=self.g) * 0.05
+
+    def lin(self, key, cout, cin, gain=1.0, bias=True):
+        self.sd[key + '.weight'] = torch.randn(cout, cin, generator=self.g) * (gain / math.sqrt(cin))
+        if bias:
+            self.sd[key + '.bias'] = torch.randn(cout, generator=self.g) * 0.05
+
+    def norm(self, key, c):
+        self.sd[key + '.weight'] = 1.0 + 0.1 * torch.randn(c, generator=self.g)
+        self.sd[key + '.bias'] = 0.1 * torch.randn(c, generator=self.g)
+
+    def resnet(self, key, cin, cout, temb=None):
+        """ResnetBlock2D; temb: the width of the time embedding its time_emb_proj reads (None: a block without one, the VAE's)"""
+        self.norm(key + '.norm1', cin); self.conv(key + '.conv1', cout, cin, 3)
+        if temb is not None:
+            self.lin(key + '.time_emb_proj', cout, temb, gain=1.5)
+        self.norm(key + '.norm2', cout); self.conv(key + '.conv2', cout, cout, 3, gain=0.5)
+        if cin != cout:
+            self.conv(key + '.conv_shortcut', cout, cin, 1)
+
+
 def vae_decoder_state_dict(block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4, seed=0):
     """Random-init parameters of the SD VAE *decoder* (+ post_quant_conv) under diffusers' key names
     (sd/diffusers/src/diffusers/models/autoencoders/vae.py:204-279, autoencoder_kl.py:105-110): BASELINE config 4 prescribes
     random-init weights (SD-1.5's cannot be fetched).  Own seeded initialiser, fan-in scaled so activations stay O(1) through the
     17 residual blocks; norms near identity.  Keys in construction order."""
-    g = torch.Generator().manual_seed(seed)
-    sd = OrderedDict()
-
-    def conv(key, cout, cin, k, gain=1.0):
-        sd[key + '.weight'] = torch.randn(cout, cin, k, k, generator=g) * (gain / math.sqrt(cin * k * k))
-        sd[key + '.bias'] = torch.randn(cout, generator=g) * 0.05
-
-    def lin(key, cout, cin, gain=1.0):
-        sd[key + '.weight'] = torch.randn(cout, cin, generator=g) * (gain / math.sqrt(cin))
-        sd[key + '.bias'] = torch.randn(cout, generator=g) * 0.05
-
-    def norm(key, c):
-        sd[key + '.weight'] = 1.0 + 0.1 * torch.randn(c, generator=g)
-        sd[key + '.bias'] = 0.1 * torch.randn(c, generator=g)
-
-    def resnet(key, cin, cout):
-        norm(key + '.norm1', cin); conv(key + '.conv1', cout, cin, 3)
-        norm(key + '.norm2', cout); conv(key + '.conv2', cout, cout, 3, gain=0.5)
-        if cin != cout:
-            conv(key + '.conv_shortcut', cout, cin, 1)
-
+    b = _DiffusersBuilder(seed)
+    conv, lin, norm, resnet = b.conv, b.lin, b.norm, b.resnet
     top = block_out_channels[-1]
     conv('post_quant_conv', latent_channels, latent_channels, 1)
     conv('decoder.conv_in', top, latent_channels, 3)
@@ -252,7 +264,7 @@ def vae_decoder_state_dict(block_out_channels=(128, 256, 512, 512), layers_per_b
         prev = c
     norm('decoder.conv_norm_out', block_out_channels[0])
     conv('decoder.conv_out', 3, block_out_channels[0], 3)
-    return sd
+    return b.sd
 
 
 def sd_unet_state_dict(block_out_channels=(320, 640, 1280, 1280), heads=8, cross_attention_dim=768, layers_per_block=2, seed=0):
@@ -264,30 +276,11 @@ def sd_unet_state_dict(block_out_channels=(320, 640, 1280, 1280), heads=8, cross
     far more than a 16-bit pipeline's error -- a golden test could not otherwise tell a model that ignores them
     (tests/golden/make_golden_sd_unet.py asserts the margins).  `heads`: diffusers' `attention_head_dim` of SD-1.x, i.e. the number of
     heads of every transformer block.  Keys in construction order."""
-    g = torch.Generator().manual_seed(seed)
-    sd = OrderedDict()
+    b = _DiffusersBuilder(seed)
+    conv, lin, norm = b.conv, b.lin, b.norm
     boc = tuple(block_out_channels)
     temb = 4 * boc[0]
-
-    def conv(key, cout, cin, k, gain=1.0):
-        sd[key + '.weight'] = torch.randn(cout, cin, k, k, generator=g) * (gain / math.sqrt(cin * k * k))
-        sd[key + '.bias'] = torch.randn(cout, generator=g) * 0.05
-
-    def lin(key, cout, cin, gain=1.0, bias=True):
-        sd[key + '.weight'] = torch.randn(cout, cin, generator=g) * (gain / math.sqrt(cin))
-        if bias:
-            sd[key + '.bias'] = torch.randn(cout, generator=g) * 0.05
-
-    def norm(key, c):
-        sd[key + '.weight'] = 1.0 + 0.1 * torch.randn(c, generator=g)
-        sd[key + '.bias'] = 0.1 * torch.randn(c, generator=g)
-
-    def resnet(key, cin, cout):
-        norm(key + '.norm1', cin); conv(key + '.conv1', cout, cin, 3)
-        lin(key + '.time_emb_proj', cout, temb, gain=1.5)
-        norm(key + '.norm2', cout); conv(key + '.conv2', cout, cout, 3, gain=0.5)
-        if cin != cout:
-            conv(key + '.conv_shortcut', cout, cin, 1)
+    resnet = lambda key, cin, cout: b.resnet(key, cin, cout, temb=temb)
 
     def transformer(key, c):
         norm(key + '.norm', c)
@@ -337,4 +330,4 @@ def sd_unet_state_dict(block_out_channels=(320, 640, 1280, 1280), heads=8, cross
             conv(f'up_blocks.{i}.upsamplers.0.conv', c, c, 3)
     norm('conv_norm_out', boc[0])
     conv('conv_out', 4, boc[0], 3)
-    return sd
+    return b.sd

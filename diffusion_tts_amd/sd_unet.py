@@ -28,7 +28,7 @@ import types
 
 import torch
 
-from . import ops
+from . import blocks, ops
 from .graphs import GraphCache
 
 STOCK = {
@@ -102,8 +102,7 @@ class SDUNet:
                  layers_per_block=2, sample_size=64, device='cuda', dtype=torch.float16):
         """attention_head_dim: the NUMBER of heads of every transformer block (diffusers' historical name for it, unet_2d_condition.py:
         `num_attention_heads = num_attention_heads or attention_head_dim`)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError('SDUNet (HIP) needs a GPU: there is no CPU fallback in this package')
+        blocks.require_gpu('SDUNet')
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError('SDUNet: activations are float16 or bfloat16')
         self.device, self.dtype = torch.device(device), dtype
@@ -128,80 +127,47 @@ class SDUNet:
         with open(cfg_file) as f:
             cfg = json.load(f)
         check_config(cfg)
-        names = [n for n in ('diffusion_pytorch_model.safetensors', 'diffusion_pytorch_model.fp16.safetensors') if
-                 os.path.exists(os.path.join(path, n))]
-        if not names:
-            raise FileNotFoundError(f'{path}: no diffusion_pytorch_model[.fp16].safetensors (a .bin pickle is not read: convert it to safetensors)')
-        from safetensors import safe_open
-        sd = {}
-        with safe_open(os.path.join(path, names[0]), framework='pt', device='cpu') as f:
-            for k in f.keys():
-                sd[k] = f.get_tensor(k)
+        sd = blocks.read_tensors(blocks.diffusers_weights(path), lambda keys: {k: k for k in keys})
         kw = {k: cfg[k] for k in ('attention_head_dim', 'cross_attention_dim', 'layers_per_block', 'sample_size') if k in cfg}
         if 'block_out_channels' in cfg:
             kw['block_out_channels'] = tuple(cfg['block_out_channels'])
         return cls(sd, device=device, dtype=dtype, **kw)
 
     # ---- parameters ----------------------------------------------------------------------------
-    def _f(self, t):
-        return t.detach().to(self.device, torch.float32).contiguous()
-
-    def _pack(self, w, b=None, pad_in=None, pad_out=None):
-        """f32 weight [O, I] / [O, I, k, k] (+ bias) on the device -> (packed [O][k][k][I] in the activation dtype, f32 bias)"""
-        if w.dim() == 2:
-            w = w[:, :, None, None]
-        if pad_in is not None and w.shape[1] < pad_in:
-            w = torch.cat([w, torch.zeros(w.shape[0], pad_in - w.shape[1], *w.shape[2:], device=w.device)], 1)
-        if pad_out is not None and w.shape[0] < pad_out:
-            w = torch.cat([w, torch.zeros(pad_out - w.shape[0], *w.shape[1:], device=w.device)], 0)
-            if b is not None:
-                b = torch.cat([b, torch.zeros(pad_out - b.shape[0], device=b.device)])
-        return ops.pack_conv_weight(w.contiguous(), self.dtype), (None if b is None else b.contiguous())
-
-    def _conv(self, sd, key, **kw):
-        return self._pack(self._f(sd[key + '.weight']), self._f(sd[key + '.bias']), **kw)
-
     def _resnet_params(self, sd, key):
-        P = types.SimpleNamespace()
-        P.g1, P.b1 = self._f(sd[key + '.norm1.weight']), self._f(sd[key + '.norm1.bias'])
-        P.w1, P.c1 = self._conv(sd, key + '.conv1')
-        P.g2, P.b2 = self._f(sd[key + '.norm2.weight']), self._f(sd[key + '.norm2.bias'])
-        P.w2, P.c2 = self._conv(sd, key + '.conv2')
-        P.ws = P.cs = None
-        if key + '.conv_shortcut.weight' in sd:
-            P.ws, P.cs = self._conv(sd, key + '.conv_shortcut')
+        P = blocks.resnet_params(self._p, sd, key)
         # time_emb_proj of every block is one row block of a single f32 matrix: one dts_linear per forward instead of 22
         P.cout = P.w1.shape[0]
         P.toff = self._tcols
-        self._tw.append(self._f(sd[key + '.time_emb_proj.weight']))
-        self._tb.append(self._f(sd[key + '.time_emb_proj.bias']))
+        self._tw.append(self._p.f32(sd[key + '.time_emb_proj.weight']))
+        self._tb.append(self._p.f32(sd[key + '.time_emb_proj.bias']))
         self._tcols += P.cout
         return P
 
     def _transformer_params(self, sd, key, c):
-        H = self.heads
+        H, p = self.heads, self._p
         if c % H:
             raise ValueError(f'SDUNet: {c} channels do not split into {H} heads')
         d = c // H
         dp = padded_head_dim(d)
         A = types.SimpleNamespace(heads=H, scale=1.0 / math.sqrt(d), hp=H * dp)
-        A.g, A.b = self._f(sd[key + '.norm.weight']), self._f(sd[key + '.norm.bias'])
+        A.g, A.b = p.norm(sd, key + '.norm')
         if sd[key + '.proj_in.weight'].dim() != 4:
             raise ValueError('SDUNet: use_linear_projection=True (a Linear proj_in) is not the stock SD-1.x U-Net')
-        A.w_in, A.b_in = self._conv(sd, key + '.proj_in')
-        A.w_out, A.b_out = self._conv(sd, key + '.proj_out')
+        A.w_in, A.b_in = p.conv(sd, key + '.proj_in')
+        A.w_out, A.b_out = p.conv(sd, key + '.proj_out')
         t = key + '.transformer_blocks.0'
         if key + '.transformer_blocks.1.norm1.weight' in sd:
             raise ValueError('SDUNet: transformer_layers_per_block > 1 is not the stock SD-1.x U-Net')
-        A.ln = [(self._f(sd[f'{t}.norm{i}.weight']), self._f(sd[f'{t}.norm{i}.bias'])) for i in (1, 2, 3)]
-        rows = lambda name: pad_head_rows(self._f(sd[f'{t}.{name}.weight']), H, dp)
-        A.w_qkv, _ = self._pack(torch.cat([rows('attn1.to_q'), rows('attn1.to_k'), rows('attn1.to_v')], 0))      # q | k | v blocks
-        A.w_o1, A.b_o1 = self._pack(pad_head_cols(self._f(sd[f'{t}.attn1.to_out.0.weight']), H, dp), self._f(sd[f'{t}.attn1.to_out.0.bias']))
-        A.w_q2, _ = self._pack(rows('attn2.to_q'))
-        A.w_kv2, _ = self._pack(torch.cat([rows('attn2.to_k'), rows('attn2.to_v')], 0))                           # k | v blocks, cin = text width
-        A.w_o2, A.b_o2 = self._pack(pad_head_cols(self._f(sd[f'{t}.attn2.to_out.0.weight']), H, dp), self._f(sd[f'{t}.attn2.to_out.0.bias']))
-        A.w_ff1, A.b_ff1 = self._conv(sd, f'{t}.ff.net.0.proj')
-        A.w_ff2, A.b_ff2 = self._conv(sd, f'{t}.ff.net.2')
+        A.ln = [p.norm(sd, f'{t}.norm{i}') for i in (1, 2, 3)]
+        rows = lambda name: pad_head_rows(p.f32(sd[f'{t}.{name}.weight']), H, dp)
+        A.w_qkv, _ = p.pack(torch.cat([rows('attn1.to_q'), rows('attn1.to_k'), rows('attn1.to_v')], 0))      # q | k | v blocks
+        A.w_o1, A.b_o1 = p.pack(pad_head_cols(p.f32(sd[f'{t}.attn1.to_out.0.weight']), H, dp), p.f32(sd[f'{t}.attn1.to_out.0.bias']))
+        A.w_q2, _ = p.pack(rows('attn2.to_q'))
+        A.w_kv2, _ = p.pack(torch.cat([rows('attn2.to_k'), rows('attn2.to_v')], 0))                           # k | v blocks, cin = text width
+        A.w_o2, A.b_o2 = p.pack(pad_head_cols(p.f32(sd[f'{t}.attn2.to_out.0.weight']), H, dp), p.f32(sd[f'{t}.attn2.to_out.0.bias']))
+        A.w_ff1, A.b_ff1 = p.conv(sd, f'{t}.ff.net.0.proj')
+        A.w_ff2, A.b_ff2 = p.conv(sd, f'{t}.ff.net.2')
         A.index = len(self._tfm)
         self._tfm.append(A)
         return A
@@ -219,12 +185,8 @@ class SDUNet:
                 want[f'down_blocks.{i}.attentions.0.transformer_blocks.0.attn1.to_q.weight'] = (c, c)
             if c % self.heads:
                 raise ValueError(f'SDUNet: block_out_channels {boc} do not split into attention_head_dim={self.heads} heads')
-        for key, shape in want.items():
-            if key not in sd:
-                raise ValueError(f'SDUNet: the state dict has no {key!r} (block_out_channels={boc}, layers_per_block={self.lpb})')
-            if tuple(sd[key].shape) != shape:
-                raise ValueError(f'SDUNet: {key} has shape {tuple(sd[key].shape)}, but block_out_channels={boc}, '
-                                 f'cross_attention_dim={self.ctx_dim} ask for {shape}')
+        blocks.check_shapes('SDUNet', sd, want, f'block_out_channels={boc}, layers_per_block={self.lpb}',
+                            f'block_out_channels={boc}, cross_attention_dim={self.ctx_dim}')
         extra = f'down_blocks.0.resnets.{self.lpb}.conv1.weight'
         if extra in sd:
             raise ValueError(f'SDUNet: the state dict has {extra!r}: more than layers_per_block={self.lpb} resnets per block')
@@ -232,12 +194,13 @@ class SDUNet:
     def _load(self, sd):
         self._check_shapes(sd)
         boc, lpb = self.boc, self.lpb
+        p = self._p = blocks.Params(self.device, self.dtype)
         self._tw, self._tb, self._tcols, self._tfm = [], [], 0, []
         half = boc[0] // 2
         self.freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half).to(self.device)    # freq_shift = 0
-        self.t1 = (self._f(sd['time_embedding.linear_1.weight']), self._f(sd['time_embedding.linear_1.bias']))
-        self.t2 = (self._f(sd['time_embedding.linear_2.weight']), self._f(sd['time_embedding.linear_2.bias']))
-        self.conv_in = self._conv(sd, 'conv_in', pad_in=64)
+        self.t1 = (p.f32(sd['time_embedding.linear_1.weight']), p.f32(sd['time_embedding.linear_1.bias']))
+        self.t2 = (p.f32(sd['time_embedding.linear_2.weight']), p.f32(sd['time_embedding.linear_2.bias']))
+        self.conv_in = p.conv(sd, 'conv_in', pad_in=64)
         self.down = []
         for i, c in enumerate(boc):
             cross = i != len(boc) - 1
@@ -247,8 +210,8 @@ class SDUNet:
                                self._transformer_params(sd, f'down_blocks.{i}.attentions.{j}', c) if cross else None))
             ds = None
             if i != len(boc) - 1:
-                w = ops.stride2_conv_weight(self._f(sd[f'down_blocks.{i}.downsamplers.0.conv.weight']))
-                ds = self._pack(w, self._f(sd[f'down_blocks.{i}.downsamplers.0.conv.bias']))
+                w = ops.stride2_conv_weight(p.f32(sd[f'down_blocks.{i}.downsamplers.0.conv.weight']))
+                ds = p.pack(w, p.f32(sd[f'down_blocks.{i}.downsamplers.0.conv.bias']))
             self.down.append((layers, ds))
         self.mid = (self._resnet_params(sd, 'mid_block.resnets.0'), self._transformer_params(sd, 'mid_block.attentions.0', boc[-1]),
                     self._resnet_params(sd, 'mid_block.resnets.1'))
@@ -260,29 +223,17 @@ class SDUNet:
             for j in range(lpb + 1):
                 layers.append((self._resnet_params(sd, f'up_blocks.{i}.resnets.{j}'),
                                self._transformer_params(sd, f'up_blocks.{i}.attentions.{j}', c) if cross else None))
-            us = self._conv(sd, f'up_blocks.{i}.upsamplers.0.conv') if i != len(rev) - 1 else None
+            us = p.conv(sd, f'up_blocks.{i}.upsamplers.0.conv') if i != len(rev) - 1 else None
             self.up.append((layers, us))
-        self.out_g, self.out_b = self._f(sd['conv_norm_out.weight']), self._f(sd['conv_norm_out.bias'])
-        self.conv_out = self._conv(sd, 'conv_out', pad_out=64)
+        self.out_g, self.out_b = p.norm(sd, 'conv_norm_out')
+        self.conv_out = p.conv(sd, 'conv_out', pad_out=64)
         self.tproj = (torch.cat(self._tw, 0).contiguous(), torch.cat(self._tb).contiguous())
-        del self._tw, self._tb
+        del self._tw, self._tb, self._p
         torch.cuda.synchronize(self.device)
 
     # ---- forward -------------------------------------------------------------------------------
     def _resnet(self, x, P, temb, skip=None):
-        """ResnetBlock2D.forward (resnet.py): norm1-silu-conv1 (+ time_emb_proj(silu(emb)) per sample and channel)-norm2-silu-conv2,
-        + the input or its 1x1 shortcut.  skip: the second half of the up blocks' torch.cat([x, skip], 1), read in place."""
-        G = self.groups
-        h = ops.group_norm(x, G, self.eps, P.g1, P.b1, x2=skip, silu=True)
-        h = ops.conv2d(h, P.w1, P.c1, bias_nc=temb[:, P.toff:P.toff + P.cout], gn_stats=True)
-        h = ops.group_norm(h, G, self.eps, P.g2, P.b2, silu=True)
-        if P.ws is not None:
-            sk = ops.conv2d(x, P.ws, P.cs, x2=skip)
-        elif skip is None:
-            sk = x
-        else:
-            raise ValueError('SDUNet: a resnet over concatenated inputs needs its conv_shortcut')
-        return ops.conv2d(h, P.w2, P.c2, residual=sk, gn_stats=True)
+        return blocks.resnet(x, P, self.groups, self.eps, bias_nc=temb[:, P.toff:P.toff + P.cout], skip=skip)
 
     def _transformer(self, x, A, kv, kv_rows):
         """Transformer2DModel.forward with one BasicTransformerBlock (transformer_2d.py, attention.py): tokens stay in NHWC, every

@@ -17,14 +17,13 @@ import types
 
 import torch
 
-from . import ops
+from . import blocks, ops
 
 
 class VAEDecoder:
     def __init__(self, state_dict, block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4, norm_num_groups=32,
                  scaling_factor=0.18215, device='cuda', dtype=torch.float16):
-        if not torch.cuda.is_available():
-            raise RuntimeError('VAEDecoder (HIP) needs a GPU: there is no CPU fallback in this package')
+        blocks.require_gpu('VAEDecoder')
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError('VAEDecoder: activations are float16 or bfloat16 (head dim 512 attention is 16-bit only)')
         self.device, self.dtype = torch.device(device), dtype
@@ -41,97 +40,49 @@ class VAEDecoder:
         Only the decoder half (`decoder.*`, `post_quant_conv.*`) is read; tensors are loaded lazily, so the encoder never leaves disk."""
         import json
         import os
-        from safetensors import safe_open
         cfg = {}
         if os.path.isdir(path):
             cfg_file = os.path.join(path, 'config.json')
             if os.path.exists(cfg_file):
                 with open(cfg_file) as f:
                     cfg = json.load(f)
-            names = [n for n in ('diffusion_pytorch_model.safetensors', 'diffusion_pytorch_model.fp16.safetensors') if
-                     os.path.exists(os.path.join(path, n))]
-            if not names:
-                raise FileNotFoundError(f'{path}: no diffusion_pytorch_model[.fp16].safetensors (a .bin pickle is not read: convert it to safetensors)')
-            path = os.path.join(path, names[0])
+            path = blocks.diffusers_weights(path)
         for key, want in (('act_fn', 'silu'), ('_class_name', 'AutoencoderKL')):
             if key in cfg and cfg[key] != want:
                 raise ValueError(f'VAEDecoder: {key}={cfg[key]!r} is not the stock SD VAE ({want!r})')
         for t in cfg.get('up_block_types', []):
             if t != 'UpDecoderBlock2D':
                 raise ValueError(f'VAEDecoder: up block {t!r} unsupported')
-        sd = {}
-        with safe_open(path, framework='pt', device='cpu') as f:
-            for k in f.keys():
-                if k.startswith('decoder.') or k.startswith('post_quant_conv.'):
-                    sd[k] = f.get_tensor(k)
-        if not sd:
-            raise ValueError(f'{path}: no decoder.* tensors')
+        sd = blocks.read_tensors(path, lambda keys: {k: k for k in keys if k.startswith(('decoder.', 'post_quant_conv.'))}, 'decoder.*')
         kw = {k: cfg[k] for k in ('layers_per_block', 'latent_channels', 'norm_num_groups', 'scaling_factor') if k in cfg}
         if 'block_out_channels' in cfg:
             kw['block_out_channels'] = tuple(cfg['block_out_channels'])
         return cls(sd, device=device, dtype=dtype, **kw)
 
     # ------------------------------------------------------------------------------------------
-    def _f(self, t):
-        return t.detach().to(self.device, torch.float32).contiguous()
-
-    def _conv_params(self, sd, key, pad_in=None, pad_out=None):
-        w, b = self._f(sd[key + '.weight']), self._f(sd[key + '.bias'])
-        if w.dim() == 2:                                           # Linear -> 1x1 conv
-            w = w[:, :, None, None].contiguous()
-        if pad_in is not None and w.shape[1] < pad_in:             # zero input channels up to the MFMA granule
-            w = torch.cat([w, torch.zeros(w.shape[0], pad_in - w.shape[1], *w.shape[2:], device=w.device)], 1).contiguous()
-        if pad_out is not None and w.shape[0] < pad_out:
-            w = torch.cat([w, torch.zeros(pad_out - w.shape[0], *w.shape[1:], device=w.device)], 0).contiguous()
-            b = torch.cat([b, torch.zeros(pad_out - b.shape[0], device=b.device)]).contiguous()
-        return ops.pack_conv_weight(w, self.dtype), b
-
-    def _resnet_params(self, sd, key):
-        P = types.SimpleNamespace()
-        P.g1, P.b1 = self._f(sd[key + '.norm1.weight']), self._f(sd[key + '.norm1.bias'])
-        P.w1, P.c1 = self._conv_params(sd, key + '.conv1')
-        P.g2, P.b2 = self._f(sd[key + '.norm2.weight']), self._f(sd[key + '.norm2.bias'])
-        P.w2, P.c2 = self._conv_params(sd, key + '.conv2')
-        P.ws = P.cs = None
-        if key + '.conv_shortcut.weight' in sd:
-            P.ws, P.cs = self._conv_params(sd, key + '.conv_shortcut')
-        return P
-
     def _load(self, sd):
-        top = self.boc[-1]
-        self.pq = self._conv_params(sd, 'post_quant_conv', pad_in=64, pad_out=64) if 'post_quant_conv.weight' in sd else None
-        self.conv_in = self._conv_params(sd, 'decoder.conv_in', pad_in=64)
-        self.mid0 = self._resnet_params(sd, 'decoder.mid_block.resnets.0')
-        self.mid1 = self._resnet_params(sd, 'decoder.mid_block.resnets.1')
+        p = blocks.Params(self.device, self.dtype)
+        self.pq = p.conv(sd, 'post_quant_conv', pad_in=64, pad_out=64) if 'post_quant_conv.weight' in sd else None
+        self.conv_in = p.conv(sd, 'decoder.conv_in', pad_in=64)
+        self.mid0 = blocks.resnet_params(p, sd, 'decoder.mid_block.resnets.0')
+        self.mid1 = blocks.resnet_params(p, sd, 'decoder.mid_block.resnets.1')
         a = 'decoder.mid_block.attentions.0'
         A = types.SimpleNamespace()
-        A.g, A.b = self._f(sd[a + '.group_norm.weight']), self._f(sd[a + '.group_norm.bias'])
-        wq = torch.cat([self._f(sd[a + f'.to_{n}.weight']) for n in 'qkv'], 0)[:, :, None, None].contiguous()     # q | k | v blocks
-        A.wqkv = ops.pack_conv_weight(wq, self.dtype)
-        A.bqkv = torch.cat([self._f(sd[a + f'.to_{n}.bias']) for n in 'qkv']).contiguous()
-        A.wo, A.bo = self._conv_params(sd, a + '.to_out.0')
-        A.dim = top
+        A.g, A.b = p.norm(sd, a + '.group_norm')
+        A.wqkv, A.bqkv = p.qkv(sd, a, ('to_q', 'to_k', 'to_v'))                                                      # q | k | v blocks
+        A.wo, A.bo = p.conv(sd, a + '.to_out.0')
         self.attn = A
         self.up = []
         for i in range(len(self.boc)):
-            res = [self._resnet_params(sd, f'decoder.up_blocks.{i}.resnets.{j}') for j in range(self.lpb + 1)]
-            ups = self._conv_params(sd, f'decoder.up_blocks.{i}.upsamplers.0.conv') if i != len(self.boc) - 1 else None
+            res = [blocks.resnet_params(p, sd, f'decoder.up_blocks.{i}.resnets.{j}') for j in range(self.lpb + 1)]
+            ups = p.conv(sd, f'decoder.up_blocks.{i}.upsamplers.0.conv') if i != len(self.boc) - 1 else None
             self.up.append((res, ups))
-        self.out_g, self.out_b = self._f(sd['decoder.conv_norm_out.weight']), self._f(sd['decoder.conv_norm_out.bias'])
-        self.out_w = self._f(sd['decoder.conv_out.weight']).permute(0, 2, 3, 1).contiguous()       # [3][kh][kw][c]
-        self.out_cb = self._f(sd['decoder.conv_out.bias'])
+        self.out_g, self.out_b = p.norm(sd, 'decoder.conv_norm_out')
+        self.out_w = p.f32(sd['decoder.conv_out.weight']).permute(0, 2, 3, 1).contiguous()         # [3][kh][kw][c]
+        self.out_cb = p.f32(sd['decoder.conv_out.bias'])
         torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------------------------------
-    def _resnet(self, x, P):
-        """ResnetBlock2D.forward with temb None: norm1-silu-conv1-norm2-silu-conv2, + (1x1 shortcut of) the input."""
-        G = self.groups
-        h = ops.group_norm(x, G, 1e-6, P.g1, P.b1, silu=True)
-        h = ops.conv2d(h, P.w1, P.c1, gn_stats=True)
-        h = ops.group_norm(h, G, 1e-6, P.g2, P.b2, silu=True)
-        sk = x if P.ws is None else ops.conv2d(x, P.ws, P.cs)
-        return ops.conv2d(h, P.w2, P.c2, residual=sk, gn_stats=True)
-
     def _attention(self, x):
         """AttnProcessor2_0 on [n, hw, c]: group norm, fused q|k|v projection, one head of dim c, output projection + residual."""
         A = self.attn
@@ -150,12 +101,12 @@ class VAEDecoder:
         if self.pq is not None:
             x = ops.conv2d(x, self.pq[0], self.pq[1])                           # 1x1 on the 4 (of 64) live channels
         x = ops.conv2d(x, self.conv_in[0], self.conv_in[1], gn_stats=True)
-        x = self._resnet(x, self.mid0)
+        x = blocks.resnet(x, self.mid0, self.groups, 1e-6)                      # ResnetBlock2D with temb None
         x = self._attention(x)
-        x = self._resnet(x, self.mid1)
+        x = blocks.resnet(x, self.mid1, self.groups, 1e-6)
         for res, ups in self.up:
             for P in res:
-                x = self._resnet(x, P)
+                x = blocks.resnet(x, P, self.groups, 1e-6)
             if ups is not None:
                 x = ops.conv2d(x, ups[0], ups[1], up=True, gn_stats=True)       # nearest-2x fused into the conv's gather
         h = ops.group_norm(x, self.groups, 1e-6, self.out_g, self.out_b, silu=True)

@@ -22,8 +22,8 @@ import warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from diffusion_tts_amd import ops
 from diffusion_tts_amd.clip_vision import CLIPVisionTower
+from op_timing import op_shares, timed_forward
 
 PEAK_16BIT_DENSE = 2.5e15          # MI355X dense f16 / bf16 matrix peak, FLOP/s
 FAMILY = {'conv2d': 'conv (1x1: projections, MLP, patch embedding)', 'attention': 'attention', 'layer_norm': 'layer_norm', 'gelu': 'gelu',
@@ -41,48 +41,6 @@ def vit_l14(layers):
                               patch_size=14, projection_dim=768)
         torch.manual_seed(0)
         return CLIPModel(CLIPConfig(text_config=tc.to_dict(), vision_config=vc.to_dict(), projection_dim=768)).eval()
-
-
-def op_shares(tower, pix):
-    """one forward with device events around every ops.* call of the module"""
-    spans, saved = [], {}
-    for name, fam in FAMILY.items():
-        fn = saved[name] = getattr(ops, name)
-
-        def timed(*a, _fn=fn, _fam=fam, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = _fn(*a, **kw)
-            e1.record()
-            spans.append((_fam, e0, e1))
-            return r
-        setattr(ops, name, timed)
-    try:
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        tower(pix)
-        e1.record()
-        torch.cuda.synchronize()
-    finally:
-        for name, fn in saved.items():
-            setattr(ops, name, fn)
-    fam_ms = {}
-    for fam, a, b in spans:
-        fam_ms[fam] = fam_ms.get(fam, 0.0) + a.elapsed_time(b)
-    total = e0.elapsed_time(e1)
-    inside = sum(fam_ms.values())
-    fam_ms['other (torch glue, launch gaps)'] = max(0.0, total - inside)
-    return {k: round(v / total, 4) for k, v in sorted(fam_ms.items(), key=lambda kv: -kv[1])}, round(inside / total, 4), len(spans)
-
-
-def timed_forward(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
 
 
 def main():
@@ -127,7 +85,7 @@ def main():
         ms, o_hip = timed_forward(run_hip)
         t_hip.append(ms)
     ms_tf, ms_hip = statistics.median(t_tf), statistics.median(t_hip)
-    shares, inside, calls = op_shares(tower, pix)
+    shares, inside, calls = op_shares(FAMILY, lambda: tower(pix))
     flops = tower.flops(a.rows)
     res = {'what': 'CLIP image tower forward, ViT-L/14 shape, random-init weights, float16', 'rows': a.rows, 'layers': a.layers, 'tokens': tower.tokens,
            'pixel_values': [3, 224, 224], 'iters': a.iters, 'warmup': a.warmup, 'device': torch.cuda.get_device_name(0),

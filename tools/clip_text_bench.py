@@ -24,6 +24,7 @@ sys.path.insert(0, ROOT)
 import torch
 from diffusion_tts_amd import ops
 from diffusion_tts_amd.clip_text import CLIPTextTower
+from op_timing import op_shares, timed_forward
 
 FAMILY = {'conv2d': 'conv (1x1: projections, MLP)', 'attention_masked': 'attention_masked', 'layer_norm': 'layer_norm', 'gelu': 'gelu',
           'text_tokens': 'text_tokens (incl. the host check and the upload of the ids)', 'cast_to_f32': 'projection (cast, linear)',
@@ -38,48 +39,6 @@ def sd15_text(layers):
                             max_position_embeddings=77, projection_dim=768, bos_token_id=49406, eos_token_id=49407, pad_token_id=49407)
         torch.manual_seed(0)
         return CLIPTextModel(tc).eval()
-
-
-def op_shares(tower, ids):
-    """one forward with device events around every ops.* call of the module"""
-    spans, saved = [], {}
-    for name, fam in FAMILY.items():
-        fn = saved[name] = getattr(ops, name)
-
-        def timed(*a, _fn=fn, _fam=fam, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = _fn(*a, **kw)
-            e1.record()
-            spans.append((_fam, e0, e1))
-            return r
-        setattr(ops, name, timed)
-    try:
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        tower(ids)
-        e1.record()
-        torch.cuda.synchronize()
-    finally:
-        for name, fn in saved.items():
-            setattr(ops, name, fn)
-    fam_ms = {}
-    for fam, a, b in spans:
-        fam_ms[fam] = fam_ms.get(fam, 0.0) + a.elapsed_time(b)
-    total = e0.elapsed_time(e1)
-    inside = sum(fam_ms.values())
-    fam_ms['other (torch glue, launch gaps)'] = max(0.0, total - inside)
-    return {k: round(v / total, 4) for k, v in sorted(fam_ms.items(), key=lambda kv: -kv[1])}, round(inside / total, 4), len(spans)
-
-
-def timed_forward(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
 
 
 def kernel_us(fn, reps=200):
@@ -140,7 +99,7 @@ def main():
         ms, o_hip = timed_forward(run_hip)
         t_hip.append(ms)
     ms_tf, ms_hip = statistics.median(t_tf), statistics.median(t_hip)
-    shares, inside, calls = op_shares(tower, ids)
+    shares, inside, calls = op_shares(FAMILY, lambda: tower(ids))
     qkv = torch.randn(a.rows, 77, 3 * 768, generator=torch.Generator().manual_seed(1)).to('cuda', torch.float16)
     us_att = kernel_us(lambda: ops.attention_masked(qkv, 12, 0.125, causal=True))
     us_att_plain = kernel_us(lambda: ops.attention(qkv, 12, 0.125))

@@ -32,6 +32,7 @@ import torch
 from diffusion_tts_amd import init as dinit
 from diffusion_tts_amd import ops
 from diffusion_tts_amd.sd_unet import SDUNet
+from op_timing import op_shares
 
 PEAK_16BIT_DENSE = 2.5e15          # MI355X dense f16 / bf16 matrix peak, FLOP/s
 
@@ -84,38 +85,6 @@ def forward_flops(boc=(320, 640, 1280, 1280), heads=8, ctx_dim=768, ctx_len=77, 
 FAMILY = {'conv2d': 'conv', 'group_norm': 'group_norm', 'attention': 'self_attention', 'cross_attention': 'cross_attention',
           'layer_norm': 'layer_norm', 'geglu': 'geglu', 'linear': 'time_embedding', 'pos_embedding': 'time_embedding',
           'cast_from_f32': 'time_embedding', 'space_to_depth2': 'layout', 'nchw_to_nhwc_pad': 'layout'}
-
-
-def op_shares(unet, x, t, ehs):
-    """one forward with device events around every ops.* call of the module"""
-    spans, saved = [], {}
-    for name, fam in FAMILY.items():
-        fn = saved[name] = getattr(ops, name)
-
-        def timed(*a, _fn=fn, _fam=fam, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = _fn(*a, **kw)
-            e1.record()
-            spans.append((_fam, e0, e1))
-            return r
-        setattr(ops, name, timed)
-    try:
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        unet(x, t, encoder_hidden_states=ehs)
-        e1.record()
-        torch.cuda.synchronize()
-    finally:
-        for name, fn in saved.items():
-            setattr(ops, name, fn)
-    fam_ms = {}
-    for fam, a, b in spans:
-        fam_ms[fam] = fam_ms.get(fam, 0.0) + a.elapsed_time(b)
-    total = e0.elapsed_time(e1)
-    fam_ms['other (torch glue, launch gaps)'] = max(0.0, total - sum(fam_ms.values()))
-    return {k: round(v / total, 4) for k, v in sorted(fam_ms.items(), key=lambda kv: -kv[1])}, len(spans)
 
 
 def grouping(ehs, reps=20):
@@ -203,7 +172,7 @@ def main():
                     outs[mode, form] = out
         same = all(torch.equal(o, outs['eager', 'stock']) for o in outs.values())
         unet._graphs.enabled = False                       # the per-op spans need the ops.* calls of an eager forward
-        shares, launches = op_shares(unet, x, t, ehs)
+        shares, _, launches = op_shares(FAMILY, lambda: unet(x, t, encoder_hidden_states=ehs))
         unet._graphs.enabled = True
         ms = statistics.median(times['eager', 'stock'])
         stat = lambda v: {'ms_median': round(statistics.median(v), 3), 'ms_min': round(min(v), 3), 'ms_max': round(max(v), 3)}
