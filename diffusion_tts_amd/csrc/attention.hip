@@ -44,6 +44,30 @@ __device__ __forceinline__ float vmax2(float a, float b) {
   return r;
 }
 
+// Pieces of the flash-attention step that are written once.  A helper is used only where it left the kernel's instruction stream as it
+// was (tools/kernel_diff.py against the build before it); forced inlining is not free here.  A helper for the -inf select on the scores
+// (array by reference, or one f32x4_t by value) rescheduled every 16-bit instantiation, att_vt_frag moved an instruction in
+// attention_x3_kernel<1, 0>, and the three-permute exchange as a helper rescheduled attention_x3_kernel<2, 7>: those stay written out.
+// Maximum of a lane's 16 scores.  Raw v_max3_f32 / v_max_f32: fmaxf() makes hipcc canonicalise every operand first (IEEE sNaN quieting, one
+// extra v_max per value: 46 vector instructions per key tile instead of 20 in a loop that is vector-issue bound); no NaN can occur here
+__device__ __forceinline__ float att_max16(const f32x4_t (&s)[4]) {
+  float m = vmax3(s[0][0], s[0][1], s[0][2]);
+  m = vmax3(m, s[0][3], s[1][0]);
+  m = vmax3(m, s[1][1], s[1][2]);
+  m = vmax3(m, s[1][3], s[2][0]);
+  m = vmax3(m, s[2][1], s[2][2]);
+  m = vmax3(m, s[2][3], s[3][0]);
+  m = vmax3(m, s[3][1], s[3][2]);
+  return vmax2(m, s[3][3]);
+}
+// V^T fragment (A operand) of 32 keys x 16 channels: two transposing 8-byte reads, 16 key rows apart, ARE the operand's four dwords
+// (element-wise repacking compiled to 16 shift/or ops).  Lane 4q'+p' of each 16-lane group addresses row q', columns 4p'..4p'+3 of a 4x16 block.
+__device__ __forceinline__ uint4 att_vt_frag(const char* lo, const char* hi) {
+  const uint2 l = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)lo));
+  const uint2 h = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)hi));
+  return make_uint4(l.x, l.y, h.x, h.y);
+}
+
 __device__ uint4 g_att_zero[64];      // 1 KiB of zeros: LDS-DMA source of key rows past the end of a ragged sequence
 
 // LDS-DMA (global -> LDS, no registers), 16 bytes per active lane; lds_off = wave-uniform LDS byte address of lane 0's slot.  Inline asm:
@@ -59,6 +83,8 @@ struct AttP {
   int qblocks;                   // query blocks per (sample, head)
   int xcd_remap;                 // 1: XCD-aware block order (default); 0: plain order (A/B aid, DTS_ATT_XCD=0)
   int out_split3;                // attention_x3_kernel: the output leaves as the split-precision conv operand image, per 32 channels hi | lo * 2^11 (f16 [n][t][2C])
+  const int32_t* key_len;        // MASK form only (dts_attention_masked): keys per sample, [n] on the device, or null
+  int causal;                    // MASK form only
 };
 
 // Block order.  The grid is 1-D over (sample*head, query block), (sample, head)-major.  Hardware deals consecutive block ids
@@ -92,10 +118,22 @@ __device__ __forceinline__ void att_block(const AttP& p, int& nh, int& qb) {
 // LDS-DMA instead of through registers (the 256 VGPRs of this instantiation leave no room for a register prefetch, and without one
 // every key tile paid six dependent global-load round trips: the kernel ran 8x below its MFMA time).  K and V have separate buffers
 // and separate phases: K(t+1) flies while the softmax and P.V of tile t run, V(t+1) while Q.K^T of tile t+1 runs; four barriers per tile.
-template <typename T, int D, int QT, int DV = D, bool PREF = true, bool DB = false, bool DMA = false>
+// MASK (dts_attention_masked; head dim 64, QT = 1): CLIP's text transformer (transformers modeling_clip.py, CLIPTextTransformer: a causal
+// mask, plus the tokenizer's attention_mask for the text encoders that use it).  Query i of sample b sees key j iff (!causal || j <= i) &&
+// j < kend, kend = min(t, key_len[b]).  Fragments, LDS rows and arithmetic are the unmasked form's; what differs:
+//   * a block walks only the key tiles that hold a key some query of it may see: tiles below min(kend, end of the query block).  A tile
+//     wholly above the diagonal or wholly past kend is never staged -- with every score -inf and the running maximum still -inf the
+//     exponent would be -inf - (-inf) = NaN.  Every tile that IS walked starts at a key key0 <= the block's first query and key0 < kend,
+//     so every query has a finite score in every tile it meets and the running maximum is finite from tile 0 on.  The tile count is the
+//     same for the four waves: the barriers stay block-uniform.
+//   * the select to -inf that masks the tail past t takes the lane's own limit (nothing of a disallowed key reaches the output as long
+//     as v is finite); only the diagonal tile (causal) and the tile that holds kend pay for it.
+//   * key rows from kend on are staged as zeros, not read.
+template <typename T, int D, int QT, int DV = D, bool PREF = true, bool DB = false, bool DMA = false, bool MASK = false>
 __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
   static_assert(!DB || PREF, "double buffering rides on the register prefetch");
   static_assert(!DMA || (D == 512 && DV == 256 && QT == 1 && !PREF && !DB), "LDS-DMA staging: the head-dim-512 form only");
+  static_assert(!MASK || (D == 64 && QT == 1 && DV == D && PREF && !DB && !DMA), "masked form: head dim 64, one query tile, single-buffered register prefetch");
   constexpr int ES = 2, ROWB = D * ES + 32;        // LDS row stride of K in bytes
   constexpr int VROWB = DV * ES + 32;              // LDS row stride of the V slice
   constexpr int CH = D / 8;                        // 16-byte chunks per K row
@@ -120,6 +158,13 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
   const size_t rowstride = (size_t)3 * C * ES;
   const char* base = p.qkv + (size_t)n * p.t * rowstride + (size_t)head * D * ES;
   const int q0 = qblk * (64 * QT) + wid * (16 * QT);
+  // kend: the keys of this sample; lim: this lane's query sees keys < lim (>= 1); ntiles: the key tiles this block walks
+  int kend = p.t, lim = p.t, ntiles = (p.t + 63) / 64;
+  if constexpr (MASK) {
+    if (p.key_len) kend = min(p.t, max(1, p.key_len[n]));          // the caller vouches for 1 <= key_len <= t, clamped for memory safety only
+    lim = p.causal ? min(kend, q0 + lq + 1) : kend;
+    ntiles = ((p.causal ? min(kend, qblk * 64 + 64) : kend) + 63) / 64;
+  }
 
   // Q fragments: B operand, lane holds Q[q][8*(lg + 4s) .. +8]
   uint4 qf[QT][KSTEPS];
@@ -149,7 +194,6 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
     for (int i = 0; i < DT; ++i) o[qt][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int ntiles = (p.t + 63) / 64;
   constexpr int NCH = (64 * CH) / 256;             // 16-byte chunks of K staged per thread per tile
   constexpr int NCHV = (64 * CHV) / 256;           // ... of the V slice
   constexpr int NPF = PREF ? NCH : 1, NPFV = PREF ? NCHV : 1;
@@ -160,12 +204,12 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
   _Pragma("unroll") for (int u = 0; u < NCH; ++u) {                                               \
     const int idx = tid + 256 * u, r = idx / CH, c = idx - r * CH;                                \
     pk[u] = make_uint4(0, 0, 0, 0);                                                               \
-    if ((key0_) + r < p.t) pk[u] = *reinterpret_cast<const uint4*>(base + (size_t)((key0_) + r) * rowstride + c * 16 + (size_t)C * ES); \
+    if ((key0_) + r < kend) pk[u] = *reinterpret_cast<const uint4*>(base + (size_t)((key0_) + r) * rowstride + c * 16 + (size_t)C * ES); \
   }                                                                                               \
   _Pragma("unroll") for (int u = 0; u < NCHV; ++u) {                                              \
     const int idx = tid + 256 * u, r = idx / CHV, c = idx - r * CHV;                              \
     pv[u] = make_uint4(0, 0, 0, 0);                                                               \
-    if ((key0_) + r < p.t) pv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)((key0_) + r) * rowstride + c * 16); \
+    if ((key0_) + r < kend) pv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)((key0_) + r) * rowstride + c * 16); \
   }
 #define ATT_STAGE_TILE(boff_)                                                                     \
   _Pragma("unroll") for (int u = 0; u < NCH; ++u) {                                               \
@@ -183,14 +227,14 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
 #define ATT_DMA_K(key0_)                                                                         \
   _Pragma("unroll") for (int i = 0; i < 16; ++i) {                                                \
     const int r = wid * 16 + i;                                                                   \
-    const char* src = ((key0_) + r < p.t) ? base + (size_t)((key0_) + r) * rowstride + (size_t)C * ES + lane * 16 : zsrc; \
+    const char* src = ((key0_) + r < kend) ? base + (size_t)((key0_) + r) * rowstride + (size_t)C * ES + lane * 16 : zsrc; \
     att_glds16(src, __builtin_amdgcn_readfirstlane(lds_k + r * ROWB));                            \
   }
 #define ATT_DMA_V(key0_)                                                                         \
   if (lane < 32) {                                                                                \
     _Pragma("unroll") for (int i = 0; i < 16; ++i) {                                              \
       const int r = wid * 16 + i;                                                                 \
-      const char* src = ((key0_) + r < p.t) ? vbase + (size_t)((key0_) + r) * rowstride + lane * 16 : zsrc; \
+      const char* src = ((key0_) + r < kend) ? vbase + (size_t)((key0_) + r) * rowstride + lane * 16 : zsrc; \
       att_glds16(src, __builtin_amdgcn_readfirstlane(lds_v + r * VROWB));                         \
     }                                                                                             \
   }
@@ -222,7 +266,7 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
         for (int u = 0; u < 4; ++u) {
           const int idx = tid + 256 * (u0 + u), r = idx / CH, c = idx - r * CH;
           tk[u] = make_uint4(0, 0, 0, 0);
-          if (key0 + r < p.t) tk[u] = *reinterpret_cast<const uint4*>(base + (size_t)(key0 + r) * rowstride + c * 16 + (size_t)C * ES);
+          if (key0 + r < kend) tk[u] = *reinterpret_cast<const uint4*>(base + (size_t)(key0 + r) * rowstride + c * 16 + (size_t)C * ES);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -237,7 +281,7 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
         for (int u = 0; u < 4; ++u) {
           const int idx = tid + 256 * (u0 + u), r = idx / CHV, c = idx - r * CHV;
           tv[u] = make_uint4(0, 0, 0, 0);
-          if (key0 + r < p.t) tv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)(key0 + r) * rowstride + c * 16);
+          if (key0 + r < kend) tv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)(key0 + r) * rowstride + c * 16);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -293,28 +337,24 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
     uint4 pb[QT][2];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-      if (key0 + 64 > p.t) {                         // only the last tile of a ragged sequence needs the mask
+      // the mask is a select to -inf on the f32 scores: exp2(-inf) = 0 exactly, so a key past the end (MASK: a disallowed key) adds 0 * v to
+      // the numerator and 0 to the denominator.  Wave-uniform test: only the last tile of a ragged sequence pays for it; MASK: the tile that
+      // holds kend and (causal) the one that reaches past the wave's first query -- the diagonal tile, the last one this block walks
+      bool edge = key0 + 64 > kend;
+      if constexpr (MASK) edge = edge || (p.causal && key0 + 63 > q0);
+      if (edge) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (key0 + j * 16 + lg * 4 + r >= p.t) sacc[qt][j][r] = -INFINITY;
+            if (key0 + j * 16 + lg * 4 + r >= lim) sacc[qt][j][r] = -INFINITY;
       }
-      // raw v_max3_f32 / v_max_f32: fmaxf() makes hipcc canonicalise every operand first (IEEE sNaN quieting, one extra v_max per
-      // value: 46 vector instructions per key tile instead of 20 in a loop that is vector-issue bound); no NaN can occur here
-      float tmax = vmax3(sacc[qt][0][0], sacc[qt][0][1], sacc[qt][0][2]);
-      tmax = vmax3(tmax, sacc[qt][0][3], sacc[qt][1][0]);
-      tmax = vmax3(tmax, sacc[qt][1][1], sacc[qt][1][2]);
-      tmax = vmax3(tmax, sacc[qt][1][3], sacc[qt][2][0]);
-      tmax = vmax3(tmax, sacc[qt][2][1], sacc[qt][2][2]);
-      tmax = vmax3(tmax, sacc[qt][2][3], sacc[qt][3][0]);
-      tmax = vmax3(tmax, sacc[qt][3][1], sacc[qt][3][2]);
-      tmax = vmax2(tmax, sacc[qt][3][3]);
+      float tmax = att_max16(sacc[qt]);
       {   // the other three lane groups' maxima in ONE crossbar round trip (three independent permutes) instead of two dependent ones
         const float t16 = __shfl_xor(tmax, 16, 64), t32 = __shfl_xor(tmax, 32, 64), t48 = __shfl_xor(tmax, 48, 64);
         tmax = vmax2(vmax3(tmax, t16, t32), t48);
       }
-      const float m_new = vmax2(m_run[qt], tmax);    // finite: every tile has >= 1 valid key
+      const float m_new = vmax2(m_run[qt], tmax);    // finite: every tile has >= 1 valid key (MASK: key key0 of every walked tile is visible to every query of the block)
       const float alpha = __builtin_amdgcn_exp2f((m_run[qt] - m_new) * sc2);
       const float mb = m_new * sc2;
 #pragma unroll
@@ -345,7 +385,6 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
     // ---- O^T += V^T . P^T ; a V^T fragment feeds every query tile
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      // transposed read: lane 4q'+p' of each 16-lane group addresses row q', columns 4p'..4p'+3 of a 4x16 block
       const int rq = (lane & 15) >> 2, rp = lane & 3;
       const char* va = sV + boff + (32 * kk + 4 * lg + rq) * VROWB + rp * 8;
 #pragma unroll
@@ -357,12 +396,7 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
         for (int dt0 = 0; dt0 < DT; dt0 += 4) {
           uint4 av[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(va + (dt0 + u) * 32));
-            const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vb + (dt0 + u) * 32));
-            const uint2 lo2 = __builtin_bit_cast(uint2, lo), hi2 = __builtin_bit_cast(uint2, hi);
-            av[u] = make_uint4(lo2.x, lo2.y, hi2.x, hi2.y);
-          }
+          for (int u = 0; u < 4; ++u) av[u] = att_vt_frag(va + (dt0 + u) * 32, vb + (dt0 + u) * 32);
 #pragma unroll
           for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -371,11 +405,7 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
       } else {
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(va + dt * 32));
-        const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vb + dt * 32));
-        // the two transposed 8-byte reads ARE the operand's four dwords (element-wise repacking compiled to 16 shift/or ops)
-        const uint2 lo2 = __builtin_bit_cast(uint2, lo), hi2 = __builtin_bit_cast(uint2, hi);
-        const uint4 av = make_uint4(lo2.x, lo2.y, hi2.x, hi2.y);
+        const uint4 av = att_vt_frag(va + dt * 32, vb + dt * 32);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) o[qt][dt] = AttMma<T>::run(av, pb[qt][kk], o[qt][dt]);
       }
@@ -572,14 +602,7 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const AttP p) {
           for (int r = 0; r < 4; ++r)
             if (key0 + j * 16 + lg * 4 + r >= p.t) sacc[qt][j][r] = -INFINITY;
       }
-      float tmax = vmax3(sacc[qt][0][0], sacc[qt][0][1], sacc[qt][0][2]);
-      tmax = vmax3(tmax, sacc[qt][0][3], sacc[qt][1][0]);
-      tmax = vmax3(tmax, sacc[qt][1][1], sacc[qt][1][2]);
-      tmax = vmax3(tmax, sacc[qt][1][3], sacc[qt][2][0]);
-      tmax = vmax3(tmax, sacc[qt][2][1], sacc[qt][2][2]);
-      tmax = vmax3(tmax, sacc[qt][2][3], sacc[qt][3][0]);
-      tmax = vmax3(tmax, sacc[qt][3][1], sacc[qt][3][2]);
-      tmx[qt] = vmax2(tmax, sacc[qt][3][3]);
+      tmx[qt] = att_max16(sacc[qt]);
     }
     if constexpr (SM2) {
 #pragma unroll
@@ -794,186 +817,8 @@ __global__ __launch_bounds__(256) void attention32_kernel(const AttP p) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Masked self-attention (dts_attention_masked; head dim 64, 16-bit types): CLIP's text transformer (transformers modeling_clip.py,
-// CLIPTextTransformer: a causal mask, plus the tokenizer's attention_mask for the text encoders that use it).  Query i of sample b sees key
-// j iff (!causal || j <= i) && j < kend, kend = min(t, key_len[b]).  A kernel of its own beside attention16_kernel<T, 64, 1> -- one block
-// = 4 waves = 64 queries, key tiles of 64 through the register prefetch, the same fragments, LDS rows and arithmetic (f32 scores, exp2
-// with the scale in the fused multiply-add, P rounded to T, the denominator from the rounded P on the matrix core, one final rounding) --
-// so that the unmasked instantiations stay what they are.  What differs:
-//   * a block walks only the key tiles that hold a key some query of it may see: tiles below min(kend, end of the query block).  A tile
-//     wholly above the diagonal or wholly past kend is never staged -- with every score -inf and the running maximum still -inf the
-//     exponent would be -inf - (-inf) = NaN.  Every tile that IS walked starts at a key key0 <= the block's first query and key0 < kend,
-//     so every query has a finite score in every tile it meets and the running maximum is finite from tile 0 on.
-//   * the mask is a select to -inf on the f32 scores (where attention16_kernel masks the tail past t): exp2(-inf) = 0 exactly, so a
-//     disallowed key adds 0 * v to the numerator and 0 to the denominator -- nothing of it reaches the output as long as v is finite.
-//     Only the diagonal tile (causal) and the tile that holds kend pay for it.
-//   * key rows from kend on are staged as zeros, not read.
-struct AttMaskP {
-  const char* qkv; char* out;
-  const int32_t* key_len;        // [n] on the device, or null
-  int n, t, heads;
-  float scale_log2e;
-  int qblocks, xcd_remap, causal;
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void attention_masked_kernel(const AttMaskP p) {
-  constexpr int D = 64, ES = 2, ROWB = D * ES + 32, CH = D / 8, KSTEPS = D / 32, DT = D / 16, NCH = (64 * CH) / 256;
-  __shared__ __attribute__((aligned(16))) char smem[2 * 64 * ROWB];
-  char* sK = smem;
-  char* sV = smem + 64 * ROWB;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int lq = lane & 15, lg = lane >> 4;
-  int bid = blockIdx.x;                              // att_block()'s order: the query blocks of a (sample, head) share an XCD
-  if (p.xcd_remap) {
-    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, j = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
-  const int nh = bid / p.qblocks, qblk = bid - nh * p.qblocks;
-  const int n = nh / p.heads, head = nh - n * p.heads;
-  const int C = p.heads * D;
-  const size_t rowstride = (size_t)3 * C * ES;
-  const char* base = p.qkv + (size_t)n * p.t * rowstride + (size_t)head * D * ES;
-  const char* const vbase = base + (size_t)2 * C * ES;
-  const int q0 = qblk * 64 + wid * 16;
-  const int qrow = q0 + lq;
-  int kend = p.t;                                    // keys of this sample: the caller vouches for 1 <= key_len <= t, clamped for memory safety only
-  if (p.key_len) kend = min(p.t, max(1, p.key_len[n]));
-  const int kblk = p.causal ? min(kend, qblk * 64 + 64) : kend;       // keys some query of this block may see
-  const int ntiles = (kblk + 63) / 64;
-  const int lim = p.causal ? min(kend, qrow + 1) : kend;              // this lane's query sees keys < lim (>= 1)
-
-  uint4 qf[KSTEPS];
-#pragma unroll
-  for (int s = 0; s < KSTEPS; ++s) {
-    qf[s] = make_uint4(0, 0, 0, 0);
-    if (qrow < p.t) qf[s] = *reinterpret_cast<const uint4*>(base + (size_t)qrow * rowstride + (lg + 4 * s) * 16);
-  }
-  const float sc2 = p.scale_log2e;
-  f32x4_t o[DT], ol = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  const uint4 ones = make_uint4(AttMma<T>::ONES2, AttMma<T>::ONES2, AttMma<T>::ONES2, AttMma<T>::ONES2);
-  float m_run = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < DT; ++i) o[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  uint4 pk[NCH], pv[NCH];
-#define ATTM_LOAD_TILE(key0_)                                                                     \
-  _Pragma("unroll") for (int u = 0; u < NCH; ++u) {                                               \
-    const int idx = tid + 256 * u, r = idx / CH, c = idx - r * CH;                                \
-    pk[u] = pv[u] = make_uint4(0, 0, 0, 0);                                                       \
-    if ((key0_) + r < kend) {                                                                     \
-      pk[u] = *reinterpret_cast<const uint4*>(base + (size_t)((key0_) + r) * rowstride + c * 16 + (size_t)C * ES); \
-      pv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)((key0_) + r) * rowstride + c * 16); \
-    }                                                                                             \
-  }
-  ATTM_LOAD_TILE(0);
-  for (int kt = 0; kt < ntiles; ++kt) {              // ntiles is the same for the four waves: the barriers are block-uniform
-    const int key0 = kt * 64;
-    __syncthreads();                                 // the previous tile is consumed
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const int idx = tid + 256 * u, r = idx / CH, c = idx - r * CH;
-      *reinterpret_cast<uint4*>(sK + r * ROWB + c * 16) = pk[u];
-      *reinterpret_cast<uint4*>(sV + r * ROWB + c * 16) = pv[u];
-    }
-    __syncthreads();
-    if (kt + 1 < ntiles) { ATTM_LOAD_TILE(key0 + 64); }
-
-    // ---- S^T tiles: 4 x (16 keys x 16 queries)
-    f32x4_t sacc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      sacc[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < KSTEPS; ++s) {
-        const uint4 ka = *reinterpret_cast<const uint4*>(sK + (j * 16 + lq) * ROWB + (lg + 4 * s) * 16);
-        sacc[j] = AttMma<T>::run(ka, qf[s], sacc[j]);
-      }
-    }
-    // ---- the mask: lane holds keys key0 + j*16 + lg*4 + r of query lq.  Wave-uniform test: the tile reaches past kend, or (causal) past
-    // the wave's first query -- the diagonal tile, the last one this block walks
-    if (key0 + 64 > kend || (p.causal && key0 + 63 > q0)) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (key0 + j * 16 + lg * 4 + r >= lim) sacc[j][r] = -INFINITY;
-    }
-    // ---- online softmax (attention16_kernel's)
-    float tmax = vmax3(sacc[0][0], sacc[0][1], sacc[0][2]);
-    tmax = vmax3(tmax, sacc[0][3], sacc[1][0]);
-    tmax = vmax3(tmax, sacc[1][1], sacc[1][2]);
-    tmax = vmax3(tmax, sacc[1][3], sacc[2][0]);
-    tmax = vmax3(tmax, sacc[2][1], sacc[2][2]);
-    tmax = vmax3(tmax, sacc[2][3], sacc[3][0]);
-    tmax = vmax3(tmax, sacc[3][1], sacc[3][2]);
-    tmax = vmax2(tmax, sacc[3][3]);
-    {
-      const float t16 = __shfl_xor(tmax, 16, 64), t32 = __shfl_xor(tmax, 32, 64), t48 = __shfl_xor(tmax, 48, 64);
-      tmax = vmax2(vmax3(tmax, t16, t32), t48);
-    }
-    const float m_new = vmax2(m_run, tmax);          // finite: key key0 of every walked tile is visible to every query of the block
-    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sc2);
-    const float mb = m_new * sc2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sacc[j][r] = __builtin_amdgcn_exp2f(fmaf(sacc[j][r], sc2, -mb));       // masked: exp2(-inf) = 0
-    m_run = m_new;
-    if (!__all(alpha == 1.0f)) {
-#pragma unroll
-      for (int i = 0; i < DT; ++i) o[i] *= alpha;
-      ol[0] *= alpha;
-    }
-    uint4 pb[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      pb[kk].x = AttMma<T>::pack2(sacc[2 * kk][0], sacc[2 * kk][1]);
-      pb[kk].y = AttMma<T>::pack2(sacc[2 * kk][2], sacc[2 * kk][3]);
-      pb[kk].z = AttMma<T>::pack2(sacc[2 * kk + 1][0], sacc[2 * kk + 1][1]);
-      pb[kk].w = AttMma<T>::pack2(sacc[2 * kk + 1][2], sacc[2 * kk + 1][3]);
-    }
-    // ---- O^T += V^T . P^T, l += ones . P^T
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int rq = (lane & 15) >> 2, rp = lane & 3;
-      const char* va = sV + (32 * kk + 4 * lg + rq) * ROWB + rp * 8;
-      const char* vb = va + 16 * ROWB;
-      ol = AttMma<T>::run(ones, pb[kk], ol);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(va + dt * 32));
-        const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vb + dt * 32));
-        const uint2 lo2 = __builtin_bit_cast(uint2, lo), hi2 = __builtin_bit_cast(uint2, hi);
-        o[dt] = AttMma<T>::run(make_uint4(lo2.x, lo2.y, hi2.x, hi2.y), pb[kk], o[dt]);
-      }
-    }
-  }
-#undef ATTM_LOAD_TILE
-  if (qrow < p.t) {
-    const float inv = 1.f / ol[0];
-    T* orow = reinterpret_cast<T*>(p.out) + ((size_t)n * p.t + qrow) * C + head * D;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) st1<T>(orow + dt * 16 + lg * 4 + r, o[dt][r] * inv);
-  }
-}
-
-template <typename T>
-int att_masked(AttMaskP p, hipStream_t st) {
-  p.qblocks = (p.t + 63) / 64;
-  p.xcd_remap = dts_knob_get(DTS_KNOB_ATT_XCD) != 0;
-  const long long nblk = (long long)p.qblocks * p.n * p.heads;
-  DTS_CHECK_ARG(nblk < (1ll << 31), "dts_attention_masked: grid too large");
-  hipLaunchKernelGGL(attention_masked_kernel<T>, dim3((unsigned)nblk), dim3(256), 0, st, p);
-  DTS_CHECK_LAUNCH("dts_attention_masked");
-  return DTS_OK;
-}
-
 template <typename K>
-int launch_att(K kernel, const AttP& p0, size_t lds, hipStream_t st, int qblock = 64, int slices = 1) {
+int launch_att(K kernel, const AttP& p0, size_t lds, hipStream_t st, int qblock = 64, int slices = 1, const char* who = "dts_attention") {
   {   // hipFuncSetAttribute once per (device, kernel): the attribute is per device, and every instantiation has the same pointer
       // TYPE, so the key is (device, pointer value)
     static std::mutex mu;
@@ -991,9 +836,9 @@ int launch_att(K kernel, const AttP& p0, size_t lds, hipStream_t st, int qblock 
   p.qblocks = (p.t + qblock - 1) / qblock;
   p.xcd_remap = dts_knob_get(DTS_KNOB_ATT_XCD) != 0;        // DTS_ATT_XCD=0 restores the plain block order (A/B aid)
   const long long nblk = (long long)p.qblocks * p.n * p.heads * slices;
-  DTS_CHECK_ARG(nblk < (1ll << 31), "dts_attention: grid too large");
+  DTS_CHECK_ARG(nblk < (1ll << 31), "%s: grid too large", who);
   hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), lds, st, p);
-  DTS_CHECK_LAUNCH("dts_attention");
+  DTS_CHECK_LAUNCH(who);
   return DTS_OK;
 }
 
@@ -1068,8 +913,10 @@ extern "C" int dts_attention_masked(const void* qkv, void* out, int dtype, int n
     dts_set_error("dts_attention_masked: head dim %d unsupported (64, the head dim of every CLIP text width)", d);
     return DTS_ERR_UNSUPPORTED;
   }
-  AttMaskP p{(const char*)qkv, (char*)out, key_len, n, t, heads, scale * 1.4426950408889634f, 0, 1, causal ? 1 : 0};
-  return dtype == DTS_BF16 ? att_masked<bf16_t>(p, to_stream(s)) : att_masked<f16_t>(p, to_stream(s));
+  AttP p{(const char*)qkv, (char*)out, n, t, heads, d, scale * 1.4426950408889634f, 0, 1, 0, key_len, causal ? 1 : 0};
+  const size_t lds = (size_t)2 * 64 * (64 * 2 + 32);
+  return dtype == DTS_BF16 ? launch_att(attention16_kernel<bf16_t, 64, 1, 64, true, false, false, true>, p, lds, to_stream(s), 64, 1, "dts_attention_masked")
+                           : launch_att(attention16_kernel<f16_t, 64, 1, 64, true, false, false, true>, p, lds, to_stream(s), 64, 1, "dts_attention_masked");
 }
 
 extern "C" int dts_attention(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, dts_stream s) {

@@ -13,6 +13,7 @@ CPU that these inputs are fair and that the bound catches a tail-mask, a rescale
   128+DB         attention16_kernel<T, 128, 1, 128, true, true>            att_db=1, t > 64
   512/DMA        attention16_kernel<T, 512, 1, 256, false, false, true>    head dim (LDS-DMA staging, hand-counted vmcnt)
   512/REG        attention16_kernel<T, 512, 1, 256, false>                 att_db=2 (register staging)
+  64/MASK        attention16_kernel<T, 64, 1, 64, true, false, false, true> dts_attention_masked, causal = 0 and no key_len: plain attention
   f32/64|128|256 attention32_kernel<D>                                     float32 input
   x3/QT1, x3/QT2 attention_x3_kernel<1 | 2, 7>                             dts_split2_f16 + dts_attention_x3, att_qt=1 | 2
   .../VAR0       attention_x3_kernel<1 | 2, 0>                             att_db=16
@@ -28,7 +29,8 @@ measure of the reference's own float32 arithmetic (oracle.edm_nets.attention_wei
 head.  Every case prints its ratio err / max(e_ref32, FLOOR), which the bound holds below K.
 Measured on the MI355X (worst ratio over every sequence length; the 16-bit figures are err / bound, limit 1):
   16-bit forms          bfloat16: sharp 0.48 - 0.53, other classes 0.28 - 0.40; float16: sharp 0.41 - 0.47, other classes 0.26 - 0.42,
-                        the same for the double-buffered, register-staged and two-query-tile forms as for their plain twins (float16
+                        the same for the double-buffered, register-staged and two-query-tile forms as for their plain twins, and for
+                        64/MASK, whose outputs are 64/QT1's bit for bit (float16
                         `sharp` stays at the emulation's "subnormals kept" figure: the matrix cores did not flush P here)
   f32/64                1.93 (sharp 1.48)          f32/128    2.49 (sharp 1.87)
   f32/256               2.70 outside sharp; sharp: 10.63 (t = 15), 5.27 (17), 3.28 (64), 3.72 (65), 3.23 (129), 2.39 (200)
@@ -72,6 +74,7 @@ FORMS16 = {
     '256': (256, 2, {}, ONE_T),
     '512/DMA': (512, 1, {}, T512),
     '512/REG': (512, 1, dict(att_db=2), T512),
+    '64/MASK': (64, 2, {}, ONE_T),
 }
 FORMS32 = {
     'f32/64': (64, 2, {}, ONE_T),
@@ -152,6 +155,11 @@ def launch(ops, form, x, heads, out=None, image=None):
             out = torch.empty((n, t, c), dtype=torch.float32, device=DEV)
         ops._call('dts_attention_x3', image.data_ptr(), out.data_ptr(), 0, n, t, heads, d, scale)
         return out
+    if form == '64/MASK':
+        if out is None:
+            return ops.attention_masked(x, heads, scale, causal=False)
+        ops._call('dts_attention_masked', x.data_ptr(), out.data_ptr(), ops.dt_code(x.dtype), n, t, heads, d, scale, 0, None)
+        return out
     if out is None:
         return ops.attention(x, heads, scale)
     ops._call('dts_attention', x.data_ptr(), out.data_ptr(), ops.dt_code(x.dtype), n, t, heads, d, scale)
@@ -208,6 +216,18 @@ def test_launcher_takes_two_query_tiles_on_a_large_grid(ops, dtype):
             same = torch.equal(got, ops.attention(x.to(DEV), heads, 0.125))
         print(f'attention 64/QT2 by the launcher\'s rule {DTN[dtype]} n={n} heads={heads} t={t} {kind}: err/bound {r:.3f}, bit-identical to att_qt=2: {same}')
         assert bool(torch.isfinite(got).all()) and r <= 1.0 and same
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=case_id)
+def test_masked_form_without_a_mask_is_the_plain_form_bit_for_bit(ops, dtype):
+    """64/MASK against 64/QT1: the same sequence of MFMA, exp2 and FMA per accumulator, and with kend = t and causal = 0 the select
+    conditions coincide -- so the outputs are equal, not merely close"""
+    d, heads = FORMS['64/MASK'][:2]
+    for t in (64, 65, 200):
+        x = case_input('64/MASK', dtype, 'randn', t).to(DEV)
+        with knobs(att_qt=1):
+            plain = launch(ops, '64/QT1', x, heads)
+        assert torch.equal(launch(ops, '64/MASK', x, heads), plain), t
 
 
 @pytest.mark.parametrize('qt,t', [(1, 128), (1, 200), (2, 256), (2, 300), (2, 145)])

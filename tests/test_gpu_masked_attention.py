@@ -1,4 +1,4 @@
-"""GPU: dts_attention_masked (csrc/attention.hip, attention_masked_kernel) against the float64 masked reference of
+"""GPU: dts_attention_masked (csrc/attention.hip, attention16_kernel<T, 64, 1, 64, true, false, false, true>) against the float64 masked reference of
 tests/masked_attention_reference.py, per element within attention_reference.bound16 as it stands (its input conditions stay asserted
 inside it), on every input class of attention_reference.KINDS, in both 16-bit types, n = 2, heads = 2, d = 64.
 
