@@ -54,6 +54,11 @@ SIGNATURES = {
     'dts_text_tokens': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'dts_gelu': [_p, _p, _i, _i64, _i, _p],
     'dts_vit_head': [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p],
+    'dts_layer_norm_x3': [_p, _p, _p, _i64, _i, _f, _p, _p, _p],
+    'dts_gelu_x3': [_p, _p, _i64, _i, _i, _p],
+    'dts_patchify_x3': [_p, _p, _i, _i, _i, _i, _p],
+    'dts_vit_tokens_f32': [_p, _p, _p, _p, _i, _i, _i, _p],
+    'dts_vit_head_f32': [_p, _p, _i, _i, _i, _f, _p, _p, _p],
     'dts_linear': [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     'dts_pos_embedding': [_p, _p, _p, _i, _i, _i, _p],
     'dts_edm_precond_in': [_p, _p, _i, _f, _p, _p, _i, _i, _p],
@@ -85,7 +90,7 @@ OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 117              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 118              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

@@ -11,8 +11,15 @@ Every decoded candidate of a search passes through these 24 layers at 257 tokens
   out_proj, fc2                              -> 1x1 dts_conv2d with the bias and the residual add in the epilogue
   fc1 + activation                           -> 1x1 dts_conv2d + dts_gelu (quick-GELU or erf GELU, in place)
   post_layernorm(token 0), visual_projection -> dts_vit_head + dts_linear (f32)
-Activations are [n, tokens, 1, channels] in `dtype` (float16 or bfloat16): this is a 16-bit THROUGHPUT mode of the scorer.  The reference
-scores in float32; there is no float32 or split-precision form of this tower (full-precision CLIP stays the transformers module).
+Activations are [n, tokens, 1, channels] in `dtype`.  float16 / bfloat16: a 16-bit THROUGHPUT mode of the scorer (the reference scores in
+float32).  CLIPVisionTowerX3 (dtype ops.F16X3, 'f16x3'): the PARITY-GRADE mode -- float32 activations, every matrix product in split precision on the 16-bit matrix
+cores (dts_conv2d in DTS_F16X3; dts_attention_x3 at head dim 64 and >= 128 tokens, the float32 dts_attention otherwise), and between them
+the float32 twins of the kernels above, which write the next product's operand image themselves:
+  patch rows -> dts_patchify_x3; tokens -> dts_vit_tokens_f32; pre_layrnorm, layer_norm1 / 2 -> dts_layer_norm_x3; activation -> dts_gelu_x3;
+  head -> dts_vit_head_f32 + dts_linear
+It is held to the float32 module's own distance from float64 (tests/test_gpu_clip_vision_x3.py).  torch.float32 itself is refused: there is
+no float32 matrix-instruction form of this tower.  CLIPVisionTower itself keeps refusing every dtype but the two 16-bit ones, 'f16x3'
+included: the split-precision mode is a class of its own, as its kernels are entry points of their own.
 
 Parameters: a state dict with transformers' key names (`vision_model.*`, `visual_projection.weight`).  Shapes the kernels do not take are
 refused by name at construction (check_config).  The forward makes no device-to-host synchronisation and no data-dependent step.
@@ -31,10 +38,12 @@ CONFIG_DEFAULTS = {'hidden_size': 768, 'intermediate_size': 3072, 'num_hidden_la
                    'patch_size': 32, 'hidden_act': 'quick_gelu', 'layer_norm_eps': 1e-5, 'projection_dim': 512}
 
 
-def check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim=None):
-    """Raises ValueError naming every setting of a CLIP vision configuration that this build's kernels do not take, with its value."""
+def check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim=None,
+                 split_precision=False):
+    """Raises ValueError naming every setting of a CLIP vision configuration that this build's kernels do not take, with its value.
+    split_precision: the check of CLIPVisionTowerX3, whose only dtype is ops.F16X3 (CLIPVisionTower's are float16 and bfloat16)."""
     bad = blocks.clip_config_errors(dtype, hidden_size, num_attention_heads, intermediate_size, hidden_act, projection_dim,
-                                    (64, 128, 256), 'one of dts_attention\'s 64 / 128 / 256')
+                                    (64, 128, 256), 'one of dts_attention\'s 64 / 128 / 256', split_precision=split_precision)
     if patch_size <= 0 or image_size <= 0 or image_size % patch_size:
         bad.append(f'image_size={image_size} is not a multiple of patch_size={patch_size}')
     if bad:
@@ -68,13 +77,18 @@ def read_vision_tensors(path):
 
 
 class CLIPVisionTower:
+    """dtype torch.float16 / torch.bfloat16: the 16-bit THROUGHPUT modes (the default, float16, is what the scorer's vision_tower='hip' has
+    always run).  The PARITY-GRADE mode is CLIPVisionTowerX3 below."""
+    SPLIT_PRECISION, DEFAULT_DTYPE = False, torch.float16
+
     def __init__(self, state_dict, hidden_size=1024, num_attention_heads=16, intermediate_size=4096, num_hidden_layers=24, image_size=224,
                  patch_size=14, hidden_act='quick_gelu', layer_norm_eps=1e-5, projection_dim=None, device='cuda', dtype=torch.float16):
         """The defaults are ViT-L/14's (openai/clip-vit-large-patch14, the reference's scorer).  projection_dim None: taken from
         visual_projection.weight."""
-        check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim)
+        check_config(hidden_size, num_attention_heads, intermediate_size, image_size, patch_size, hidden_act, dtype, projection_dim,
+                     split_precision=self.SPLIT_PRECISION)
         blocks.require_gpu('CLIPVisionTower')
-        self.device, self.dtype = torch.device(device), dtype
+        self.device, self.dtype, self.x3 = torch.device(device), dtype, self.SPLIT_PRECISION
         self.hidden, self.heads, self.inter, self.layers_n = int(hidden_size), int(num_attention_heads), int(intermediate_size), int(num_hidden_layers)
         self.image_size, self.patch, self.act, self.eps = int(image_size), int(patch_size), hidden_act, float(layer_norm_eps)
         self.grid = self.image_size // self.patch
@@ -89,9 +103,10 @@ class CLIPVisionTower:
         self._load(state_dict)
 
     @classmethod
-    def from_clip_model(cls, model, dtype=torch.float16, device='cuda'):
+    def from_clip_model(cls, model, dtype=None, device='cuda'):
         """From a `transformers.CLIPModel` or `CLIPVisionModelWithProjection`: only its state dict and configuration are read, no reference
-        to the module is kept."""
+        to the module is kept.  dtype None: the class's default (float16; f16x3 for CLIPVisionTowerX3)."""
+        dtype = cls.DEFAULT_DTYPE if dtype is None else dtype
         vc = getattr(model.config, 'vision_config', None) or model.config
         sd = {k: v for k, v in model.state_dict().items() if k.startswith(PREFIX) or k == PROJECTION}
         return cls(sd, hidden_size=vc.hidden_size, num_attention_heads=vc.num_attention_heads, intermediate_size=vc.intermediate_size,
@@ -99,8 +114,9 @@ class CLIPVisionTower:
                    layer_norm_eps=vc.layer_norm_eps, device=device, dtype=dtype)
 
     @classmethod
-    def from_pretrained(cls, path, dtype=torch.float16, device='cuda'):
+    def from_pretrained(cls, path, dtype=None, device='cuda'):
         """Reads a local directory of `config.json` + `model.safetensors` (read_vision_tensors: the vision tensors only)."""
+        dtype = cls.DEFAULT_DTYPE if dtype is None else dtype
         cfg, sd = read_vision_tensors(path)
         cfg.pop('projection_dim')                     # the tensor's own shape decides
         return cls(sd, device=device, dtype=dtype, **cfg)
@@ -147,12 +163,25 @@ class CLIPVisionTower:
             raise ValueError(f'CLIPVisionTower: pixel_values {tuple(pixel_values.shape)} is not [n, 3, {S}, {S}]')
         n = pixel_values.shape[0]
         x = pixel_values.to(self.device, torch.float32).contiguous()
+        if self.x3:
+            return self._forward_x3(x, n)
         rows = ops.patchify(x, self.patch, self.dtype, self.kpad)                                  # [n, g*g, kpad]
         emb = ops.conv2d(rows.view(n, g, g, self.kpad), self.w_patch)                              # the patch embedding has no bias
         h = ops.vit_tokens(emb.view(n, g * g, C), self.cls, self.pos)
         h = ops.layer_norm(h, *self.pre_ln, eps=self.eps).view(n, T, 1, C)
         h = blocks.clip_encoder(h, self.layers, self.eps, self.act, lambda qkv: ops.attention(qkv, self.heads, self.scale))
         pooled = ops.vit_head(h.view(n, T, C), *self.post_ln, eps=self.eps)                        # f32 [n, C]: the class token only
+        self.rows += n
+        return ops.linear(pooled, self.w_proj)
+
+    def _forward_x3(self, x, n):
+        """the same forward in the split-precision mode: float32 activations, X3Weight matrix products (ops.F16X3)"""
+        C, T, g = self.hidden, self.tokens, self.grid
+        emb = ops.conv2d(ops.patchify_x3(x, self.patch, self.kpad), self.w_patch)                  # f32 [n, g, g, C]
+        h = ops.vit_tokens_f32(emb.view(n, g * g, C), self.cls, self.pos)
+        h = ops.layer_norm_x3(h, *self.pre_ln, eps=self.eps, want_f32=True, want_split=False).view(n, T, 1, C)     # the residual stream
+        h = blocks.clip_encoder_x3(h, self.layers, self.eps, self.act, self.heads, self.scale)
+        pooled = ops.vit_head_f32(h.view(n, T, C), *self.post_ln, eps=self.eps)
         self.rows += n
         return ops.linear(pooled, self.w_proj)
 
@@ -164,3 +193,13 @@ class CLIPVisionTower:
         C, I, T, L = self.hidden, self.inter, self.tokens, self.layers_n
         per_layer = 2 * T * C * 3 * C + 2 * T * C * C + 2 * 2 * T * T * C + 2 * 2 * T * C * I
         return n * (2 * (T - 1) * 3 * self.patch * self.patch * C + L * per_layer + 2 * C * self.proj_dim)
+
+
+class CLIPVisionTowerX3(CLIPVisionTower):
+    """The parity-grade form of the tower: float32 activations, every matrix product in split precision (dtype ops.F16X3, its only dtype),
+    held to a small factor of the float32 transformers module's own rounding error against float64 -- use it where the scorer's
+    selections must match the reference's.  Same constructor, state dict, from_clip_model / from_pretrained and flops() as CLIPVisionTower."""
+    SPLIT_PRECISION, DEFAULT_DTYPE = True, ops.F16X3
+
+    def __init__(self, state_dict, *args, dtype=ops.F16X3, **kw):
+        super().__init__(state_dict, *args, dtype=dtype, **kw)

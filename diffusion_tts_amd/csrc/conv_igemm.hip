@@ -189,8 +189,9 @@ __device__ unsigned long long g_seg[4096 * 2 * 8];
 #define DTS_SEG_STORE
 #endif
 
-__device__ uint4 g_zero16[1024];   // 16 KiB of zeros: source of padded (out-of-image) rows; a row pointer into it is advanced
-                                   // along K like a real one (cin * element size <= 15 KiB: 3 x 1536 channels of the split-precision mode included), so no per-step select is needed
+__device__ uint4 g_zero16[2048];   // 32 KiB of zeros: source of padded (out-of-image) rows; a row pointer into it is advanced
+                                   // along K like a real one (cin * element size <= 32 KiB - 128: the 2 x 4096 f16 of the split-precision image of a ViT-L/14 fc2 operand
+                                   // included, 16 KiB + 128 B, which the former 16 KiB page refused), so no per-step select is needed
 
 // LDS-DMA through inline asm: hipcc does not count an asm memory op in its s_waitcnt bookkeeping, so it does not
 // drain the in-flight tile in front of the (non-aliasing) ds_reads of the other buffer, as it does for the builtin.

@@ -308,6 +308,15 @@ def split3_f16(x1, x2=None):
     return out
 
 
+def split2_f16(x):
+    """float32 [..., c] -> float16 [..., 2*c]: hi(c) | lo(c) of x * 2^6 per row (dts_split2_f16: the operand image of dts_attention_x3, what
+    conv2d(..., out_split2=True) writes from its epilogue)"""
+    c = x.shape[-1]
+    out = torch.empty(tuple(x.shape[:-1]) + (2 * c,), dtype=torch.float16, device=x.device)
+    _call('dts_split2_f16', _ptr(x, 'x', torch.float32), c, _ptr(out), x.numel() // c)
+    return out
+
+
 def conv_in3(x, w, bias, cout, dtype):
     """x f32 NCHW [n,3,h,w]; w f32 OIHW [cout,3,3,3] -> NHWC [n,h,w,cout]."""
     n, c, h, wd = x.shape
@@ -678,6 +687,110 @@ def vit_head(tokens, gamma, beta, eps=1e-5):
     out = torch.empty((n, c), dtype=torch.float32, device=tokens.device)
     _call('dts_vit_head', _ptr(tokens, 'tokens'), _ptr(out), dt_code(tokens.dtype), n, t, c, float(eps), _ptr(gamma, 'gamma', torch.float32),
           _ptr(beta, 'beta', torch.float32))
+    return out
+
+
+# ---- CLIP vision tower, split-precision mode (F16X3) ------------------------------------------------
+# float32 activations; what only a split-precision 1x1 conv2d reads leaves as its operand image (SplitAct: split3_f16's bits).
+def _f32_gpu(t, who, name):
+    """host-side refusal, by name, before any launch: `t` must be a contiguous float32 GPU tensor"""
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise ValueError(f'{who}: {name} must be a float32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}')
+    return _ptr(t, name, torch.float32)
+
+
+def _norm_pair(who, gamma, beta, c):
+    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
+        raise ValueError(f'{who}: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} for {c} channels')
+    return _ptr(gamma, 'gamma', torch.float32), _ptr(beta, 'beta', torch.float32)
+
+
+def layer_norm_x3(x, gamma, beta, eps=1e-5, want_f32=False, want_split=True):
+    """LayerNorm over the last dimension of a contiguous float32 tensor [..., c] (dts_layer_norm_x3); gamma, beta float32 [c]; c a multiple of
+    32, at most 2048.  Returns the operand image of the normalised rows (SplitAct; a 3-D input [n, t, c] is taken as [n, t, 1, c]), or with
+    want_f32 the pair (float32 rows shaped like x, SplitAct), or with want_split=False the float32 rows alone.  The image is the split of the
+    float32 rows whether or not those are written."""
+    if not (want_f32 or want_split):
+        raise ValueError('layer_norm_x3: neither want_f32 nor want_split')
+    xp = _f32_gpu(x, 'layer_norm_x3', 'x')
+    if x.dim() not in (3, 4):
+        raise ValueError(f'layer_norm_x3: x {tuple(x.shape)} is not [n, t, c] or [n, h, w, c]')
+    c = x.shape[-1]
+    if c <= 0 or c % 32 or c > 2048:
+        raise ValueError(f'layer_norm_x3: {c} channels (a multiple of 32, at most 2048)')
+    gp, bp = _norm_pair('layer_norm_x3', gamma, beta, c)
+    lead = tuple(x.shape[:-1]) if x.dim() == 4 else tuple(x.shape[:2]) + (1,)
+    out = torch.empty_like(x) if want_f32 else None
+    img = torch.empty(lead + (2 * c,), dtype=torch.float16, device=x.device) if want_split else None
+    _call('dts_layer_norm_x3', xp, _ptr(out), _ptr(img), x.numel() // c, c, float(eps), gp, bp)
+    if not want_split:
+        return out
+    return (out, SplitAct(img, c)) if want_f32 else SplitAct(img, c)
+
+
+def gelu_x3(x, kind='quick_gelu'):
+    """act(x) of a contiguous float32 tensor [n, h, w, c] as the operand image of the convolution that follows (SplitAct; dts_gelu_x3); kind as
+    ops.gelu; c a multiple of 32."""
+    if kind not in GELU_KINDS:
+        raise ValueError(f'gelu_x3: kind {kind!r} (one of {sorted(GELU_KINDS)})')
+    xp = _f32_gpu(x, 'gelu_x3', 'x')
+    if x.dim() != 4:
+        raise ValueError(f'gelu_x3: x {tuple(x.shape)} is not [n, h, w, c]')
+    c = x.shape[-1]
+    if c <= 0 or c % 32:
+        raise ValueError(f'gelu_x3: {c} channels (a multiple of 32)')
+    img = torch.empty(tuple(x.shape[:-1]) + (2 * c,), dtype=torch.float16, device=x.device)
+    _call('dts_gelu_x3', xp, _ptr(img), x.numel() // c, c, GELU_KINDS[kind])
+    return SplitAct(img, c)
+
+
+def patchify_x3(x, patch, kpad=None):
+    """pixel_values float32 NCHW [n, 3, S, S] -> the operand image of the unrounded patch rows (SplitAct of logical shape [n, S/patch, S/patch,
+    kpad]; dts_patchify_x3): ops.patchify's column order, columns from 3*patch*patch on are zero.  kpad defaults to patch_kpad(patch) and must
+    be a multiple of 32 covering 3*patch*patch."""
+    xp = _f32_gpu(x, 'patchify_x3', 'x')
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError(f'patchify_x3: x {tuple(x.shape)} is not [n, 3, S, S]')
+    n, _, S, _ = x.shape
+    if patch <= 0 or S % patch:
+        raise ValueError(f'patchify_x3: image size {S} is not a multiple of the patch size {patch}')
+    kpad = patch_kpad(patch) if kpad is None else int(kpad)
+    if kpad % 32 or kpad < 3 * patch * patch:
+        raise ValueError(f'patchify_x3: kpad {kpad} (a multiple of 32, at least 3*patch*patch = {3 * patch * patch})')
+    g = S // patch
+    img = torch.empty((n, g, g, 2 * kpad), dtype=torch.float16, device=x.device)
+    _call('dts_patchify_x3', xp, _ptr(img), n, S, patch, kpad)
+    return SplitAct(img, kpad)
+
+
+def vit_tokens_f32(patches, cls, pos):
+    """patches float32 [n, t-1, c], cls float32 [c], pos float32 [t, c] -> float32 tokens [n, t, c]: row 0 = cls + pos[0], row 1 + p =
+    patches[:, p] + pos[1 + p] (dts_vit_tokens_f32: one float32 add); c a multiple of 4."""
+    pp = _f32_gpu(patches, 'vit_tokens_f32', 'patches')
+    if patches.dim() != 3:
+        raise ValueError(f'vit_tokens_f32: patches {tuple(patches.shape)} is not [n, t - 1, c]')
+    n, tp, c = patches.shape
+    if tuple(cls.shape) != (c,) or tuple(pos.shape) != (tp + 1, c):
+        raise ValueError(f'vit_tokens_f32: cls {tuple(cls.shape)} / pos {tuple(pos.shape)} for patches {tuple(patches.shape)}')
+    if tp < 1 or c <= 0 or c % 4:
+        raise ValueError(f'vit_tokens_f32: {tp} patches x {c} channels (at least one patch, channels a multiple of 4)')
+    out = torch.empty((n, tp + 1, c), dtype=torch.float32, device=patches.device)
+    _call('dts_vit_tokens_f32', pp, _ptr(cls, 'cls', torch.float32), _ptr(pos, 'pos', torch.float32), _ptr(out), n, tp + 1, c)
+    return out
+
+
+def vit_head_f32(tokens, gamma, beta, eps=1e-5):
+    """tokens float32 [n, t, c] -> float32 [n, c] = LayerNorm(tokens[:, 0]) * gamma + beta (dts_vit_head_f32: the class token only);
+    c a multiple of 8, at most 2048.  The projection follows as ops.linear."""
+    tp = _f32_gpu(tokens, 'vit_head_f32', 'tokens')
+    if tokens.dim() != 3:
+        raise ValueError(f'vit_head_f32: tokens {tuple(tokens.shape)} is not [n, t, c]')
+    n, t, c = tokens.shape
+    if c <= 0 or c % 8 or c > 2048:
+        raise ValueError(f'vit_head_f32: {c} channels (a multiple of 8, at most 2048)')
+    gp, bp = _norm_pair('vit_head_f32', gamma, beta, c)
+    out = torch.empty((n, c), dtype=torch.float32, device=tokens.device)
+    _call('dts_vit_head_f32', tp, _ptr(out), n, t, c, float(eps), gp, bp)
     return out
 
 

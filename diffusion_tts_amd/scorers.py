@@ -221,11 +221,12 @@ class CLIPScorer(Scorer):
                  tower_dtype=torch.float16, text_tower='transformers'):
         """vision_tower: 'transformers' (default: `model.get_image_features`, the reference's arithmetic in the model's own precision) |
         'hip' (clip_vision.CLIPVisionTower built from `model`: the image tower on this build's kernels with `tower_dtype` = float16 /
-        bfloat16 activations -- a 16-bit THROUGHPUT mode of the scorer, where the reference scores in float32; a configuration the kernels
-        do not take is refused by name, there is no fallback).  The text branch, its cache and the pre-processing are the same either way.
+        bfloat16 activations -- a 16-bit THROUGHPUT mode of the scorer, where the reference scores in float32 -- or ops.F16X3, the
+        parity-grade mode (clip_vision.CLIPVisionTowerX3): float32 activations, split-precision matrix products; a configuration the kernels do not take is refused by
+        name, there is no fallback).  The text branch, its cache and the pre-processing are the same either way.
         text_tower: 'transformers' (default: `model.get_text_features`) | 'hip' (clip_text.CLIPTextTower built from `model`, `tower_dtype`
         activations: the prompt's embedding from this build's kernels -- an opt-in 16-bit mode like vision_tower='hip'; the reference embeds
-        the text in float32).  The text-embedding cache and the cosine tail are unchanged.
+        the text in float32; it has no split-precision form, so tower_dtype=ops.F16X3 with text_tower='hip' is refused).  The text-embedding cache and the cosine tail are unchanged.
         device_preprocess: run the image processor's resize / rescale / normalise on the GPU (clip_preprocess.DevicePreprocessor:
         Pillow's integer bicubic + the processor's own value table, identical pixel_values) whenever the images are square uint8 GPU
         tensors and the processor has the stock configuration; False keeps the reference's host path (images.cpu() + PIL) always."""
@@ -256,11 +257,15 @@ class CLIPScorer(Scorer):
                 tokenizer = ByteTokenizer(tc.vocab_size)
         if vision_tower not in ('transformers', 'hip'):
             raise ValueError(f"CLIPScorer: vision_tower must be 'transformers' or 'hip', got {vision_tower!r}")
+        if text_tower == 'hip' and isinstance(tower_dtype, str) and tower_dtype == ops.F16X3:
+            raise ValueError("CLIPScorer: text_tower='hip' with tower_dtype='f16x3': the text tower has no split-precision form (it would "
+                             "need a masked split-precision attention); keep text_tower='transformers', which embeds the prompt in float32")
         self.clip = model.to(self.device).eval()
         self.vision_tower, self._tower = vision_tower, None
         if vision_tower == 'hip':
-            from .clip_vision import CLIPVisionTower
-            self._tower = CLIPVisionTower.from_clip_model(self.clip, dtype=tower_dtype, device=self.device)
+            from .clip_vision import CLIPVisionTower, CLIPVisionTowerX3
+            x3 = isinstance(tower_dtype, str) and tower_dtype == ops.F16X3
+            self._tower = (CLIPVisionTowerX3 if x3 else CLIPVisionTower).from_clip_model(self.clip, dtype=tower_dtype, device=self.device)
         if text_tower not in ('transformers', 'hip'):
             raise ValueError(f"CLIPScorer: text_tower must be 'transformers' or 'hip', got {text_tower!r}")
         self.text_tower, self._text_tower = text_tower, None
@@ -291,7 +296,7 @@ class CLIPScorer(Scorer):
                 images = images.cpu()
             pix = self.image_processor(images=images, return_tensors='pt', do_rescale=do_rescale)['pixel_values']
         if self._tower is not None:
-            img_emb = self._tower(pix.to(dev))                         # f32 [n, projection_dim] from 16-bit activations
+            img_emb = self._tower(pix.to(dev))                         # f32 [n, projection_dim] (activations in tower_dtype)
         else:
             img_emb = _features(self.clip.get_image_features(pixel_values=pix.to(self.dtype).to(dev))).float().contiguous()
         n = img_emb.shape[0]

@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 117        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 118        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -53,7 +53,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      114: dts_patchify, dts_vit_tokens, dts_gelu, dts_vit_head (the CLIP scorer's vision tower);
                                      115: dts_jpeg_workspace_bytes, dts_jpeg_size (the compressibility scorer's JPEG byte length);
                                      116: dts_group_rows (the SD U-Net's distinct text contexts, grouped on the device);
-                                     117: dts_attention_masked, dts_text_tokens (the CLIP text tower: SD's text encoder and the CLIP scorer's text side)) */
+                                     117: dts_attention_masked, dts_text_tokens (the CLIP text tower: SD's text encoder and the CLIP scorer's text side);
+                                     118: dts_layer_norm_x3, dts_gelu_x3, dts_patchify_x3, dts_vit_tokens_f32, dts_vit_head_f32 (the CLIP vision tower in DTS_F16X3)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -250,6 +251,29 @@ int dts_text_tokens(const int32_t* ids, const float* tok, const float* pos, void
  * biased variance, statistics in f32 as dts_layer_norm) -- token 0 only, the other t - 1 tokens are never read.  tokens [n][t][c] DTS_BF16 /
  * DTS_F16; c % 8 == 0, c <= 2048.  visual_projection follows as dts_linear on the f32 rows. */
 int dts_vit_head(const void* tokens, float* out, int dtype, int n, int t, int c, float eps, const float* gamma, const float* beta, dts_stream s);
+
+/* ---- the CLIP vision tower in the split-precision mode (DTS_F16X3): f32 activations; a result whose only reader is a split-precision 1x1
+ * dts_conv2d leaves as that convolution's operand image, bit for bit what dts_split3_f16 makes of the f32 values (f16 [rows][2*c], per 32
+ * channels hi(32) | lo * 2^11 (32)), and the f32 tensor is not written.  All pointers 16-byte aligned. ---- */
+/* torch.nn.LayerNorm (CLIPEncoderLayer.layer_norm1 / layer_norm2, CLIPVisionTransformer.pre_layrnorm) over f32 rows [rows][c]: biased variance
+ * as the mean of (x - mean)^2 over the row in registers, one wave per row; the statistics and (x - mean) * rstd * gamma + beta are formed in f64
+ * and rounded once to f32 (an f32 rstd's rounding error would scale every output of the row); gamma / beta f32 [c].  out_f32 (nullable): the normalised rows f32
+ * [rows][c] (pre_layrnorm: the residual stream); out_split (nullable): their operand image f16 [rows][2*c] (the qkv and fc1 projections'
+ * operand) -- the same bits whether or not out_f32 is written.  At least one of the two; c % 32 == 0, c <= 2048. */
+int dts_layer_norm_x3(const float* x, float* out_f32, void* out_split, int64_t rows, int c, float eps, const float* gamma, const float* beta,
+                      dts_stream s);
+/* CLIPMLP's activation_fn between fc1 and fc2: x f32 [rows][c] -> the operand image f16 [rows][2*c] of act(x); kind as dts_gelu (0 = quick-GELU
+ * x / (1 + exp(-1.702 x)), 1 = the erf GELU x * erfc(-x / sqrt 2) / 2: both finite over the whole f32 range).  c % 32 == 0. */
+int dts_gelu_x3(const float* x, void* out_split, int64_t rows, int c, int kind, dts_stream s);
+/* dts_patchify's gather for the split-precision patch embedding: x f32 NCHW [n][3][size][size] -> the operand image f16 [n][g*g][2*kpad] of the
+ * unrounded patch rows, same column order (c*patch + py)*patch + px, columns 3*patch*patch .. kpad-1 written as zeros.  kpad % 32 == 0. */
+int dts_patchify_x3(const float* x, void* out_split, int n, int size, int patch, int kpad, dts_stream s);
+/* dts_vit_tokens in f32 (CLIPVisionEmbeddings: cat([class_embedding, patch_embeds], 1) + position_embedding): tokens f32 [n][t][c], tokens[n][0] =
+ * cls + pos[0], tokens[n][1 + p] = patches[n][p] + pos[1 + p] -- one f32 add per element; patches f32 [n][t-1][c].  c % 4 == 0, t >= 2. */
+int dts_vit_tokens_f32(const float* patches, const float* cls, const float* pos, float* tokens, int n, int t, int c, dts_stream s);
+/* dts_vit_head over f32 tokens [n][t][c] (post_layernorm of the class token): out f32 [n][c] = LayerNorm(tokens[n][0][:]) * gamma + beta with
+ * dts_layer_norm_x3's arithmetic, one wave per sample; the other tokens are never read.  c % 8 == 0, c <= 2048.  dts_linear follows. */
+int dts_vit_head_f32(const float* tokens, float* out, int n, int t, int c, float eps, const float* gamma, const float* beta, dts_stream s);
 
 /* ---- K7/K8: embedding MLP pieces and EDM preconditioning (networks.py:200-206,437-447,654-668) ---- */
 /* y[m][n] = act_out( act_in(x[m][:]) . w[n][:] + bias[n] (+ y[m][n] if accumulate) ); all f32; act: 0 none, 1 SiLU */

@@ -21,7 +21,8 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
     --text-encoder: SD backend: transformers (default: the stock CLIPTextModel) | hip (clip_text.CLIPTextTower on this build's kernels, read
                   from $DTS_SD_TEXT_ENCODER_DIR or the cached snapshot's text_encoder/; no fallback)
     --clip-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel image tower, float32 like the reference) | hip
-                  (clip_vision.CLIPVisionTower on this build's kernels, float16 activations: a 16-bit throughput mode of the scorer; no fallback)
+                  (clip_vision.CLIPVisionTower on this build's kernels; no fallback).  --clip-tower-dtype f16 (default) | bf16: 16-bit
+                  throughput modes of the scorer | f16x3: the parity-grade mode (float32 activations, split-precision matrix products)
     --jpeg-codec: --scorer compressibility: pil (default: the reference's host encode per image) | hip (the same byte count computed on the
                   GPU, identical rewards; image sides must be multiples of 16; no fallback)
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
@@ -40,10 +41,14 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='transformers', clip_model=None, jpeg_codec='pil'):
+CLIP_TOWER_DTYPES = {'f16': torch.float16, 'bf16': torch.bfloat16, 'f16x3': 'f16x3'}      # --clip-tower-dtype -> CLIPVisionTower dtype
+
+
+def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='transformers', clip_model=None, jpeg_codec='pil',
+               clip_tower_dtype='f16'):
     """main.py:60-71 of the reference.  compute_dtype: the search's --dtype; the ImageNet classifier runs in the search's own mode for the two parity
-    modes (float32, f16x3) and in float16 otherwise (also beside a bfloat16 denoiser: scorers.ImageNetScorer).  clip_tower: --clip-tower;
-    clip_model: a transformers.CLIPModel to score with instead of the cached checkpoint (scorers.CLIPScorer model=).  jpeg_codec: --jpeg-codec."""
+    modes (float32, f16x3) and in float16 otherwise (also beside a bfloat16 denoiser: scorers.ImageNetScorer).  clip_tower: --clip-tower,
+    clip_tower_dtype: --clip-tower-dtype (the activations of the 'hip' tower); clip_model: a transformers.CLIPModel to score with instead of the cached checkpoint (scorers.CLIPScorer model=).  jpeg_codec: --jpeg-codec."""
     from diffusion_tts_amd import scorers as S
     if scorer_name == 'brightness':
         return S.BrightnessScorer(dtype=torch.float32)
@@ -52,7 +57,8 @@ def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='tra
     if scorer_name == 'imagenet' and backend == 'edm':
         return S.ImageNetScorer(dtype=torch.float32, device=device, compute_dtype=compute_dtype if compute_dtype in (torch.float32, 'f16x3') else torch.float16)
     if scorer_name == 'clip' and backend == 'sd':
-        return S.CLIPScorer(dtype=torch.float32, device=device, model=clip_model, vision_tower=clip_tower)    # local HF cache only; raises with instructions otherwise
+        return S.CLIPScorer(dtype=torch.float32, device=device, model=clip_model, vision_tower=clip_tower,
+                            tower_dtype=CLIP_TOWER_DTYPES[clip_tower_dtype])    # local HF cache only; raises with instructions otherwise
     raise ValueError(f"Unknown or invalid scorer '{scorer_name}' for backend '{backend}'")
 
 
@@ -150,7 +156,7 @@ def main_sd(args):
     te = load_sd_text_encoder(model_id, dev, te_kind)
 
     scorer = get_scorer('sd', args.scorer, dev, clip_tower=getattr(args, 'clip_tower', 'transformers'),
-                        jpeg_codec=getattr(args, 'jpeg_codec', 'pil'))
+                        jpeg_codec=getattr(args, 'jpeg_codec', 'pil'), clip_tower_dtype=getattr(args, 'clip_tower_dtype', 'f16'))
     pipe = SDSearchPipeline(unet, vae, device=dev, text_encoder=te, tokenizer=tok)     # encodes the prompt itself (pipeline...:976-992)
     params = {'N': args.N, 'lambda': args.lambda_, 'eps': args.eps, 'K': args.K, 'B': args.B, 'S': args.S}
     torch.manual_seed(args.seed)                                                       # same host RNG stream on every rank
@@ -203,6 +209,9 @@ def build_parser():
     parser.add_argument('--clip-tower', dest='clip_tower', type=str, default='transformers', choices=['transformers', 'hip'],
                         help="SD backend, --scorer clip: 'hip' = the CLIP image tower on this build's kernels in float16 (a 16-bit throughput mode: the "
                              "reference scores in float32; an error if the kernels do not take the model's shape), 'transformers' = the stock module")
+    parser.add_argument('--clip-tower-dtype', dest='clip_tower_dtype', type=str, default='f16', choices=['f16', 'bf16', 'f16x3'],
+                        help="--clip-tower hip: the tower's activations.  f16 (default) / bf16: the 16-bit throughput modes; f16x3: the parity-grade "
+                             "mode (float32 activations, split-precision matrix products: the float32 module's rewards to its own rounding error)")
     parser.add_argument('--jpeg-codec', dest='jpeg_codec', type=str, default='pil', choices=['pil', 'hip'],
                         help="--scorer compressibility: 'hip' = the JPEG byte length computed on the GPU (identical rewards; image sides must be "
                              "multiples of 16, an error otherwise), 'pil' = the reference's host encode of every image")
