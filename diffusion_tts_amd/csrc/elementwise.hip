@@ -160,20 +160,29 @@ __global__ void heun_correct_kernel(const double* __restrict__ x_hat, const floa
 }
 
 // ---- K10/K11 -----------------------------------------------------------------------------------------
+// The reference's `(x * 127.5 + 128).clip(0, 255).to(torch.uint8)` is two tensor operations: the product is rounded, then the sum.  A
+// fused multiply-add rounds once and lands on the other side of an integer for about two values in a million (one pixel level off), so
+// contraction is switched off in both kernels: v_mul + v_add, never v_fma.
 template <typename E>
 __global__ void quantize_kernel(const E* __restrict__ x, uint8_t* __restrict__ out, long long count) {
+#pragma clang fp contract(off)
   GSL(i, count) {
     // the reference converts the f32 denoiser output to f64 first (edm/main.py:87,92 .to(float64)), so the
-    // affine map and the clip run in f64 whatever the storage type
-    double v = (double)x[i] * 127.5 + 128.0;
+    // affine map and the clip run in f64 whatever the storage type: f64 product rounded, f64 sum rounded (a float32 input's product
+    // with 127.5 is exact in f64, so only the double instance can differ from the fused form)
+    double v = (double)x[i] * 127.5;
+    v = v + 128.0;
     v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
     out[i] = (uint8_t)v;                                   // truncation, as Tensor.to(torch.uint8)
   }
 }
-// SD backend: the image is f32 and the reference's affine map runs in f32 (pipeline_stable_diffusion.py:1116)
+// SD backend: the image is f32 and the reference's affine map runs in f32 (pipeline_stable_diffusion.py:1116): f32 product rounded, then
+// f32 sum rounded
 __global__ void quantize_f32math_kernel(const float* __restrict__ x, uint8_t* __restrict__ out, long long count) {
+#pragma clang fp contract(off)
   GSL(i, count) {
-    float v = x[i] * 127.5f + 128.0f;
+    float v = x[i] * 127.5f;
+    v = v + 128.0f;
     v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
     out[i] = (uint8_t)v;
   }

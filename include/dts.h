@@ -310,7 +310,8 @@ int dts_heun_correct(const double* x_hat, const float* D2, const double* d_cur, 
 
 /* ---- K10/K11: scorer pre-processing and brightness reward (edm/main.py:126; scorers.py:38-52) ----- */
 /* u8 = trunc(clip(x*127.5+128, 0, 255)); x is f64 (is_f32=0) or f32 (1): arithmetic in f64 as the EDM loop's (.to(float64) first);
- * is_f32=2: f32 input AND f32 arithmetic, as the SD loop's (pipeline_stable_diffusion.py:1116) */
+ * is_f32=2: f32 input AND f32 arithmetic, as the SD loop's (pipeline_stable_diffusion.py:1116).  The product is rounded, then the sum
+ * (two tensor operations in the reference): never a fused multiply-add, whose single rounding changes the byte of ~2 values in a million */
 int dts_quantize_u8(const void* x, int is_f32, uint8_t* out, int64_t count, dts_stream s);
 /* rewards[n] = clamp(mean_hw(0.2126 R + 0.7152 G + 0.0722 B)/1, 0, 1) on u8/255 images NCHW [n][3][h][w] */
 int dts_brightness(const uint8_t* img, float* rewards, int n, int hw, dts_stream s);
