@@ -26,6 +26,13 @@ class ConvArgs(C.Structure):
                 ('skip_c', C.c_int32), ('skip_x', _p), ('skip_w', _p), ('skip_acc_scale', C.c_float), ('skip_up', C.c_int32)]
 
 
+class ConvPlanInfo(C.Structure):
+    """dts_conv_plan_info: the launch plan of a dts_conv2d call (include/dts.h)"""
+    _fields_ = [(f, C.c_int32) for f in ('kernel', 'tile', 'waves', 'stages', 'pf', 'gn', 'sk', 'dbg', 'splits', 'ks_per_split', 'n_ct', 'n_pt', 'nblk',
+                                         'threads', 'lds_bytes', 'stats_in_kernel', 'stats_in_reduce', 'stats_written', 'epi_rows', 'fuses_gn',
+                                         'folds_skip', 'refused')]
+
+
 # name -> argtypes (every function returns int status except the three noted below)
 SIGNATURES = {
     'dts_nchw_to_nhwc': [_p, _p, _i, _i, _i, _i, _i, _p],
@@ -86,11 +93,11 @@ SIGNATURES = {
     'dts_cfg_combine': [_p, _p, _f, _p, _i, _i64, _p],
     'dts_ddim_candidates': [_p, _p, _p, _p, _p, _i, _f, _f, _f, _i, _i64, _p],
 }
-OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64),
+OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_conv_plan': ([C.POINTER(ConvArgs), C.POINTER(ConvPlanInfo)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64),
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 118              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 119              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

@@ -20,6 +20,10 @@
 // applied to the per-lane SOURCE chunk and again on the fragment read.  Out-of-image rows read a 16-byte zero word.
 // Double-buffered: tile k+1 is in flight while tile k feeds the MFMAs.
 // f32 mode uses v_mfma_f32_16x16x4_f32 (exact f32 FMA chain) = the parity path.
+//
+// Host side (end of the file): conv_plan() decides everything about a call once -- kernel, tile, waves, ring depth, K split, grid, LDS, who
+// writes the statistics, what is refused -- and conv_launch_plan() is the one switch from those fields to a kernel instantiation; dts_conv2d
+// runs the two, the queries (dts_conv_kernel, dts_conv_fuses_gn, dts_conv_folds_skip, dts_conv_plan) return fields of the same plan.
 #include "dts_common.h"
 #include <hip/hip_ext.h>
 #include <type_traits>
@@ -30,8 +34,8 @@ namespace {
 
 // per-call launch state that is not a kernel argument (no globals: dts_conv2d may be called from several host threads)
 struct ConvCall {
+  hipStream_t st;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // optional dispatch-attached timing events (dts_conv_args)
-  bool stats_written = false;
 };
 
 struct ConvP {
@@ -1654,56 +1658,80 @@ int launch_reduce(const ConvP& q, bool with_stats, hipStream_t st) {
   }
 }
 
-template <typename T, int MT, int NT, int WM, int WN, bool PF, int STAGES, typename OT = T>
-int launch_conv_staged(const ConvP& q, int nblk, int splits, hipStream_t st, ConvCall& call) {
-  constexpr int NW = WM * WN;
-  constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
-  const size_t lds = (size_t)STAGES * (BM + BN) * 128;
+// ---- the launch plan ---------------------------------------------------------------------------------------------------------------
+// Everything the host decides about one dts_conv2d call, decided in ONE place (conv_plan) from the shape, the dtype, which optional
+// arguments are present and the tuning knobs.  dts_conv2d launches what the plan says (conv_launch_plan); dts_conv_kernel,
+// dts_conv_fuses_gn, dts_conv_folds_skip and dts_conv_plan return fields of it.
+
+// the knobs, read once per plan: DTS_CONV_VARIANT (1 = ping-pong wherever it applies, 0 = never, unset = by shape), DTS_CONV_TILE=64|128|192
+// (only honoured when it divides cout), DTS_CONV_SPLITS (forced K split), DTS_CONV_STAGES = 2 | 3 | 4 and DTS_CONV_WAVES = 4 | 8 (forced ring depth /
+// waves per block), DTS_CONV_HALF_ROUND, DTS_CONV_EPI32, DTS_CONV_SKIP_FOLD: tuning and A/B aids.  DTS_F32_TILE192=0 restores the smaller f32
+// tile (A/B aid; plain environment, read once per process)
+struct ConvKnobs { int variant, tile, splits, stages, waves, half_round, epi32, skip_fold; bool f32_tile192; };
+ConvKnobs conv_knobs() {
+  static const bool f32_192 = !(getenv("DTS_F32_TILE192") && atoi(getenv("DTS_F32_TILE192")) == 0);
+  return {dts_knob_get(DTS_KNOB_CONV_VARIANT), dts_knob_get(DTS_KNOB_CONV_TILE), dts_knob_get(DTS_KNOB_CONV_SPLITS),
+          dts_knob_get(DTS_KNOB_CONV_STAGES), dts_knob_get(DTS_KNOB_CONV_WAVES), dts_knob_get(DTS_KNOB_CONV_HALF_ROUND),
+          dts_knob_get(DTS_KNOB_CONV_EPI32), dts_knob_get(DTS_KNOB_CONV_SKIP_FOLD), f32_192};
+}
+
+// the fields of dts_conv_plan_info (include/dts.h says what each means) + why dts_conv2d must refuse the call, where `refused` is set
+struct ConvPlan : dts_conv_plan_info { char refuse[200]; };
+
+// ---- the launcher: a plan becomes a launch
+template <auto KERNEL>
+int conv_launch(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
   static bool attr_done[DTS_MAX_DEVICES] = {};            // the attribute is per DEVICE: a process that drives several GPUs sets it on each
   const int dev = current_device();
   if (!attr_done[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<T, MT, NT, WM, WN, PF, STAGES, OT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
     attr_done[dev] = true;
   }
+  const dim3 grid(pl.nblk, pl.splits), block(pl.threads);
   if (call.ev_start != nullptr && call.ev_stop != nullptr)
-    hipExtLaunchKernelGGL((conv_igemm_kernel<T, MT, NT, WM, WN, PF, STAGES, OT>), dim3(nblk, splits), dim3(64 * NW), lds, st, call.ev_start, call.ev_stop, 0, q);
+    hipExtLaunchKernelGGL(KERNEL, grid, block, (size_t)pl.lds_bytes, call.st, call.ev_start, call.ev_stop, 0, q);
   else
-    hipLaunchKernelGGL((conv_igemm_kernel<T, MT, NT, WM, WN, PF, STAGES, OT>), dim3(nblk, splits), dim3(64 * NW), lds, st, q);
-  DTS_CHECK_LAUNCH("dts_conv2d");
+    hipLaunchKernelGGL(KERNEL, grid, block, (size_t)pl.lds_bytes, call.st, q);
+  DTS_CHECK_LAUNCH(pl.kernel != 0 ? "dts_conv2d(ping-pong)" : "dts_conv2d");
   return DTS_OK;
 }
 
-template <typename T, int MT, int NT, int WM, int WN, bool PF, typename OT = T>
-int launch_conv(const ConvP& p, hipStream_t st, float* ws, long long ws_bytes, ConvCall& call) {
-  constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
-  constexpr int BKE = 8 * ET<T>::EPV;
-  ConvP q = p;
-  q.n_ct = p.cout / BM;
-  q.n_pt = (p.P + BN - 1) / BN;
-  const int nblk = q.n_ct * q.n_pt;
-  const int nk = p.taps * (p.cin / BKE);
-  // split-K when the tile grid cannot fill the chip.  Two launch forms follow from the grid (see below): at most 256 blocks run as 8 waves
-  // with a 3-deep ring, one block per CU; more run as 4 waves with two co-resident blocks per CU (512 slots).  Estimated microseconds per
-  // form, from tools/conv_stamps.py and the split sweep of tools/conv_bench.py (conv_splits = 1..8 at 4, 8 and 16 rows,
-  // profiles/r03_small_batch_experiments.txt item 9): ~5 us of prologue + epilogue; 0.75 us per K step for the 8-wave form, 1.25 us per step
-  // and round of resident blocks for the 4-wave form; the second pass moves `splits` f32 slabs of P x cout (~3 us + slab bytes at ~4 MB/us),
-  // which for many-pixel layers at a small batch costs more than the shorter K loop saves.
+// conv_igemm_kernel of one tile (MT x 4 MFMA tiles per wave, WM x WN waves in its 4-wave form; the 8-wave form halves the couts per wave)
+template <typename T, typename OT, int MT, int WM, int WN, bool PF>
+int conv_launch_igemm(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
+#define DTS_IGEMM(MT_, WM_, STAGES_) conv_launch<&conv_igemm_kernel<T, MT_, 4, WM_, WN, PF, STAGES_, OT>>(pl, q, call)
+  if constexpr (sizeof(T) == 2) {                            // (f32: the 2-deep ring with 4 waves only)
+    if (pl.waves == 8) return pl.stages == 3 ? DTS_IGEMM(MT / 2, WM * 2, 3) : DTS_IGEMM(MT / 2, WM * 2, 2);
+    if (pl.stages == 3) return DTS_IGEMM(MT, WM, 3);
+    if constexpr (std::is_same<T, OT>::value)
+      if (pl.stages == 4) return DTS_IGEMM(MT, WM, 4);
+  }
+  return DTS_IGEMM(MT, WM, 2);
+#undef DTS_IGEMM
+}
+
+// K split of a conv_igemm_kernel launch.  Split-K when the tile grid cannot fill the chip.  Two launch forms follow from the grid: at most
+// 256 blocks run as 8 waves with a 3-deep ring, one block per CU; more run as 4 waves with two co-resident blocks per CU (512 slots).
+// Estimated microseconds per form, from tools/conv_stamps.py and the split sweep of tools/conv_bench.py (conv_splits = 1..8 at 4, 8 and
+// 16 rows, profiles/r03_small_batch_experiments.txt item 9): ~5 us of prologue + epilogue; 0.75 us per K step for the 8-wave form, 1.25 us
+// per step and round of resident blocks for the 4-wave form; the second pass moves `splits` f32 slabs of P x cout (~3 us + slab bytes at
+// ~4 MB/us), which for many-pixel layers at a small batch costs more than the shorter K loop saves.
+// slab: bytes of one f32 partial slab; can8: the 8-wave form exists (16-bit operands); x3: split precision.
+int igemm_splits(int nblk, int nk, double slab, bool can8, bool x3, bool ws, long long ws_bytes, int forced) {
   const int slots = 512;                                     // 256 CUs x 2 resident blocks
   int splits = 1;
-  if (ws != nullptr && nblk < (slots * 3) / 4 && nk >= 16 && !p.out_split2) {      // (the split-image output is written by the conv epilogue only)
+  if (ws && nblk < (slots * 3) / 4 && nk >= 16) {
     int smax = 8;
     if (smax > nk / 8) smax = nk / 8;
-    while (smax > 1 && (long long)smax * p.P * p.cout * 4 > ws_bytes) --smax;
+    while (smax > 1 && (long long)smax * (long long)slab > ws_bytes) --smax;
     if (smax < 1) smax = 1;
-    const bool can8 = sizeof(T) == 2 && MT % 2 == 0;
-    constexpr double KS = std::is_same<T, OT>::value ? 1.0 : 1.5;        // a split-precision K step carries 3 MFMAs per tile instead of 2
+    const double KS = x3 ? 1.5 : 1.0;                        // a split-precision K step carries 3 MFMAs per tile instead of 2
     auto est = [&](int s_) {
       const int steps = (nk + s_ - 1) / s_;
       double t;
       if (can8 && (long long)nblk * s_ <= 256) t = 5.0 + steps * 0.75 * KS;
       else t = (double)((nblk * s_ + slots - 1) / slots) * (5.5 + steps * 1.25 * KS);
-      if (s_ > 1) t += 3.0 + (s_ + 0.5) * (double)p.P * p.cout * 4.0 / 4.0e6;
+      if (s_ > 1) t += 3.0 + (s_ + 0.5) * slab / 4.0e6;
       return t;
     };
     int best = 1;
@@ -1711,137 +1739,44 @@ int launch_conv(const ConvP& p, hipStream_t st, float* ws, long long ws_bytes, C
       if (est(s_) < est(best)) best = s_;
     splits = best;
   }
-  {
-    const int forced = dts_knob_get(DTS_KNOB_CONV_SPLITS);    // DTS_CONV_SPLITS: tuning aid, as in the ping-pong launcher
-    // (the reduce pass is instantiated for 2..8 slabs: a larger forced value is clamped here, as in the ping-pong launcher, instead of
-    // launching the conv kernel and then failing in launch_reduce with the output never produced)
-    const int f8 = (forced > 8 ? 8 : forced) * (p.out_split2 ? 0 : 1);
-    if (f8 > 0 && ws != nullptr && nk >= 2 * f8 && (long long)f8 * p.P * p.cout * 4 <= ws_bytes) splits = f8;
-  }
-  q.ks_per_split = (nk + splits - 1) / splits;
-  splits = (nk + q.ks_per_split - 1) / q.ks_per_split;       // no empty split
-  q.splits = splits;
-  q.partial = ws;
-  // statistics come from the fused epilogue (whole launches, 64-pixel wave strips) or, under split-K, from the reduce pass
-  float* const stats_req = p.stats;
-  const bool stats_in_reduce = splits > 1 && stats_req != nullptr && (p.hout * p.wout) % 64 == 0 && p.cout % 4 == 0;
-  if (splits > 1 || NT != 4) q.stats = nullptr;
-  call.stats_written = q.stats != nullptr || stats_in_reduce;
-  // ring depth: a grid of at most one block per CU cannot hide a tile's round trip behind a co-resident block, so it keeps two
-  // tiles in flight (3 stages; DTS_CONV_STAGES = 2 | 3 | 4 forces a depth for A/B runs)
-  int stages = ((long long)nblk * splits <= 256 && q.ks_per_split >= 3) ? 3 : 2;
-  const int forced_stages = dts_knob_get(DTS_KNOB_CONV_STAGES);
-  if (forced_stages >= 2 && forced_stages <= 4) stages = forced_stages;
-  if (std::is_same<T, float>::value) stages = 2;            // parity mode: one configuration
-  if ((size_t)stages * (BM + BN) * 128 > 160 * 1024) stages = 3;
-  // 8 waves per block (the same tile, half the couts per wave) when the grid leaves one block per CU; DTS_CONV_WAVES = 4 | 8 forces it
-  bool waves8 = sizeof(T) == 2 && MT % 2 == 0 && (long long)nblk * splits <= 256;
-  const int forced_waves = dts_knob_get(DTS_KNOB_CONV_WAVES);
-  if (forced_waves == 4) waves8 = false;
-  if (forced_waves == 8) waves8 = sizeof(T) == 2 && MT % 2 == 0;
-  int rc;
-  if constexpr (sizeof(T) == 2 && MT % 2 == 0) {
-    if (waves8) {
-      if (stages >= 3) rc = launch_conv_staged<T, MT / 2, NT, WM * 2, WN, PF, 3, OT>(q, nblk, splits, st, call);
-      else rc = launch_conv_staged<T, MT / 2, NT, WM * 2, WN, PF, 2, OT>(q, nblk, splits, st, call);
-      if (rc != DTS_OK) return rc;
-      if (splits > 1) {
-        if (stats_in_reduce) q.stats = stats_req;
-        return launch_reduce<OT>(q, stats_in_reduce, st);
-      }
-      return DTS_OK;
-    }
-  }
-  // (the 4-deep ring exists for the A/B knob only, and only for OT = T)
-  if (stages == 4 && std::is_same<T, OT>::value) rc = launch_conv_staged<T, MT, NT, WM, WN, PF, (sizeof(T) == 2 ? 4 : 2)>(q, nblk, splits, st, call);
-  else if (stages >= 3) rc = launch_conv_staged<T, MT, NT, WM, WN, PF, (sizeof(T) == 2 ? 3 : 2), OT>(q, nblk, splits, st, call);
-  else rc = launch_conv_staged<T, MT, NT, WM, WN, PF, 2, OT>(q, nblk, splits, st, call);
-  if (rc != DTS_OK) return rc;
-  if (splits > 1) {
-    if (stats_in_reduce) q.stats = stats_req;
-    return launch_reduce<OT>(q, stats_in_reduce, st);
-  }
-  return DTS_OK;
+  // (the reduce pass is instantiated for 2..8 slabs: a larger forced value is clamped, as for the ping-pong kernel)
+  const int f8 = forced > 8 ? 8 : forced;
+  if (f8 > 0 && ws && nk >= 2 * f8 && (long long)f8 * (long long)slab <= ws_bytes) splits = f8;
+  return splits;
 }
 
-// ---- ping-pong launcher: one block per (192- or 128-cout tile, 256-pixel tile[, K split]); 512 threads, 154 KB (MT = 6) / 130 KB (MT = 4) of LDS
-template <typename T, int TAPS, int DBG = 0, bool GN = false, int MT = 6, typename OT = T, bool SK = false>
-int launch_conv_pp(const ConvP& p, hipStream_t st, float* ws, long long ws_bytes, ConvCall& call) {
-  // 3x3 only: the kernel's TAPS == 1 form has a landing race with more than one channel chunk (see conv_pick_pp) and must not be launched
-  static_assert(TAPS == 9, "conv_pp_kernel: only the 3x3 form is safe to launch");
-  if constexpr (sizeof(T) != 2) {
-    return DTS_ERR_UNSUPPORTED;
-  } else {
-    constexpr int BM = 32 * MT, BN = 256, BKE = 64;
-    ConvP q = p;
-    q.n_ct = p.cout / BM;
-    q.n_pt = (p.P + BN - 1) / BN;
-    const int nblk = q.n_ct * q.n_pt;
-    const int nk = p.taps * (p.cin / BKE);
-    int splits = 1;
-    const int forced = dts_knob_get(DTS_KNOB_CONV_SPLITS);
-    if (ws != nullptr && nk >= 16 && !p.out_split2 && !SK) {      // (SK: the second K loop needs the complete accumulators; dts_conv_folds_skip only admits grids that would not split)
-      if (forced > 0) splits = forced;
-      else if (nblk < 192) {
-        // One resident block per CU.  Splitting K fills idle CUs but pays a second pass over `splits` f32 slabs of P x cout, which for
-        // the many-pixel layers of a SMALL batch costs more than it saves (64x64 level at 8 rows: 2 x 25 MB of slabs for a 10 us
-        // shorter K loop -- tools/conv_stamps.py).  Estimated microseconds, from the in-kernel stamps: ~5 us of prologue + epilogue,
-        // ~1.05 us per K tile (two ~1050-cycle segments), reduce = ~3 us + slab bytes at ~4 MB/us.
-        const int nchunk = nk / TAPS;
-        double best = 1e30;
-        for (int s_ = 1; s_ <= 8 && s_ <= nchunk; ++s_) {
-          const int cps = (nchunk + s_ - 1) / s_, se = (nchunk + cps - 1) / cps;
-          if (se != s_ || nblk * se > 256) continue;
-          double t = 5.0 + cps * TAPS * (std::is_same<T, OT>::value ? 1.05 : 1.4);      // (split precision: 72 MFMAs per tile and wave instead of 48)
-          if (se > 1) t += 3.0 + (se + 0.5) * (double)p.P * p.cout * 4.0 / 4.0e6;
-          if (t < best) { best = t; splits = se; }
-        }
-      }
-      if (splits > 8) splits = 8;
-      if (forced > 0 && splits > nk / 8) splits = nk / 8;
-      if (splits > nk / TAPS) splits = nk / TAPS;
-      while (splits > 1 && (long long)splits * p.P * p.cout * 4 > ws_bytes) --splits;
-      if (splits < 1) splits = 1;
-    }
-    {   // every split a whole number of channel chunks (TAPS tiles each)
-      const int nchunk = nk / TAPS;
-      const int cps = (nchunk + splits - 1) / splits;
-      q.ks_per_split = cps * TAPS;
-      splits = (nchunk + cps - 1) / cps;
-    }
-    q.splits = splits;
-    q.partial = ws;
-    float* const stats_req = p.stats;
-    const bool stats_in_reduce = splits > 1 && stats_req != nullptr && (p.hout * p.wout) % 64 == 0 && p.cout % 4 == 0;
-    if (splits > 1) q.stats = nullptr;
-    call.stats_written = q.stats != nullptr || stats_in_reduce;
-    constexpr size_t lds = (size_t)(6 * 16 * MT + 2 * 328) * 128;      // A: 2 groups x 3 slots x 16*MT rows; halo: 2 buffers x 328 rows
-    static bool attr_done[DTS_MAX_DEVICES] = {};
-    const int dev = current_device();
-    if (!attr_done[dev]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pp_kernel<T, TAPS, DBG, GN, MT, OT, SK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_done[dev] = true;
-    }
-    if (call.ev_start != nullptr && call.ev_stop != nullptr)
-      hipExtLaunchKernelGGL((conv_pp_kernel<T, TAPS, DBG, GN, MT, OT, SK>), dim3(nblk, splits), dim3(512), lds, st, call.ev_start, call.ev_stop, 0, q);
-    else
-      hipLaunchKernelGGL((conv_pp_kernel<T, TAPS, DBG, GN, MT, OT, SK>), dim3(nblk, splits), dim3(512), lds, st, q);
-    DTS_CHECK_LAUNCH("dts_conv2d(ping-pong)");
-    if (splits > 1) {
-      if (stats_in_reduce) q.stats = stats_req;
-      return launch_reduce<OT>(q, stats_in_reduce, st);
-    }
-    return DTS_OK;
-  }
-}
+// The ping-pong kernel runs one resident block per CU: below this many blocks its launcher weighs a K split (pp_splits).  The skip fold
+// needs the complete accumulators, so it is admitted only for grids that would NOT weigh one (conv_plan): one threshold, stated here.
+// (ADVICE.md item 2 suggests folding wherever pp_splits would in fact answer 1 -- grids of 129..191 blocks.  That changes which launches
+// fold, a speed change nobody has measured: a later pull request's.)
+inline bool pp_considers_split(long long nblk) { return nblk < 192; }
 
-template <typename T, bool PF, typename OT = T>
-int conv_dispatch_tile(const ConvP& p, int tile, hipStream_t st, float* ws, long long ws_bytes, ConvCall& call) {
-  switch (tile) {
-    case 192: return launch_conv<T, 6, 4, 2, 2, PF, OT>(p, st, ws, ws_bytes, call);
-    case 128: return launch_conv<T, 4, 4, 2, 2, PF, OT>(p, st, ws, ws_bytes, call);
-    default: return launch_conv<T, 4, 4, 1, 4, PF, OT>(p, st, ws, ws_bytes, call);
+// K split of a conv_pp_kernel launch (whole channel chunks of 9 tiles; the caller normalises)
+int pp_splits(int nblk, int nk, double slab, bool x3, bool ws, long long ws_bytes, int forced) {
+  int splits = 1;
+  if (!ws || nk < 16) return splits;
+  if (forced > 0) splits = forced;
+  else if (pp_considers_split(nblk)) {
+    // One resident block per CU.  Splitting K fills idle CUs but pays a second pass over `splits` f32 slabs of P x cout, which for
+    // the many-pixel layers of a SMALL batch costs more than it saves (64x64 level at 8 rows: 2 x 25 MB of slabs for a 10 us
+    // shorter K loop -- tools/conv_stamps.py).  Estimated microseconds, from the in-kernel stamps: ~5 us of prologue + epilogue,
+    // ~1.05 us per K tile (two ~1050-cycle segments), reduce = ~3 us + slab bytes at ~4 MB/us.
+    const int nchunk = nk / 9;
+    double best = 1e30;
+    for (int s_ = 1; s_ <= 8 && s_ <= nchunk; ++s_) {
+      const int cps = (nchunk + s_ - 1) / s_, se = (nchunk + cps - 1) / cps;
+      if (se != s_ || nblk * se > 256) continue;
+      double t = 5.0 + cps * 9 * (x3 ? 1.4 : 1.05);          // (split precision: 72 MFMAs per tile and wave instead of 48)
+      if (se > 1) t += 3.0 + (se + 0.5) * slab / 4.0e6;
+      if (t < best) { best = t; splits = se; }
+    }
   }
+  if (splits > 8) splits = 8;
+  if (forced > 0 && splits > nk / 8) splits = nk / 8;
+  if (splits > nk / 9) splits = nk / 9;
+  while (splits > 1 && (long long)splits * (long long)slab > ws_bytes) --splits;
+  if (splits < 1) splits = 1;
+  return splits;
 }
 
 // the shapes the ping-pong / halo kernel takes (and with it the fused GroupNorm apply)
@@ -1853,14 +1788,12 @@ bool conv_pp_eligible(int dtype, int ksize, int cout, int c1, int c2, int n, int
          (c1 % 64 == 0) && (c2 % 64 == 0);
 }
 
-// Which kernel a launch takes: 0 = conv_igemm_kernel (4 waves), 6 / 4 = conv_pp_kernel with 192- / 128-cout blocks.  One rule for
-// conv_dispatch and for dts_conv_kernel (what bench.py attributes its per-launch times to).
+// Which kernel a launch takes: 0 = conv_igemm_kernel, 6 / 4 = conv_pp_kernel with 192- / 128-cout blocks.
 // Measured (tools/conv_bench.py --variants, profiles/r02_conv_variants.txt): 3x3 layers +3..11 %, 1x1 layers -10..15 % (their 6-12 K
 // tiles do not amortise the exposed prologue/epilogue of a one-block-per-CU kernel): 3x3 only.  With a residual input the epilogue's
 // residual fetch is exposed in the ping-pong kernel (no early fetch): short-K layers (cin < 384) then lose 2-3 % to the 4-wave kernel.
-int conv_pick_pp(bool f32, const ConvP& p, bool x3 = false) {
-  const int variant = dts_knob_get(DTS_KNOB_CONV_VARIANT);      // 1 = ping-pong wherever it applies, 0 = never, unset = by shape
-  if (f32 || variant == 0 || dts_knob_get(DTS_KNOB_CONV_TILE) > 0) return 0;
+int conv_pick_pp(const ConvKnobs& k, bool f32, const ConvP& p, bool x3) {
+  if (f32 || k.variant == 0 || k.tile > 0) return 0;
   // 3x3 only.  The kernel's 1x1 form (TAPS = 1) was 5-20 % slower than the 4-wave kernel on every 1x1 layer, and with more than one
   // channel chunk it had a landing race: a 1x1 chunk is ONE tile, so the other group's pieces of the next halo are issued one segment
   // before they are read, but only waited for at the end of that group's COMPUTE, a segment later (3x3 issues them >= 3 segments
@@ -1869,10 +1802,10 @@ int conv_pick_pp(bool f32, const ConvP& p, bool x3 = false) {
   const int mt = p.cout % 192 == 0 ? 6 : (p.cout % 128 == 0 ? 4 : 0);
   // square power-of-two images of 16..., whole 256-pixel tiles, 32-bit lane offsets, no fused upsample (cout passed as 192: the
   // divisibility is handled here)
-  if (mt == 0 || !conv_pp_eligible(DTS_BF16, p.taps == 9 ? 3 : 1, 192, p.c1, p.c2, p.n, p.hin, p.win, p.up)) return 0;
+  if (mt == 0 || !conv_pp_eligible(DTS_BF16, 3, 192, p.c1, p.c2, p.n, p.hin, p.win, p.up)) return 0;
   if ((long long)p.cout * p.taps * p.cin * 2 >= (1ll << 31)) return 0;
-  if (p.gn_coef != nullptr) return (mt == 6 && !p.up) ? 6 : 0;   // dts_conv2d has checked dts_conv_fuses_gn
-  if (variant >= 1) return mt;                                   // forced (1) or a timing-only diagnostic build (11/21/41/51)
+  if (p.gn_coef != nullptr) return (mt == 6 && !p.up) ? 6 : 0;   // (conv_plan refuses the call unless fuses_gn)
+  if (k.variant >= 1) return mt;                                 // forced (1) or a timing-only diagnostic build (11/21/41/51)
   const long long blocks_pp = (long long)(p.cout / (32 * mt)) * ((p.P + 255) / 256);
   // a short-K layer whose ping-pong grid fills at most half the chip (64x64 level, 192 -> 192, at the 8 rows per forward of a sharded
   // search: 128 blocks of 27 tiles) is faster on the 8-wave implicit-GEMM kernel, whose 192 x 128 tiles give twice the blocks and need no
@@ -1884,62 +1817,58 @@ int conv_pick_pp(bool f32, const ConvP& p, bool x3 = false) {
   // (their neighbours keep the operands of the ping-pong form warm; profiles/r03_small_batch_experiments.txt item 9c).
   // NOT in the split-precision mode: with three MFMAs per staged K step the ping-pong form's half round (+ its K split) beats the
   // 128 x 128 implicit-GEMM grid there -- DDPM++-32 rejection step 9.07 -> 8.82 ms, same box, alternating (profiles/r05_experiments.txt item 16).
-  const int hr_knob = dts_knob_get(DTS_KNOB_CONV_HALF_ROUND);     // unset: by mode; 1 / 0 force the rule on / off (A/B aid)
-  const bool half_round_128 = mt == 4 && blocks_pp > 64 && blocks_pp <= 128 && p.wout >= 32 && p.cout <= 256 && (x3 ? hr_knob == 1 : hr_knob != 0);
-  const bool auto_pp = p.taps == 9 && !short_small && !half_round_128;     // (round 2 excluded residual layers with cin < 384: since the COMPUTE-side trims of round 3 the ping-pong kernel wins there too, profiles/r03_conv_variants.txt)
+  const bool half_round_128 = mt == 4 && blocks_pp > 64 && blocks_pp <= 128 && p.wout >= 32 && p.cout <= 256 && (x3 ? k.half_round == 1 : k.half_round != 0);
+  const bool auto_pp = !short_small && !half_round_128;     // (round 2 excluded residual layers with cin < 384: since the COMPUTE-side trims of round 3 the ping-pong kernel wins there too, profiles/r03_conv_variants.txt)
   return (auto_pp && blocks_pp >= 64) ? mt : 0;
 }
 
-template <typename T, typename OT = T>
-int conv_dispatch(const ConvP& p, hipStream_t st, float* ws, long long ws_bytes, ConvCall& call) {
-  const int g_tile_override = dts_knob_get(DTS_KNOB_CONV_TILE);     // DTS_CONV_TILE=64|128|192 (tuning aid; only honoured when it divides cout)
-  int tile = (p.cout % 192 == 0) ? 192 : (p.cout % 128 == 0 ? 128 : 64);    // measured: tools/conv_bench.py
-  // f32 (parity mode): the 192-cout tile spilled until round 4 (its epilogue held 96 residual registers beside 96 accumulators; the residual
-  // slices now come two at a time: 204-220 VGPRs, no scratch).  DTS_F32_TILE192=0 restores the smaller tile (A/B aid).
-  static const bool f32_192 = !(getenv("DTS_F32_TILE192") && atoi(getenv("DTS_F32_TILE192")) == 0);
-  if (std::is_same<T, float>::value && tile == 192 && !f32_192) tile = (p.cout % 128 == 0) ? 128 : 64;
-  const int pp = conv_pick_pp(std::is_same<T, float>::value, p, !std::is_same<T, OT>::value);
-  if constexpr (!std::is_same<T, OT>::value) {       // split-precision mode: the two shipped ping-pong forms and the implicit-GEMM forms, no knob variants
-    if (p.sk_w != nullptr) {                         // dts_conv2d has checked dts_conv_folds_skip
-      if (pp == 6) return launch_conv_pp<T, 9, 0, false, 6, OT, true>(p, st, ws, ws_bytes, call);
-      if (pp == 4) return launch_conv_pp<T, 9, 0, false, 4, OT, true>(p, st, ws, ws_bytes, call);
-      return DTS_ERR_UNSUPPORTED;
-    }
-    if (pp == 6) return launch_conv_pp<T, 9, 0, false, 6, OT>(p, st, ws, ws_bytes, call);
-    if (pp == 4) return launch_conv_pp<T, 9, 0, false, 4, OT>(p, st, ws, ws_bytes, call);
-    if (g_tile_override > 0 && p.cout % g_tile_override == 0) tile = g_tile_override;
-    if (p.taps == 9) return conv_dispatch_tile<T, true, OT>(p, tile, st, ws, ws_bytes, call);
-    return conv_dispatch_tile<T, false, OT>(p, tile, st, ws, ws_bytes, call);
-  }
-  if (pp == 6) {
-    const int variant = dts_knob_get(DTS_KNOB_CONV_VARIANT);
-#define DTS_PP(DBG_) launch_conv_pp<T, 9, DBG_>(p, st, ws, ws_bytes, call)
-    if (p.gn_coef != nullptr) return launch_conv_pp<T, 9, 0, true>(p, st, ws, ws_bytes, call);
-#ifdef DTS_DIAG_KERNELS      // diagnostic builds only (tools/conv_stamps.py --diag): 11/21/41/51 are TIMING-ONLY (outputs wrong by construction)
-    if (variant == 11) return DTS_PP(1);
-    if (variant == 21) return DTS_PP(2);
-    if (variant == 41) return DTS_PP(4);
-    if (variant == 51) return DTS_PP(5);
-    if (variant == 61) return DTS_PP(6);     // LOAD-order A/B builds (correct outputs)
-    if (variant == 71) return DTS_PP(7);
-    if (variant == 81) return DTS_PP(8);     // weight pieces split between LOAD and COMPUTE (measured slower)
+// DTS_CONV_VARIANT -> the DBG form of conv_pp_kernel; -1: a form this library was built without.  Diagnostic builds only (tools/conv_stamps.py
+// --diag): 11/21/41/51 are TIMING-ONLY (outputs wrong by construction); 61/71: LOAD-order A/B builds (correct outputs); 81: weight pieces split
+// between LOAD and COMPUTE, 91: second-half weight fragments read inside COMPUTE (both measured slower, profiles/r03_conv_variants.txt)
+int conv_pp_dbg(int variant) {
+  if (variant <= 1) return 0;
+#ifdef DTS_DIAG_KERNELS
+  const int d = variant / 10;
+  return (variant % 10 == 1 && d >= 1 && d <= 9 && d != 3) ? d : 0;
 #else
-    if (variant == 91) return DTS_PP(9);     // EXPERIMENT: second-half weight fragments read inside COMPUTE
-    if (variant > 1) {
-      dts_set_error("dts_conv2d: DTS_CONV_VARIANT=%d selects a diagnostic kernel that this library was built without (-DDTS_DIAG_KERNELS)", variant);
-      return DTS_ERR_ARG;
-    }
+  return -1;
 #endif
-    return DTS_PP(0);
+}
+
+// the one switch from a plan to a kernel instantiation.  Only what the plan can name is instantiated: the ping-pong kernel for 16-bit
+// operands, 3x3 (its TAPS == 1 form has a landing race, see conv_pick_pp, and must not be launched); GN and the diagnostic forms with
+// 16-bit outputs and 192-cout blocks, SK in split precision.
+template <typename T, typename OT = T>
+int conv_launch_plan(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
+  if constexpr (sizeof(T) == 2) {
+#define DTS_PP(DBG_, GN_, MT_, SK_) conv_launch<&conv_pp_kernel<T, 9, DBG_, GN_, MT_, OT, SK_>>(pl, q, call)
+    if constexpr (!std::is_same<T, OT>::value) {
+      if (pl.kernel == 6 && pl.sk) return DTS_PP(0, false, 6, true);
+      if (pl.kernel == 4 && pl.sk) return DTS_PP(0, false, 4, true);
+    } else if (pl.kernel == 6) {
+      if (pl.gn) return DTS_PP(0, true, 6, false);
+#ifdef DTS_DIAG_KERNELS
+      switch (pl.dbg) {
+        case 1: return DTS_PP(1, false, 6, false);
+        case 2: return DTS_PP(2, false, 6, false);
+        case 4: return DTS_PP(4, false, 6, false);
+        case 5: return DTS_PP(5, false, 6, false);
+        case 6: return DTS_PP(6, false, 6, false);
+        case 7: return DTS_PP(7, false, 6, false);
+        case 8: return DTS_PP(8, false, 6, false);
+        case 9: return DTS_PP(9, false, 6, false);
+      }
+#endif
+    }
+    if (pl.kernel == 6) return DTS_PP(0, false, 6, false);
+    if (pl.kernel == 4) return DTS_PP(0, false, 4, false);      // 128-cout blocks: the widths that are no multiple of 192 (classifier 128/256/512, SD VAE 128/256/512)
 #undef DTS_PP
   }
-  if (pp == 4)     // 128-cout blocks: the widths that are no multiple of 192 (classifier 128/256/512, SD VAE 128/256/512)
-    return launch_conv_pp<T, 9, 0, false, 4>(p, st, ws, ws_bytes, call);
-  if (g_tile_override > 0 && p.cout % g_tile_override == 0) tile = g_tile_override;
-  // fragment prefetch pays on the long K loops of the 3x3 layers; f32 (parity mode) keeps the lean order: its 192-cout
-  // tile is already at the 256-VGPR limit
-  if (p.taps == 9 && !std::is_same<T, float>::value) return conv_dispatch_tile<T, true>(p, tile, st, ws, ws_bytes, call);
-  return conv_dispatch_tile<T, false>(p, tile, st, ws, ws_bytes, call);
+  switch (pl.tile) {
+    case 192: return pl.pf ? conv_launch_igemm<T, OT, 6, 2, 2, true>(pl, q, call) : conv_launch_igemm<T, OT, 6, 2, 2, false>(pl, q, call);
+    case 128: return pl.pf ? conv_launch_igemm<T, OT, 4, 2, 2, true>(pl, q, call) : conv_launch_igemm<T, OT, 4, 2, 2, false>(pl, q, call);
+    default: return pl.pf ? conv_launch_igemm<T, OT, 4, 1, 4, true>(pl, q, call) : conv_launch_igemm<T, OT, 4, 1, 4, false>(pl, q, call);
+  }
 }
 
 // the shape part of ConvP from the C arguments (what the kernel choice depends on)
@@ -1950,6 +1879,115 @@ void conv_shape_from_args(const dts_conv_args* a, ConvP& p) {
   p.cout = a->cout; p.taps = a->ksize * a->ksize; p.up = a->up;
   p.P = (int)((long long)p.n * p.hout * p.wout);
   p.residual = (const char*)a->residual; p.gn_coef = a->gn_coef;
+  p.out_split2 = a->out_split2;
+}
+
+ConvPlan conv_plan(const dts_conv_args* a) {
+  ConvPlan pl{};
+  pl.kernel = -1; pl.splits = 1;
+  auto refuse = [&](const char* fmt, int v0 = 0, int v1 = 0, int v2 = 0) { pl.refused = 1; snprintf(pl.refuse, sizeof(pl.refuse), fmt, v0, v1, v2); return pl; };
+  if (a == nullptr) return refuse("dts_conv2d: null args");
+  const ConvKnobs k = conv_knobs();
+  const bool f32 = a->dtype == DTS_F32, x3 = a->dtype == DTS_F16X3;
+  // the fused GroupNorm apply is the 192-cout ping-pong form's, without upsample; the grid rule of conv_pick_pp, without its exceptions
+  // (with gn_coef the kernel choice does not depend on the residual)
+  pl.fuses_gn = a->ksize == 3 && k.variant != 0 && k.tile <= 0 && !a->up &&
+                conv_pp_eligible(a->dtype, a->ksize, a->cout, a->c1, a->c2, a->n, a->hin, a->win, a->up) &&
+                (k.variant == 1 || (long long)(a->cout / 192) * (((long long)a->n * a->hin * a->win + 255) / 256) >= 64);
+  // (these leave kernel = -1: what dts_conv_kernel calls invalid arguments)
+  if (a->ksize != 1 && a->ksize != 3) return refuse("dts_conv2d: ksize %d", a->ksize);
+  if (a->n <= 0 || a->hin <= 0 || a->win <= 0) return refuse("dts_conv2d: bad shape");
+  if (a->cout <= 0) return refuse("dts_conv2d: cout %d must be a multiple of 64", a->cout);
+  if ((long long)a->n * a->hin * a->win * (a->up ? 4 : 1) >= (1ll << 30)) return refuse("dts_conv2d: too many pixels");
+  ConvP p;
+  conv_shape_from_args(a, p);
+  const int mt = conv_pick_pp(k, f32, p, x3);
+  pl.kernel = mt;
+  // ---- grid and K loop
+  int unit = 1;                                              // K steps that stay together in a split
+  if (mt != 0) {
+    pl.n_ct = p.cout / (32 * mt); pl.n_pt = (p.P + 255) / 256;
+    pl.threads = 512;
+    pl.lds_bytes = (6 * 16 * mt + 2 * 328) * 128;                  // A: 2 groups x 3 slots x 16*MT rows; halo: 2 buffers x 328 rows
+    unit = 9;                                                // every split a whole number of channel chunks (9 tiles each)
+  } else {
+    pl.tile = (p.cout % 192 == 0) ? 192 : (p.cout % 128 == 0 ? 128 : 64);    // measured: tools/conv_bench.py
+    // f32 (parity mode): the 192-cout tile spilled until round 4 (its epilogue held 96 residual registers beside 96 accumulators; the residual
+    // slices now come two at a time: 204-220 VGPRs, no scratch).
+    if (f32 && pl.tile == 192 && !k.f32_tile192) pl.tile = (p.cout % 128 == 0) ? 128 : 64;
+    if (k.tile > 0 && p.cout % k.tile == 0) pl.tile = (k.tile == 192 || k.tile == 128) ? k.tile : 64;
+    pl.n_ct = p.cout / pl.tile; pl.n_pt = (p.P + (pl.tile == 64 ? 255 : 127)) / (pl.tile == 64 ? 256 : 128);      // 64 x 256, 128 x 128, 192 x 128
+    // fragment prefetch pays on the long K loops of the 3x3 layers; f32 (parity mode) keeps the lean order: its 192-cout
+    // tile is already at the 256-VGPR limit
+    pl.pf = p.taps == 9 && !f32;
+  }
+  pl.nblk = pl.n_ct * pl.n_pt;
+  const int bke = f32 ? 32 : 64, nk = p.taps * (p.cin / bke);
+  // ---- fused input GroupNorm, folded skip convolution
+  pl.gn = a->gn_coef != nullptr;
+  {
+    const int su = a->skip_up ? 1 : 0;
+    // forced ping-pong (DTS_CONV_VARIANT=1): any grid folds, unsplit -- the tests' small shapes
+    pl.folds_skip = x3 && mt != 0 && !a->up && a->residual == nullptr && !a->out_split2 && a->gn_coef == nullptr &&
+                    a->skip_c > 0 && a->skip_c % 64 == 0 && k.skip_fold != 0 && k.splits <= 0 && !(su && ((a->hin | a->win) & 1)) &&
+                    (!pp_considers_split(pl.nblk) || k.variant == 1) &&
+                    (long long)a->n * (a->hin >> su) * (a->win >> su) * a->skip_c * 2 < (1ll << 31) && (long long)a->cout * a->skip_c * 2 < (1ll << 31);
+  }
+  // ---- what dts_conv2d refuses (the queries above answer for any shape)
+  if (a->cout % 64 != 0) return refuse("dts_conv2d: cout %d must be a multiple of 64", a->cout);
+  if (a->c1 <= 0 || a->c1 % bke != 0 || a->c2 % bke != 0) return refuse("dts_conv2d: channels (%d,%d) must be multiples of %d", a->c1, a->c2, bke);
+  // out-of-image rows are read from g_zero16 with a pointer that advances along K like a real row: it must stay inside the page
+  if ((long long)p.cin * (f32 ? 4 : 2) + 128 > (long long)sizeof(g_zero16))
+    return refuse("dts_conv2d: %d input channels exceed the zero-row page (%d bytes)", p.cin, (int)sizeof(g_zero16));
+  if (p.hout >= 32768 || p.wout >= 32768) return refuse("dts_conv2d: spatial size too large");
+  if (a->out_split2 && !(x3 && a->stats_out == nullptr)) return refuse("dts_conv2d: out_split2 is the split-precision mode's, without strip statistics");
+  if (a->acc_scale != 0.f && a->acc_scale != 1.f && !x3) return refuse("dts_conv2d: acc_scale is the split-precision mode's (DTS_F16X3)");
+  if (pl.gn && !pl.fuses_gn) return refuse("dts_conv2d: gn_coef given for a launch that cannot fuse the GroupNorm apply (ask dts_conv_fuses_gn first)");
+  if (a->skip_c != 0 || a->skip_w != nullptr || a->skip_x != nullptr) {
+    if (a->skip_w == nullptr || a->skip_x == nullptr || !pl.folds_skip)
+      return refuse("dts_conv2d: skip_* given for a launch that cannot fold the 1x1 skip convolution (ask dts_conv_folds_skip first)");
+    pl.sk = true;
+  }
+  if (pl.gn && x3) return refuse("dts_conv2d: gn_coef is not available in the split-precision mode");
+  if (a->dtype < DTS_F32 || a->dtype > DTS_F16X3) return refuse("bad dtype %d", a->dtype);
+  if (mt == 6 && !x3 && !pl.gn) {                            // (the diagnostic forms exist for the plain 192-cout 16-bit launch only)
+    pl.dbg = conv_pp_dbg(k.variant);
+    if (pl.dbg < 0) return refuse("dts_conv2d: DTS_CONV_VARIANT=%d selects a diagnostic kernel that this library was built without (-DDTS_DIAG_KERNELS)", k.variant);
+  }
+  // ---- K split: `splits` f32 partial slabs in the workspace + the reduce pass.  Not with the split-image output (written by the conv
+  // epilogue only) and not under a folded skip (its second K loop needs the complete accumulators)
+  const bool ws = a->workspace != nullptr && !a->out_split2 && !pl.sk;
+  const double slab = (double)p.P * p.cout * 4.0;
+  pl.splits = mt != 0 ? pp_splits(pl.nblk, nk, slab, x3, ws, (long long)a->workspace_bytes, k.splits)
+                      : igemm_splits(pl.nblk, nk, slab, !f32, x3, ws, (long long)a->workspace_bytes, k.splits);
+  {
+    const int nunit = nk / unit, per = (nunit + pl.splits - 1) / pl.splits;
+    pl.ks_per_split = per * unit;
+    pl.splits = (nunit + per - 1) / per;                     // no empty split
+  }
+  // statistics come from the fused epilogue (whole launches, 64-pixel wave strips) or, under split-K, from the reduce pass
+  pl.stats_in_kernel = a->stats_out != nullptr && pl.splits == 1;
+  pl.stats_in_reduce = a->stats_out != nullptr && pl.splits > 1 && (p.hout * p.wout) % 64 == 0 && p.cout % 4 == 0;
+  pl.stats_written = pl.stats_in_kernel || pl.stats_in_reduce;
+  // the row-layout f32 epilogue: the split-precision mode's default; the f32 parity mode keeps the accumulator-layout epilogue (the mode is the
+  // REFERENCE the others are compared with: its summation orders stay what rounds 2-4 validated against the CPU oracle) unless DTS_CONV_EPI32=1
+  pl.epi_rows = k.epi32 < 0 ? (x3 ? 1 : 0) : (k.epi32 == 2 ? 2 : (k.epi32 != 0));
+  if (mt != 0) return pl;
+  // ---- conv_igemm_kernel: ring depth and waves
+  const bool one_per_cu = (long long)pl.nblk * pl.splits <= 256;
+  // ring depth: a grid of at most one block per CU cannot hide a tile's round trip behind a co-resident block, so it keeps two
+  // tiles in flight (3 stages)
+  pl.stages = (one_per_cu && pl.ks_per_split >= 3) ? 3 : 2;
+  if (k.stages >= 2 && k.stages <= 4) pl.stages = k.stages;
+  if (f32) pl.stages = 2;                                    // parity mode: one configuration
+  const int stage_bytes = (pl.tile + (pl.tile == 64 ? 256 : 128)) * 128;
+  if (pl.stages * stage_bytes > 160 * 1024) pl.stages = 3;
+  // 8 waves per block (the same tile, half the couts per wave) when the grid leaves one block per CU; 16-bit operands only
+  pl.waves = (!f32 && (k.waves == 8 || (k.waves != 4 && one_per_cu))) ? 8 : 4;
+  if (pl.stages == 4 && (pl.waves == 8 || x3)) pl.stages = 3;      // (the 4-deep ring exists for the A/B knob only: 4 waves, 16-bit outputs)
+  pl.threads = 64 * pl.waves;
+  pl.lds_bytes = pl.stages * stage_bytes;
+  return pl;
 }
 
 }  // namespace
@@ -1970,106 +2008,61 @@ extern "C" int dts_debug_read_segments(unsigned long long* host, int count) {
 }
 #endif
 
-extern "C" int dts_conv_kernel(const dts_conv_args* a) {
-  if (a == nullptr || (a->ksize != 1 && a->ksize != 3) || a->n <= 0 || a->hin <= 0 || a->win <= 0 || a->cout <= 0) return -1;
-  if ((long long)a->n * a->hin * a->win * (a->up ? 4 : 1) >= (1ll << 30)) return -1;
-  ConvP p;
-  conv_shape_from_args(a, p);
-  return conv_pick_pp(a->dtype == DTS_F32, p, a->dtype == DTS_F16X3);
-}
+extern "C" int dts_conv_kernel(const dts_conv_args* a) { return conv_plan(a).kernel; }
 
-extern "C" int dts_conv_fuses_gn(const dts_conv_args* a) {
-  if (a == nullptr || a->ksize != 3) return 0;
-  const int variant = dts_knob_get(DTS_KNOB_CONV_VARIANT);
-  if (variant == 0 || dts_knob_get(DTS_KNOB_CONV_TILE) > 0) return 0;
-  if (a->up || !conv_pp_eligible(a->dtype, a->ksize, a->cout, a->c1, a->c2, a->n, a->hin, a->win, a->up)) return 0;
-  const long long blocks_pp = (long long)(a->cout / 192) * (((long long)a->n * a->hin * a->win + 255) / 256);
-  return (variant == 1 || blocks_pp >= 64) ? 1 : 0;              // with gn_coef the kernel choice does not depend on the residual
-}
+extern "C" int dts_conv_fuses_gn(const dts_conv_args* a) { return conv_plan(a).fuses_gn ? 1 : 0; }
 
-extern "C" int dts_conv_folds_skip(const dts_conv_args* a) {
-  if (a == nullptr || a->dtype != DTS_F16X3 || a->ksize != 3 || a->up || a->residual != nullptr || a->out_split2 || a->gn_coef != nullptr) return 0;
-  if (a->skip_c <= 0 || a->skip_c % 64 != 0 || a->n <= 0 || a->hin <= 0 || a->win <= 0 || a->cout <= 0) return 0;
-  if (dts_knob_get(DTS_KNOB_CONV_SKIP_FOLD) == 0 || dts_knob_get(DTS_KNOB_CONV_SPLITS) > 0) return 0;
-  if ((long long)a->n * a->hin * a->win >= (1ll << 30)) return 0;
-  if (a->skip_up && ((a->hin | a->win) & 1)) return 0;
-  ConvP p;
-  conv_shape_from_args(a, p);
-  const int mt = conv_pick_pp(false, p, true);
-  if (mt == 0) return 0;
-  const long long nblk = (long long)(p.cout / (32 * mt)) * ((p.P + 255) / 256);
-  // a grid below 192 blocks would take a K split (launch_conv_pp), which the fold excludes: there the separate 1x1 launch stays.  (Forced
-  // ping-pong, DTS_CONV_VARIANT=1: any grid folds, unsplit -- the tests' small shapes.)
-  if (nblk < 192 && dts_knob_get(DTS_KNOB_CONV_VARIANT) != 1) return 0;
-  const long long px = (long long)a->n * (a->hin >> (a->skip_up ? 1 : 0)) * (a->win >> (a->skip_up ? 1 : 0));
-  return (px * a->skip_c * 2 < (1ll << 31) && (long long)a->cout * a->skip_c * 2 < (1ll << 31)) ? 1 : 0;
+// (the fold is the ping-pong kernel's, for grids that do not weigh a K split: pp_considers_split, the rule pp_splits itself uses)
+extern "C" int dts_conv_folds_skip(const dts_conv_args* a) { return conv_plan(a).folds_skip ? 1 : 0; }
+
+extern "C" int dts_conv_plan(const dts_conv_args* a, dts_conv_plan_info* out) {
+  DTS_CHECK_ARG(out != nullptr, "dts_conv_plan: null output");
+  const ConvPlan pl = conv_plan(a);
+  *out = pl;
+  if (pl.refused) dts_set_error("%s", pl.refuse);
+  return pl.kernel < 0 ? DTS_ERR_ARG : DTS_OK;
 }
 
 extern "C" int dts_conv2d(dts_conv_args* a, dts_stream s) {
-  DTS_CHECK_ARG(a != nullptr, "dts_conv2d: null args");
+  const ConvPlan pl = conv_plan(a);                          // (with every check that needs no pointer)
+  DTS_CHECK_ARG(!pl.refused, "%s", pl.refuse);
   DTS_CHECK_ARG(a->x1 && a->w && a->out, "dts_conv2d: null tensor");
-  DTS_CHECK_ARG(a->ksize == 1 || a->ksize == 3, "dts_conv2d: ksize %d", a->ksize);
-  DTS_CHECK_ARG(a->n > 0 && a->hin > 0 && a->win > 0, "dts_conv2d: bad shape");
-  DTS_CHECK_ARG(a->cout > 0 && a->cout % 64 == 0, "dts_conv2d: cout %d must be a multiple of 64", a->cout);
   DTS_CHECK_ARG(a->c2 == 0 || a->x2 != nullptr, "dts_conv2d: c2 without x2");
-  const int bke = (a->dtype == DTS_F32) ? 32 : 64;
-  DTS_CHECK_ARG(a->c1 > 0 && a->c1 % bke == 0 && a->c2 % bke == 0, "dts_conv2d: channels (%d,%d) must be multiples of %d",
-                a->c1, a->c2, bke);
   DTS_CHECK_ARG(a->bias_nc == nullptr || a->ld_bias_nc >= a->cout, "dts_conv2d: ld_bias_nc");
-  // out-of-image rows are read from g_zero16 with a pointer that advances along K like a real row: it must stay inside the page
-  DTS_CHECK_ARG((long long)(a->c1 + a->c2) * (a->dtype == DTS_F32 ? 4 : 2) + 128 <= (long long)sizeof(g_zero16),
-                "dts_conv2d: %d input channels exceed the zero-row page (%d bytes)", a->c1 + a->c2, (int)sizeof(g_zero16));
   ConvP p;
+  conv_shape_from_args(a, p);
+  DTS_CHECK_ARG(a->stats_out == nullptr || ((p.hout * p.wout) % 64 == 0 && (uintptr_t)a->stats_out % 16 == 0),
+                "dts_conv2d: strip statistics need hout*wout to be a multiple of 64 and a 16-byte aligned buffer");
+  DTS_CHECK_ARG(a->workspace == nullptr || ((uintptr_t)a->workspace % 16 == 0 && a->workspace_bytes >= 0), "dts_conv2d: workspace");
   p.x1 = (const char*)a->x1; p.x2 = (const char*)a->x2; p.w = (const char*)a->w;
-  p.bias = a->bias; p.bias_nc = (const char*)a->bias_nc; p.residual = (const char*)a->residual; p.out = (char*)a->out;
-  p.c1 = a->c1; p.c2 = a->c2; p.cin = a->c1 + a->c2; p.ld_bias_nc = a->ld_bias_nc;
-  p.n = a->n; p.hin = a->hin; p.win = a->win;
-  p.hout = a->up ? 2 * a->hin : a->hin; p.wout = a->up ? 2 * a->win : a->win;
-  DTS_CHECK_ARG(p.hout < 32768 && p.wout < 32768, "dts_conv2d: spatial size too large");
-  p.cout = a->cout; p.taps = a->ksize * a->ksize; p.up = a->up;
-  const long long P = (long long)p.n * p.hout * p.wout;
-  DTS_CHECK_ARG(P < (1ll << 30), "dts_conv2d: too many pixels");
-  p.P = (int)P; p.out_scale = a->out_scale; p.acc_scale = a->acc_scale == 0.f ? 1.f : a->acc_scale; p.n_ct = p.n_pt = 0;
-  p.out_split2 = a->out_split2;
-  DTS_CHECK_ARG(!a->out_split2 || (a->dtype == DTS_F16X3 && a->stats_out == nullptr), "dts_conv2d: out_split2 is the split-precision mode's, without strip statistics");
-  p.splits = 1; p.ks_per_split = 0; p.partial = nullptr;
+  p.bias = a->bias; p.bias_nc = (const char*)a->bias_nc; p.out = (char*)a->out;
+  p.ld_bias_nc = a->ld_bias_nc;
+  p.out_scale = a->out_scale; p.acc_scale = a->acc_scale == 0.f ? 1.f : a->acc_scale;
   p.w_shift = p.hw_shift = -1;
   {
     const int hw = p.hout * p.wout;
     if ((p.wout & (p.wout - 1)) == 0 && (hw & (hw - 1)) == 0) { p.w_shift = __builtin_ctz(p.wout); p.hw_shift = __builtin_ctz(hw); }
   }
-  p.gn_coef = a->gn_coef; p.gn_silu = a->gn_silu;
-  {   // the row-layout f32 epilogue: the split-precision mode's default; the f32 parity mode keeps the accumulator-layout epilogue (the mode is the
-      // REFERENCE the others are compared with: its summation orders stay what rounds 2-4 validated against the CPU oracle) unless DTS_CONV_EPI32=1
-    const int k_ = dts_knob_get(DTS_KNOB_CONV_EPI32);
-    p.epi_rows = k_ < 0 ? (a->dtype == DTS_F16X3 ? 1 : 0) : (k_ == 2 ? 2 : (k_ != 0));
-  }
-  DTS_CHECK_ARG(a->gn_coef == nullptr || dts_conv_fuses_gn(a), "dts_conv2d: gn_coef given for a launch that cannot fuse the GroupNorm apply "
-                "(ask dts_conv_fuses_gn first)");
+  p.gn_silu = a->gn_silu;
   p.sk_x = p.sk_w = nullptr; p.sk_c = p.sk_up = 0; p.sk_ratio = 1.f;
-  if (a->skip_c != 0 || a->skip_w != nullptr || a->skip_x != nullptr) {
-    DTS_CHECK_ARG(a->skip_w != nullptr && a->skip_x != nullptr && dts_conv_folds_skip(a), "dts_conv2d: skip_* given for a launch that cannot fold the 1x1 "
-                  "skip convolution (ask dts_conv_folds_skip first)");
+  if (pl.sk) {
     const float ss = a->skip_acc_scale == 0.f ? 1.f : a->skip_acc_scale;
     p.sk_x = (const char*)a->skip_x; p.sk_w = (const char*)a->skip_w; p.sk_c = a->skip_c; p.sk_up = a->skip_up ? 1 : 0;
     p.sk_ratio = p.acc_scale / ss; p.acc_scale = ss;
   }
-  p.stats = a->stats_out;
-  DTS_CHECK_ARG(a->stats_out == nullptr || ((p.hout * p.wout) % 64 == 0 && (uintptr_t)a->stats_out % 16 == 0),
-                "dts_conv2d: strip statistics need hout*wout to be a multiple of 64 and a 16-byte aligned buffer");
-  DTS_CHECK_ARG(a->workspace == nullptr || ((uintptr_t)a->workspace % 16 == 0 && a->workspace_bytes >= 0), "dts_conv2d: workspace");
-  hipStream_t st = to_stream(s);
-  int rc = DTS_OK;
+  p.n_ct = pl.n_ct; p.n_pt = pl.n_pt; p.splits = pl.splits; p.ks_per_split = pl.ks_per_split; p.epi_rows = pl.epi_rows;
+  p.partial = (float*)a->workspace;
+  p.stats = pl.stats_in_kernel ? a->stats_out : nullptr;
   ConvCall call;
-  call.ev_start = (hipEvent_t)a->ev_start; call.ev_stop = (hipEvent_t)a->ev_stop;
-  DTS_CHECK_ARG(p.acc_scale == 1.f || a->dtype == DTS_F16X3, "dts_conv2d: acc_scale is the split-precision mode's (DTS_F16X3)");
-  if (a->dtype == DTS_F16X3) {
-    // split precision: f16 operand planes on the 16-bit MFMA, f32 accumulate, f32 epilogue operands and output
-    DTS_CHECK_ARG(a->gn_coef == nullptr, "dts_conv2d: gn_coef is not available in the split-precision mode");
-    rc = conv_dispatch<f16_t, float>(p, st, (float*)a->workspace, (long long)a->workspace_bytes, call);
-  } else {
-    DTS_DISPATCH_DTYPE(a->dtype, rc = conv_dispatch<T>(p, st, (float*)a->workspace, (long long)a->workspace_bytes, call));
+  call.st = to_stream(s); call.ev_start = (hipEvent_t)a->ev_start; call.ev_stop = (hipEvent_t)a->ev_stop;
+  int rc = DTS_OK;
+  // split precision: f16 operand planes on the 16-bit MFMA, f32 accumulate, f32 epilogue operands and output
+  if (a->dtype == DTS_F16X3) rc = conv_launch_plan<f16_t, float>(pl, p, call);
+  else DTS_DISPATCH_DTYPE(a->dtype, rc = conv_launch_plan<T>(pl, p, call));
+  if (rc == DTS_OK && pl.splits > 1) {                       // the second pass of a split launch: fixed-order sum of the slabs + the epilogue
+    if (pl.stats_in_reduce) p.stats = a->stats_out;
+    DTS_DISPATCH_DTYPE(a->dtype == DTS_F16X3 ? DTS_F32 : a->dtype, rc = launch_reduce<T>(p, pl.stats_in_reduce, call.st));
   }
-  a->stats_written = call.stats_written ? 1 : 0;
+  a->stats_written = pl.stats_written ? 1 : 0;
   return rc;
 }

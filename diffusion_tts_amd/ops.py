@@ -232,14 +232,10 @@ def conv_folds_skip(x1, w, skip):
     return bool(L.load().dts_conv_folds_skip(C.byref(a)))
 
 
-def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, out_scale=1.0, out=None, gn_stats=False,
-           timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None):
-    """skip=(SplitAct, X3Weight, up): the block's 1x1 skip convolution of that operand accumulated by this launch (only where conv_folds_skip()
-    says so; `bias` is then the sum of the two layers' biases and there is no `residual`).
-    timing_events=(start, stop): raw hipEvent_t handles attached to the conv kernel's own dispatch (measurement only).
-    gn_stats=True: the epilogue also emits the GroupNorm moments of the output (per 64-pixel strip and channel); they
-    ride on the returned tensor as `out._gn_stats` (None when the launch could not produce them) and are consumed by
-    group_norm(), which then skips its own pass over the tensor."""
+def _conv2d_args(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, out_scale=1.0, out=None, gn_stats=False,
+                 timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None):
+    """the dts_conv_args of conv2d(...) (and of conv_plan(...): one builder, so the two cannot differ): (args, out, statistics buffer or None,
+    out_split2, tensors the arguments point into)"""
     n, hin, win, c1 = x1.shape
     c2 = 0 if x2 is None else x2.shape[-1]
     cout, kh, kw, cin = w.shape
@@ -256,7 +252,7 @@ def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, 
         out = torch.empty((n, ho, wo, 2 * cout), dtype=torch.float16, device=x1.device)
     elif out is None:
         out = torch.empty((n, ho, wo, cout), dtype=x1.dtype, device=x1.device)
-    a = L.ConvArgs()
+    a, xs = L.ConvArgs(), None
     a.out_split2 = int(out_split2)
     dt_in = x1.dtype
     if x3:      # the conv reads the f16 split image (per 32 channels hi | lo) of concat(x1, x2); epilogue operands and output stay float32
@@ -291,9 +287,33 @@ def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, 
         if tuple(gn_coef.shape) != (n, c1 + c2, 2):
             raise ValueError(f'conv2d: gn_coef shape {tuple(gn_coef.shape)} != {(n, c1 + c2, 2)}')
         a.gn_coef, a.gn_silu = _ptr(gn_coef, 'gn_coef', torch.float32), int(gn_silu)
+    return a, out, st, out_split2, (xs, ws)
+
+
+def conv_plan(*args, **kw):
+    """The launch plan of conv2d(same arguments) as a dict of dts_conv_plan_info's fields (kernel, tile, waves, stages, pf, gn, sk, dbg, splits,
+    ks_per_split, n_ct, n_pt, nblk, threads, lds_bytes, stats_in_kernel, stats_in_reduce, stats_written, epi_rows, fuses_gn, folds_skip,
+    refused): what the launcher derives, nothing is launched.  Test and measurement aid."""
+    a, *_keep = _conv2d_args(*args, **kw)
+    info = L.ConvPlanInfo()
+    _call('dts_conv_plan', C.byref(a), C.byref(info))
+    return {f: int(getattr(info, f)) for f, _ in L.ConvPlanInfo._fields_}
+
+
+def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, out_scale=1.0, out=None, gn_stats=False,
+           timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None):
+    """skip=(SplitAct, X3Weight, up): the block's 1x1 skip convolution of that operand accumulated by this launch (only where conv_folds_skip()
+    says so; `bias` is then the sum of the two layers' biases and there is no `residual`).
+    timing_events=(start, stop): raw hipEvent_t handles attached to the conv kernel's own dispatch (measurement only).
+    gn_stats=True: the epilogue also emits the GroupNorm moments of the output (per 64-pixel strip and channel); they
+    ride on the returned tensor as `out._gn_stats` (None when the launch could not produce them) and are consumed by
+    group_norm(), which then skips its own pass over the tensor."""
+    a, out, st, out_split2, _keep = _conv2d_args(x1, w, bias, x2=x2, bias_nc=bias_nc, residual=residual, up=up, out_scale=out_scale, out=out,
+                                                 gn_stats=gn_stats, timing_events=timing_events, gn_coef=gn_coef, gn_silu=gn_silu,
+                                                 out_split2=out_split2, skip=skip)
     _call('dts_conv2d', C.byref(a))
     if out_split2:
-        return SplitQKV(out, (n, ho, wo, cout))
+        return SplitQKV(out, (out.shape[0], out.shape[1], out.shape[2], out.shape[3] // 2))
     out._gn_stats = st if (st is not None and a.stats_written) else None
     return out
 

@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 118        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 119        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -54,11 +54,13 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      115: dts_jpeg_workspace_bytes, dts_jpeg_size (the compressibility scorer's JPEG byte length);
                                      116: dts_group_rows (the SD U-Net's distinct text contexts, grouped on the device);
                                      117: dts_attention_masked, dts_text_tokens (the CLIP text tower: SD's text encoder and the CLIP scorer's text side);
-                                     118: dts_layer_norm_x3, dts_gelu_x3, dts_patchify_x3, dts_vit_tokens_f32, dts_vit_head_f32 (the CLIP vision tower in DTS_F16X3)) */
+                                     118: dts_layer_norm_x3, dts_gelu_x3, dts_patchify_x3, dts_vit_tokens_f32, dts_vit_head_f32 (the CLIP vision tower in DTS_F16X3);
+                                     119: dts_conv_plan (the whole launch plan of a dts_conv2d call, as a query)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
- * timing-only diagnostic kernels exist only in builds made with -DDTS_DIAG_KERNELS and are refused by the product library).  knob: index of
+ * timing-only diagnostic kernels and the A/B experiments that lost (DTS_CONV_VARIANT = 11 .. 91) exist only in builds made with -DDTS_DIAG_KERNELS and are
+ * refused by the product library).  knob: index of
  * enum dts_knob in csrc/dts_common.h; value -1 = launcher default.  Used by tools/conv_bench.py and tools/att_bench.py to A/B variants in one process. */
 int dts_set_tuning(int knob, int value);
 int dts_get_tuning(int knob);
@@ -127,6 +129,24 @@ int dts_conv_folds_skip(const dts_conv_args* a);
  * implicit-GEMM kernel, 6 / 4 = the 8-wave ping-pong / halo kernel with 192- / 128-cout blocks, -1 = invalid arguments.  Measurement aid:
  * bench.py attributes its per-launch times and algorithmic bytes to the kernel name a trace will show. */
 int dts_conv_kernel(const dts_conv_args* a);
+/* The whole launch plan of dts_conv2d for these arguments, as the launcher itself derives it (host only: no GPU needed; the three queries
+ * above return fields of the same plan).  Reads the shape, the dtype, the tuning knobs and which of residual / gn_coef / skip_* /
+ * stats_out / out_split2 / workspace (+ workspace_bytes) are present; pointers are never dereferenced.  Returns DTS_ERR_ARG where
+ * dts_conv_kernel answers -1, else DTS_OK; `refused` = 1: dts_conv2d refuses the call (dts_last_error says why) and the fields after
+ * the first refusing rule are not filled.  Measurement and test aid. */
+typedef struct dts_conv_plan_info {
+  int32_t kernel;                         /* as dts_conv_kernel: 0 / 6 / 4, -1 = invalid arguments */
+  int32_t tile, waves, stages, pf;        /* conv_igemm_kernel: cout tile 64 | 128 | 192, waves 4 | 8, LDS ring depth 2 | 3 | 4, fragment prefetch; 0 otherwise */
+  int32_t gn, sk, dbg;                    /* conv_pp_kernel: fused GroupNorm apply, folded skip convolution, diagnostic form (0 in the product library) */
+  int32_t splits, ks_per_split;           /* K split (grid.y; > 1: f32 partial slabs + the reduce pass) and K steps per split */
+  int32_t n_ct, n_pt, nblk;               /* cout tiles, pixel tiles, grid.x = n_ct * n_pt */
+  int32_t threads, lds_bytes;             /* block size, dynamic LDS */
+  int32_t stats_in_kernel, stats_in_reduce, stats_written;      /* who writes stats_out; stats_written as dts_conv2d will report it */
+  int32_t epi_rows;                       /* f32 outputs: 1 / 2 = a row-layout epilogue, 0 = the accumulator-layout one */
+  int32_t fuses_gn, folds_skip;           /* as dts_conv_fuses_gn / dts_conv_folds_skip */
+  int32_t refused;
+} dts_conv_plan_info;
+int dts_conv_plan(const dts_conv_args* a, dts_conv_plan_info* out);
 int dts_conv2d(dts_conv_args* a, dts_stream s);      /* writes a->stats_written; no state is kept between calls (thread-safe) */
 
 /* first / last convolutions of the U-Nets (3 image channels; direct, not MFMA) */

@@ -329,7 +329,7 @@ def k_steps(case, mode):
 
 
 def effective_splits(case, mode):
-    """(splits, K steps per split) a forced-split launch ends up with -- the launchers' rules restated (launch_conv / launch_conv_pp).
+    """(splits, K steps per split) a forced-split launch ends up with -- the launch plan's rules restated (conv_plan with igemm_splits / pp_splits, conv_igemm.hip).
     conv_igemm_kernel: conv_splits = s is honoured (at most 8) when nk >= 2 s; each split takes ceil(nk / s) steps and empty splits are
     dropped.  conv_pp_kernel: s is cut to nk / 8 and to the number of chunks (a chunk = all nine taps of one granule); each split takes
     ceil(chunks / s) whole chunks."""

@@ -8,7 +8,8 @@ launch).  The output must EQUAL the reference; there is no tolerance in this leg
 every element must have been written and the guard bands on both sides must still be NaN.  Where the launch reports GroupNorm strip
 statistics they must equal the float64 moments of the stored output (per 64-pixel strip for the implicit-GEMM kernel and the reduce pass,
 per image for the ping-pong kernel, whose strips are patch rows); where it cannot, `_gn_stats` must be None.  Each case asserts
-ops.conv_kernel's answer, and forms the query cannot tell apart are forced with _lib.set_tuning (the old values put back whatever
+ops.conv_kernel's answer and the whole route of ops.conv_plan (tile, waves, ring depth, K split, who wrote the statistics:
+_assert_plan), and forms the queries cannot tell apart are forced with _lib.set_tuning (the old values put back whatever
 happens).  That includes the K split, which decides whether the kernel's own epilogue or the reduce pass writes the output: every case
 pins it (conv_splits = 1, or a forced split under its own name; two `auto_*` cases leave it to the launcher).  The route
 table -- which (kernel form) x (mode) cells exist and why the others do not -- is conv_reference.CASES / ABSENT.
@@ -127,6 +128,29 @@ def _guarded(shape, dtype):
     return buf, buf[GUARD:GUARD + numel].view(shape)
 
 
+def _assert_plan(case, mode, plan, stats_written):
+    """the whole route, not only the kernel: ops.conv_plan (what the launcher itself derives) names the tile, waves and ring depth the case's knobs
+    ask for and the K split the table says; and its stats_written is what the launch then reported -- observable from the launch itself, which
+    ties the query to what ran"""
+    knobs = dict(case.knobs)
+    assert plan['refused'] == 0 and plan['kernel'] == _kernel_of(case)
+    if plan['kernel'] == 0:
+        default_tile = 192 if case.cout % 192 == 0 else 128 if case.cout % 128 == 0 else 64
+        assert plan['tile'] == knobs.get('conv_tile', default_tile)
+        if mode == 'f32':             # one configuration (conv_reference.KNOB_ABSENT)
+            assert (plan['waves'], plan['stages']) == (4, 2)
+        else:
+            assert plan['waves'] == knobs.get('conv_waves', plan['waves']) and plan['waves'] in (4, 8)
+            assert plan['stages'] == knobs.get('conv_stages', plan['stages']) and plan['stages'] in (2, 3, 4)
+    else:
+        assert (plan['gn'], plan['sk']) == (int(case.gn), int(case.skip is not None))
+    if case.splits > 0:
+        assert (plan['splits'], plan['ks_per_split']) == R.effective_splits(case, mode)
+    else:
+        assert plan['splits'] >= 1
+    assert plan['stats_written'] == int(stats_written)
+
+
 def _launch(ops, case, mode, a, want_stats):
     """ops.conv2d of the case on the arguments `a` (float64 CPU tensors): (out NCHW on the CPU in its own dtype, stats or None, the guard
     buffer, the kernel the query names); a SplitQKV's data comes back as it is"""
@@ -157,13 +181,16 @@ def _launch(ops, case, mode, a, want_stats):
         if a['skip'] is not None:
             assert ops.conv_folds_skip(x1d, wp, kw['skip'])
         if case.split2:
-            out = ops.conv2d(x1d, wp, bias, x2=x2d, bias_nc=bnc, residual=res, up=case.up, out_scale=a['out_scale'], out_split2=True, **kw)
+            call = dict(x2=x2d, bias_nc=bnc, residual=res, up=case.up, out_scale=a['out_scale'], out_split2=True, **kw)
+            out = ops.conv2d(x1d, wp, bias, **call)
             torch.cuda.synchronize()
+            _assert_plan(case, mode, ops.conv_plan(x1d, wp, bias, **call), False)
             return out.data.cpu(), None, None, kernel
         buf, view = _guarded((case.n, ho, wo, case.cout), dt)
-        out = ops.conv2d(x1d, wp, bias, x2=x2d, bias_nc=bnc, residual=res, up=case.up, out_scale=a['out_scale'], out=view,
-                         gn_stats=want_stats, **kw)
+        call = dict(x2=x2d, bias_nc=bnc, residual=res, up=case.up, out_scale=a['out_scale'], out=view, gn_stats=want_stats, **kw)
+        out = ops.conv2d(x1d, wp, bias, **call)
         torch.cuda.synchronize()
+        _assert_plan(case, mode, ops.conv_plan(x1d, wp, bias, **call), out._gn_stats is not None)
     assert out.data_ptr() == view.data_ptr()
     st = out._gn_stats
     return R.nchw(out.cpu()), (None if st is None else st.cpu()), buf.cpu(), kernel
