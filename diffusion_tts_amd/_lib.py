@@ -30,7 +30,7 @@ class ConvPlanInfo(C.Structure):
     """dts_conv_plan_info: the launch plan of a dts_conv2d call (include/dts.h)"""
     _fields_ = [(f, C.c_int32) for f in ('kernel', 'tile', 'waves', 'stages', 'pf', 'gn', 'sk', 'dbg', 'splits', 'ks_per_split', 'n_ct', 'n_pt', 'nblk',
                                          'threads', 'lds_bytes', 'stats_in_kernel', 'stats_in_reduce', 'stats_written', 'epi_rows', 'fuses_gn',
-                                         'folds_skip', 'refused')]
+                                         'folds_skip', 'refused', 'phases')]
 
 
 # name -> argtypes (every function returns int status except the three noted below)
@@ -93,11 +93,11 @@ SIGNATURES = {
     'dts_cfg_combine': [_p, _p, _f, _p, _i, _i64, _p],
     'dts_ddim_candidates': [_p, _p, _p, _p, _p, _i, _f, _f, _f, _i, _i64, _p],
 }
-OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_conv_plan': ([C.POINTER(ConvArgs), C.POINTER(ConvPlanInfo)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64),
+OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_conv_takes_phases': ([C.POINTER(ConvArgs)], _i), 'dts_conv_plan': ([C.POINTER(ConvArgs), C.POINTER(ConvPlanInfo)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64),
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 119              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 120              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():
@@ -128,7 +128,7 @@ def check(status, what=''):
         raise RuntimeError(f'libdts_hip {what} failed ({status}): {msg}')
 
 
-KNOBS = {'att_xcd': 0, 'att_qt': 1, 'conv_tile': 2, 'conv_splits': 3, 'conv_variant': 4, 'gn_fuse': 5, 'att_db': 6, 'conv_stages': 7, 'conv_waves': 8, 'conv_half_round': 9, 'conv_epi32': 10, 'conv_skip_fold': 11}
+KNOBS = {'att_xcd': 0, 'att_qt': 1, 'conv_tile': 2, 'conv_splits': 3, 'conv_variant': 4, 'gn_fuse': 5, 'att_db': 6, 'conv_stages': 7, 'conv_waves': 8, 'conv_half_round': 9, 'conv_epi32': 10, 'conv_skip_fold': 11, 'conv_up_phases': 12}
 
 
 def set_tuning(name, value):

@@ -8,12 +8,14 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libdts_hip.so')
-SOURCES = ['conv_igemm.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip', 'resample.hip', 'transformer.hip', 'group_rows.hip', 'vit.hip', 'vit_x3.hip', 'jpeg.hip']
+SOURCES = ['conv_igemm.hip', 'conv_igemm_phase.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip', 'resample.hip', 'transformer.hip', 'group_rows.hip', 'vit.hip', 'vit_x3.hip', 'jpeg.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 # per-source extras.  attention: keep the MFMA accumulators in VGPRs -- the online-softmax rescale reads and rewrites them
 # every key tile, and with the default AGPR form hipcc emitted 80 v_accvgpr_read/write per tile (a quarter of the loop's VALU).
 EXTRA = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1']}
+# sources that include another source (rebuilt when it changes)
+INCLUDES = {'conv_igemm_phase.hip': ['conv_igemm.hip']}
 
 
 def _newer(a, b):
@@ -27,7 +29,8 @@ def build(force=False, verbose=False):
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace('.hip', '.o'))
         objs.append(o)
-        if force or _newer(s, o) or any(_newer(h, o) for h in hdrs):
+        deps = hdrs + [os.path.join(CSRC, d) for d in INCLUDES.get(src, [])]
+        if force or _newer(s, o) or any(_newer(h, o) for h in deps):
             jobs.append([HIPCC, *FLAGS, *EXTRA.get(src, []), '-c', s, '-o', o])
 
     def run(cmd):
@@ -54,7 +57,7 @@ def build(force=False, verbose=False):
 OBJDUMP = os.environ.get('LLVM_OBJDUMP', '/opt/rocm/lib/llvm/bin/llvm-objdump')
 READELF = os.environ.get('LLVM_READELF', os.path.join(os.path.dirname(OBJDUMP), 'llvm-readelf'))
 # objects whose kernels write M0 in inline asm (LDS-DMA destination) and await the loads with hand-counted s_waitcnt vmcnt(N)
-M0_OBJECTS = ['conv_igemm.o', 'attention.o']
+M0_OBJECTS = ['conv_igemm.o', 'conv_igemm_phase.o', 'attention.o']
 
 
 def _device_object(obj, tmp):

@@ -30,6 +30,12 @@
 
 static_assert(sizeof(dts_conv_args) == 208, "dts_conv_args layout changed: bump DTS_ABI_VERSION and update the bindings (_lib.py ConvArgs)");
 
+// The phase forms of conv_igemm_kernel (PH = true) are instantiated in a translation unit of their own, conv_igemm_phase.hip, which is this
+// file compiled with DTS_CONV_PHASE_TU: it keeps the kernel templates and the launcher and leaves out the C entry points, so the eight
+// kernels compile beside this file instead of lengthening the longest compile of the build.  The two units meet in this one function; its
+// arguments are this file's ConvPlan, ConvP and ConvCall (internal types, identical in both units since both are this text).
+int dts_conv_launch_phase_form(const void* plan, const void* params, const void* call);
+
 namespace {
 
 // per-call launch state that is not a kernel argument (no globals: dts_conv2d may be called from several host threads)
@@ -242,6 +248,37 @@ struct TileMap {
 };
 __device__ __forceinline__ TileMap linear_tile(int pn0) { return TileMap{pn0, 0, 0, 0, pn0 >> 6}; }
 
+// Phase tiles (conv_igemm_kernel<.., PH = true>: a nearest-2x upsampled 3x3 conv as four 2x2 convs over the LOW-resolution input): row r is
+// low-resolution pixel q = pn0 + r = (n, y, x), whose output pixel of this block's phase (py, px) is (n, 2y + py, 2x + px).  q is beyond the
+// batch exactly when pix(r) >= P (the sample index is the leading term of both), so the epilogues' `pix(..) < P` tests hold as they are.
+// The f32 epilogues (conv_epilogue, conv_epilogue_rows_f32) take either map as a template argument.
+struct PhaseTileMap {
+  int pn0;                              // first low-resolution pixel of the tile
+  int py, px;
+  int lw, lhw;                          // low-resolution width, low-resolution pixels per sample
+  int lw_shift, lhw_shift;              // their log2 when both are powers of two, else -1 (coordinates by division)
+  __device__ __forceinline__ int pix(int r) const {
+    const int q = pn0 + r;
+    int n, y, x;
+    if (lhw_shift >= 0) {
+      n = q >> lhw_shift;
+      const int rem = q & ((1 << lhw_shift) - 1);
+      y = rem >> lw_shift; x = rem & ((1 << lw_shift) - 1);
+    } else {
+      n = q / lhw;
+      const int rem = q - n * lhw;
+      y = rem / lw; x = rem - y * lw;
+    }
+    return n * 4 * lhw + (2 * y + py) * 2 * lw + 2 * x + px;
+  }
+  // the wave's 64 low-resolution pixels are strip s of sample n (S = lhw / 64 strips per sample and phase); its moments go to strip
+  // n * 4S + phase * S + s of the output's buffer (gn_coef_strips_kernel sums all strips of a sample and assumes no adjacency)
+  __device__ __forceinline__ int strip(int wn) const {
+    const int S = lhw >> 6, gs = (pn0 >> 6) + wn, n = gs / S;
+    return n * 4 * S + (2 * py + px) * S + (gs - n * S);
+  }
+};
+
 // LDS-DMA pieces [u0, u1) of the residual tile into the staged tile at LDS byte address `stage` (wave-uniform): piece u is the
 // 16-byte slots u*NTHR .. u*NTHR+NTHR-1 of the dense, XOR-swizzled pixel-major tile described in conv_epilogue_fast.
 template <int BM, int NTHR>
@@ -428,8 +465,8 @@ __device__ __forceinline__ void conv_epilogue_fast(const ConvP& kp, f32x4_t (&ac
 // What it does NOT buy (measured, round 5): with one block per CU the blocks of a launch reach their epilogues together, and 196 KB of f32
 // output (+ 196 KB of residual) per block at a 256th of the HBM rate is ~20k (+ 20k) cycles whatever the instruction stream does: -13 % on
 // the 1x1 layers, -3 % on the ping-pong residual layers, +1.8 % on the N = 64 step (profiles/r05_experiments.txt).
-template <int MT, int NT>
-__device__ __forceinline__ void conv_epilogue_rows_f32(const ConvP& kp, f32x4_t (&acc)[MT][NT], int cm0, const TileMap& tm, int wm, int wn,
+template <int MT, int NT, typename TM = TileMap>
+__device__ __forceinline__ void conv_epilogue_rows_f32(const ConvP& kp, f32x4_t (&acc)[MT][NT], int cm0, const TM& tm, int wm, int wn,
                                                        int lrow, int lq, char* smem, int wave) {
   static_assert(NT == 4, "64-pixel wave strips");
   constexpr int CW = 16 * MT;                          // couts of this wave's rows
@@ -533,8 +570,8 @@ __device__ __forceinline__ void conv_epilogue_rows_f32(const ConvP& kp, f32x4_t 
 
 // ---- epilogue of one (cout tile, pixel tile[, K split]): lane holds couts co..co+3 of pixel pp for each (mt, nt)
 // RING: bytes of the caller's (idle) LDS ring, which the staged output tile reuses
-template <typename T, int MT, int NT, int BM, int BN, int NTHR, int RING>
-__device__ __forceinline__ void conv_epilogue(const ConvP& kp, f32x4_t (&acc)[MT][NT], int cm0, const TileMap& tm, int split, int wm, int wn,
+template <typename T, int MT, int NT, int BM, int BN, int NTHR, int RING, typename TM = TileMap>
+__device__ __forceinline__ void conv_epilogue(const ConvP& kp, f32x4_t (&acc)[MT][NT], int cm0, const TM& tm, int split, int wm, int wn,
                                               int lrow, int lq, char* smem, bool bias_in_acc, int stage_off, int early_u0, int early_u1) {
   const int p_P = kp.P, p_cout = kp.cout, p_hout = kp.hout, p_wout = kp.wout;
   // ---- epilogue: lane holds couts co..co+3 of pixel pp for each (mt, nt): one 4-element vector load/store
@@ -713,7 +750,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& kp, f32x4_t (&acc)[MT
 // tile: (wh, hi), (wh * 2^-11, lo * 2^11), (wl, hi) -- the scaled copy of the wh fragment is made in registers (4 v_pk_mul_f16).  Round 4
 // staged three separate K steps (planes hi | lo | hi against hi | hi * 2^-11 | lo): 1.5 x the LDS-DMA pieces, fragment reads and HBM bytes
 // per product for the same MFMAs.
-template <typename T, int MT, int NT, int WM, int WN, bool PF, int STAGES = 2, typename OT = T>
+// PH (split precision only; dts_conv_args.up == 2): the 3x3 convolution over the nearest-2x upsampled input as four 2x2 convolutions over the
+// low-resolution input.  Every 2x2 cell of the upsampled image repeats one input pixel, so an output pixel of phase (py, px) = (y & 1, x & 1)
+// sees a 2x2 low-resolution neighbourhood and the nine taps collapse to four whose weights are sums of the original ones (packed per phase
+// by ops.pack_conv_weight(.., up_phases=True): [4][cout][2][2][cin], kp.taps = 4): 4/9 of the MFMAs for the same output.  The pixel rows of
+// a block are LOW-resolution pixels; the phase is a third factor of the block index (cout tile fastest, then phase, then pixel tile: the
+// four phases of a pixel tile read the same activation rows from L2); tap t reads low-resolution offset ((t >> 1) - 1 + py,
+// (t & 1) - 1 + px) -- the padding after the upsample is exactly the low-resolution out-of-range row -- and the epilogue addresses the
+// output, bias_nc and the residual through a PhaseTileMap.  No K split (the plan refuses one).
+template <typename T, int MT, int NT, int WM, int WN, bool PF, int STAGES = 2, typename OT = T, bool PH = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)) void conv_igemm_kernel(const ConvP kp) {
   const char* const p_x1 = kp.x1; const char* const p_x2 = kp.x2; const char* const p_w = kp.w;
   const int p_c1 = kp.c1, p_c2 = kp.c2, p_cin = kp.cin, p_hin = kp.hin, p_win = kp.win, p_hout = kp.hout, p_wout = kp.wout;
@@ -726,6 +771,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
   constexpr int NW = WM * WN;
   constexpr bool X3I = !std::is_same<T, OT>::value;
   static_assert(!X3I || std::is_same<T, f16_t>::value, "split precision runs on the f16 matrix instruction");
+  static_assert(!PH || X3I, "the phase form is the split-precision mode's");
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(STAGES >= 2 && STAGES <= 4, "ring depth");
   constexpr int SLAB = 8 * NW;             // rows staged by one wave-instruction round of the whole block
@@ -744,14 +790,18 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
 
   // ---- XCD-aware tile mapping: blocks b, b+8, b+16.. (same XCD under round-robin dispatch) walk the
   // cout tiles of one pixel tile consecutively, so the activation rows are re-read from that XCD's L2.
-  const int nblk = p_n_ct * p_n_pt;
+  const int nblk = p_n_ct * p_n_pt * (PH ? 4 : 1);
   int bid = blockIdx.x;
   {
     const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, j = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
   }
-  const int ct = bid % p_n_ct, pt = bid / p_n_ct;
+  const int ct = bid % p_n_ct, pt = PH ? (bid / p_n_ct) >> 2 : bid / p_n_ct;
   const int cm0 = ct * BM, pn0 = pt * BN;
+  const int phase = PH ? (bid / p_n_ct) & 3 : 0, ph_y = phase >> 1, ph_x = phase & 1;
+  // the coordinates of a tile's pixel ROWS: output pixels, or (PH) low-resolution pixels
+  const int g_h = PH ? p_hin : p_hout, g_w = PH ? p_win : p_wout, g_P = PH ? p_P >> 2 : p_P;
+  const int g_hw_shift = PH ? kp.hw_shift - 2 : kp.hw_shift, g_w_shift = PH ? kp.w_shift - 1 : kp.w_shift;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid % WM, wn = wid / WM;
@@ -778,13 +828,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
 
 #define SET_ROWS(tap_, ci0_)                                                                                  \
   {                                                                                                           \
-    const int dh_ = (p_taps == 9) ? (tap_) / 3 - 1 : 0, dw_ = (p_taps == 9) ? (tap_) % 3 - 1 : 0;             \
+    const int dh_ = PH ? ((tap_) >> 1) - 1 + ph_y : ((p_taps == 9) ? (tap_) / 3 - 1 : 0);                     \
+    const int dw_ = PH ? ((tap_) & 1) - 1 + ph_x : ((p_taps == 9) ? (tap_) % 3 - 1 : 0);                      \
     const char* xb; int cs, cofs;                                                                             \
     if ((ci0_) < p_c1) { xb = p_x1; cs = p_c1; cofs = (ci0_); } else { xb = p_x2; cs = p_c2; cofs = (ci0_) - p_c1; } \
     _Pragma("unroll") for (int j = 0; j < RB; ++j) {                                                          \
       const int hu = (pix_hw[j] >> 16) + dh_, wu = (pix_hw[j] & 0xffff) + dw_;                                \
-      const bool ok = pix_n[j] >= 0 && (unsigned)hu < (unsigned)p_hout && (unsigned)wu < (unsigned)p_wout;    \
-      const int hs = p_up ? (hu >> 1) : hu, ws = p_up ? (wu >> 1) : wu;                                       \
+      const bool ok = pix_n[j] >= 0 && (unsigned)hu < (unsigned)g_h && (unsigned)wu < (unsigned)g_w;          \
+      const int hs = (!PH && p_up) ? (hu >> 1) : hu, ws = (!PH && p_up) ? (wu >> 1) : wu;                     \
       brow[j] = ok ? xb + ((size_t)(pix_n[j] + hs * p_win + ws) * cs + cofs) * ES + schunk : zsrc;            \
     }                                                                                                         \
   }
@@ -809,7 +860,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
   // issue-side K state (tap, cin offset) runs STAGES-1 tiles ahead of the compute side
   int tap = ks_begin / steps_per_tap, ci0 = (ks_begin - tap * steps_per_tap) * BKE;
 #pragma unroll
-  for (int j = 0; j < RA; ++j) arow[j] = p_w + ((size_t)(cm0 + r0 + SLAB * j) * K + (size_t)ks_begin * BKE) * ES + schunk;
+  for (int j = 0; j < RA; ++j) arow[j] = p_w + ((size_t)((PH ? phase * kp.cout : 0) + cm0 + r0 + SLAB * j) * K + (size_t)ks_begin * BKE) * ES + schunk;
   // first tile: the weight rows go out before the pixel coordinates of the activation rows are worked out, so that
   // arithmetic runs under the first loads' latency (the prologue is ~5k exposed cycles per block)
   {
@@ -820,17 +871,17 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
 #pragma unroll
   for (int j = 0; j < RB; ++j) {
     const int pp = pn0 + r0 + SLAB * j;
-    if (pp < p_P) {
+    if (pp < g_P) {
       int n, ho, wo;
       if (kp.hw_shift >= 0) {                            // block-uniform: every U-Net level here is a power of two
-        n = pp >> kp.hw_shift;
-        const int rem = pp & ((1 << kp.hw_shift) - 1);
-        ho = rem >> kp.w_shift; wo = rem & ((1 << kp.w_shift) - 1);
+        n = pp >> g_hw_shift;
+        const int rem = pp & ((1 << g_hw_shift) - 1);
+        ho = rem >> g_w_shift; wo = rem & ((1 << g_w_shift) - 1);
       } else {
-        const int hw = p_hout * p_wout;
+        const int hw = g_h * g_w;
         n = pp / hw;
         const int rem = pp - n * hw;
-        ho = rem / p_wout; wo = rem - ho * p_wout;
+        ho = rem / g_w; wo = rem - ho * g_w;
       }
       pix_n[j] = n * p_hin * p_win;
       pix_hw[j] = (ho << 16) | wo;
@@ -962,6 +1013,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
   }
 
   DTS_STAMP(2);
+  if constexpr (PH) {
+    const bool sh = kp.hw_shift >= 0;
+    const PhaseTileMap tm{pn0, ph_y, ph_x, p_win, p_hin * p_win, sh ? g_w_shift : -1, sh ? g_hw_shift : -1};
+    conv_epilogue<OT, MT, NT, BM, BN, 64 * NW, RING_BYTES>(kp, acc, cm0, tm, (int)blockIdx.y, wm, wn, lrow, lq, smem, bias_in_acc, stage_off, early_u0, early_u1);
+  } else
   conv_epilogue<OT, MT, NT, BM, BN, 64 * NW, RING_BYTES>(kp, acc, cm0, linear_tile(pn0), (int)blockIdx.y, wm, wn, lrow, lq, smem, bias_in_acc, stage_off, early_u0, early_u1);
   DTS_STAMP(3);
   DTS_STAMP_RT(5);
@@ -1665,14 +1721,14 @@ int launch_reduce(const ConvP& q, bool with_stats, hipStream_t st) {
 
 // the knobs, read once per plan: DTS_CONV_VARIANT (1 = ping-pong wherever it applies, 0 = never, unset = by shape), DTS_CONV_TILE=64|128|192
 // (only honoured when it divides cout), DTS_CONV_SPLITS (forced K split), DTS_CONV_STAGES = 2 | 3 | 4 and DTS_CONV_WAVES = 4 | 8 (forced ring depth /
-// waves per block), DTS_CONV_HALF_ROUND, DTS_CONV_EPI32, DTS_CONV_SKIP_FOLD: tuning and A/B aids.  DTS_F32_TILE192=0 restores the smaller f32
+// waves per block), DTS_CONV_HALF_ROUND, DTS_CONV_EPI32, DTS_CONV_SKIP_FOLD, DTS_CONV_UP_PHASES: tuning and A/B aids.  DTS_F32_TILE192=0 restores the smaller f32
 // tile (A/B aid; plain environment, read once per process)
-struct ConvKnobs { int variant, tile, splits, stages, waves, half_round, epi32, skip_fold; bool f32_tile192; };
+struct ConvKnobs { int variant, tile, splits, stages, waves, half_round, epi32, skip_fold, up_phases; bool f32_tile192; };
 ConvKnobs conv_knobs() {
   static const bool f32_192 = !(getenv("DTS_F32_TILE192") && atoi(getenv("DTS_F32_TILE192")) == 0);
   return {dts_knob_get(DTS_KNOB_CONV_VARIANT), dts_knob_get(DTS_KNOB_CONV_TILE), dts_knob_get(DTS_KNOB_CONV_SPLITS),
           dts_knob_get(DTS_KNOB_CONV_STAGES), dts_knob_get(DTS_KNOB_CONV_WAVES), dts_knob_get(DTS_KNOB_CONV_HALF_ROUND),
-          dts_knob_get(DTS_KNOB_CONV_EPI32), dts_knob_get(DTS_KNOB_CONV_SKIP_FOLD), f32_192};
+          dts_knob_get(DTS_KNOB_CONV_EPI32), dts_knob_get(DTS_KNOB_CONV_SKIP_FOLD), dts_knob_get(DTS_KNOB_CONV_UP_PHASES), f32_192};
 }
 
 // the fields of dts_conv_plan_info (include/dts.h says what each means) + why dts_conv2d must refuse the call, where `refused` is set
@@ -1687,7 +1743,7 @@ int conv_launch(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
     attr_done[dev] = true;
   }
-  const dim3 grid(pl.nblk, pl.splits), block(pl.threads);
+  const dim3 grid(pl.nblk, pl.splits), block(pl.threads);      // (phase launches: nblk counts the four phases of every tile)
   if (call.ev_start != nullptr && call.ev_stop != nullptr)
     hipExtLaunchKernelGGL(KERNEL, grid, block, (size_t)pl.lds_bytes, call.st, call.ev_start, call.ev_stop, 0, q);
   else
@@ -1697,9 +1753,9 @@ int conv_launch(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
 }
 
 // conv_igemm_kernel of one tile (MT x 4 MFMA tiles per wave, WM x WN waves in its 4-wave form; the 8-wave form halves the couts per wave)
-template <typename T, typename OT, int MT, int WM, int WN, bool PF>
+template <typename T, typename OT, int MT, int WM, int WN, bool PF, bool PH = false>
 int conv_launch_igemm(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
-#define DTS_IGEMM(MT_, WM_, STAGES_) conv_launch<&conv_igemm_kernel<T, MT_, 4, WM_, WN, PF, STAGES_, OT>>(pl, q, call)
+#define DTS_IGEMM(MT_, WM_, STAGES_) conv_launch<&conv_igemm_kernel<T, MT_, 4, WM_, WN, PF, STAGES_, OT, PH>>(pl, q, call)
   if constexpr (sizeof(T) == 2) {                            // (f32: the 2-deep ring with 4 waves only)
     if (pl.waves == 8) return pl.stages == 3 ? DTS_IGEMM(MT / 2, WM * 2, 3) : DTS_IGEMM(MT / 2, WM * 2, 2);
     if (pl.stages == 3) return DTS_IGEMM(MT, WM, 3);
@@ -1843,6 +1899,8 @@ int conv_launch_plan(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
   if constexpr (sizeof(T) == 2) {
 #define DTS_PP(DBG_, GN_, MT_, SK_) conv_launch<&conv_pp_kernel<T, 9, DBG_, GN_, MT_, OT, SK_>>(pl, q, call)
     if constexpr (!std::is_same<T, OT>::value) {
+      // the phase form (instantiated in conv_igemm_phase.hip): 192- / 128-cout tiles, fragment prefetch; waves and ring depth (2 | 3) are conv_launch_igemm's
+      if (pl.phases) return dts_conv_launch_phase_form(&pl, &q, &call);
       if (pl.kernel == 6 && pl.sk) return DTS_PP(0, false, 6, true);
       if (pl.kernel == 4 && pl.sk) return DTS_PP(0, false, 4, true);
     } else if (pl.kernel == 6) {
@@ -1901,7 +1959,11 @@ ConvPlan conv_plan(const dts_conv_args* a) {
   if ((long long)a->n * a->hin * a->win * (a->up ? 4 : 1) >= (1ll << 30)) return refuse("dts_conv2d: too many pixels");
   ConvP p;
   conv_shape_from_args(a, p);
-  const int mt = conv_pick_pp(k, f32, p, x3);
+  // up == 2: the phase form of conv_igemm_kernel (`w` holds four 2x2-tap weights); never the ping-pong kernel, whose ring protocol is
+  // derived for nine-tap chunks
+  const bool ph = a->up == 2;
+  if (ph) p.taps = 4;
+  const int mt = ph ? 0 : conv_pick_pp(k, f32, p, x3);
   pl.kernel = mt;
   // ---- grid and K loop
   int unit = 1;                                              // K steps that stay together in a split
@@ -1917,11 +1979,12 @@ ConvPlan conv_plan(const dts_conv_args* a) {
     if (f32 && pl.tile == 192 && !k.f32_tile192) pl.tile = (p.cout % 128 == 0) ? 128 : 64;
     if (k.tile > 0 && p.cout % k.tile == 0) pl.tile = (k.tile == 192 || k.tile == 128) ? k.tile : 64;
     pl.n_ct = p.cout / pl.tile; pl.n_pt = (p.P + (pl.tile == 64 ? 255 : 127)) / (pl.tile == 64 ? 256 : 128);      // 64 x 256, 128 x 128, 192 x 128
+    if (ph) pl.n_pt = (p.P / 4 + 127) / 128;                 // the pixel rows of a phase tile are low-resolution pixels
     // fragment prefetch pays on the long K loops of the 3x3 layers; f32 (parity mode) keeps the lean order: its 192-cout
     // tile is already at the 256-VGPR limit
-    pl.pf = p.taps == 9 && !f32;
+    pl.pf = a->ksize == 3 && !f32;
   }
-  pl.nblk = pl.n_ct * pl.n_pt;
+  pl.nblk = pl.n_ct * pl.n_pt * (ph ? 4 : 1);               // (the phase is a third factor of the block index)
   const int bke = f32 ? 32 : 64, nk = p.taps * (p.cin / bke);
   // ---- fused input GroupNorm, folded skip convolution
   pl.gn = a->gn_coef != nullptr;
@@ -1950,6 +2013,18 @@ ConvPlan conv_plan(const dts_conv_args* a) {
   }
   if (pl.gn && x3) return refuse("dts_conv2d: gn_coef is not available in the split-precision mode");
   if (a->dtype < DTS_F32 || a->dtype > DTS_F16X3) return refuse("bad dtype %d", a->dtype);
+  // ---- up == 2, the phase form (dts_conv_takes_phases answers whether all of this holds).  A residual is supported: both f32 epilogues
+  // address it through the tile map like the output.
+  if (ph) {
+    if (!x3) return refuse("dts_conv2d: up = 2 (phase-packed weights) is the split-precision mode's (DTS_F16X3), dtype %d", a->dtype);
+    if (a->ksize != 3) return refuse("dts_conv2d: up = 2 needs ksize 3, got %d", a->ksize);
+    if (a->c2 != 0 || a->x2 != nullptr) return refuse("dts_conv2d: up = 2 takes no second input");
+    if (a->gn_coef != nullptr || pl.sk || a->out_split2) return refuse("dts_conv2d: up = 2 takes no gn_coef, skip_* or out_split2");
+    if (pl.tile == 64) return refuse("dts_conv2d: up = 2 needs cout %d to be a multiple of 128 or 192", a->cout);
+    if (a->stats_out != nullptr && (a->hin * a->win) % 64 != 0)
+      return refuse("dts_conv2d: up = 2 with strip statistics needs hin*win = %d to be a multiple of 64 (a wave's strip is 64 low-resolution pixels)", a->hin * a->win);
+    if (k.up_phases == 0) return refuse("dts_conv2d: up = 2 while DTS_CONV_UP_PHASES=0");
+  }
   if (mt == 6 && !x3 && !pl.gn) {                            // (the diagnostic forms exist for the plain 192-cout 16-bit launch only)
     pl.dbg = conv_pp_dbg(k.variant);
     if (pl.dbg < 0) return refuse("dts_conv2d: DTS_CONV_VARIANT=%d selects a diagnostic kernel that this library was built without (-DDTS_DIAG_KERNELS)", k.variant);
@@ -1965,6 +2040,11 @@ ConvPlan conv_plan(const dts_conv_args* a) {
     pl.ks_per_split = per * unit;
     pl.splits = (nunit + per - 1) / per;                     // no empty split
   }
+  if (ph) {
+    // the phase form takes no K split (the reduce pass knows nothing of phases): a grid that wants one, or a forced one, is the old route's
+    if (pl.splits > 1) return refuse("dts_conv2d: up = 2 with a K split of %d (the phase form takes none: use the fused-gather route)", pl.splits);
+    pl.phases = 1;
+  }
   // statistics come from the fused epilogue (whole launches, 64-pixel wave strips) or, under split-K, from the reduce pass
   pl.stats_in_kernel = a->stats_out != nullptr && pl.splits == 1;
   pl.stats_in_reduce = a->stats_out != nullptr && pl.splits > 1 && (p.hout * p.wout) % 64 == 0 && p.cout % 4 == 0;
@@ -1972,6 +2052,8 @@ ConvPlan conv_plan(const dts_conv_args* a) {
   // the row-layout f32 epilogue: the split-precision mode's default; the f32 parity mode keeps the accumulator-layout epilogue (the mode is the
   // REFERENCE the others are compared with: its summation orders stay what rounds 2-4 validated against the CPU oracle) unless DTS_CONV_EPI32=1
   pl.epi_rows = k.epi32 < 0 ? (x3 ? 1 : 0) : (k.epi32 == 2 ? 2 : (k.epi32 != 0));
+  // (phase form: a wave's strip is 64 LOW-resolution pixels, which must not straddle samples or the end of the batch for the row layout)
+  if (ph && (a->hin * a->win) % 64 != 0) pl.epi_rows = 0;
   if (mt != 0) return pl;
   // ---- conv_igemm_kernel: ring depth and waves
   const bool one_per_cu = (long long)pl.nblk * pl.splits <= 256;
@@ -1991,6 +2073,16 @@ ConvPlan conv_plan(const dts_conv_args* a) {
 }
 
 }  // namespace
+
+#ifdef DTS_CONV_PHASE_TU
+// conv_igemm_phase.hip: the launch of a plan with phases = 1, and with it the only instantiations of conv_igemm_kernel<.., PH = true>
+int dts_conv_launch_phase_form(const void* plan, const void* params, const void* call) {
+  const ConvPlan& pl = *static_cast<const ConvPlan*>(plan);
+  const ConvP& q = *static_cast<const ConvP*>(params);
+  const ConvCall& c = *static_cast<const ConvCall*>(call);
+  return pl.tile == 192 ? conv_launch_igemm<f16_t, float, 6, 2, 2, true, true>(pl, q, c) : conv_launch_igemm<f16_t, float, 4, 2, 2, true, true>(pl, q, c);
+}
+#else
 
 #ifdef DTS_STAMPS
 extern "C" int dts_debug_read_stamps(unsigned long long* host, int count) {
@@ -2015,6 +2107,14 @@ extern "C" int dts_conv_fuses_gn(const dts_conv_args* a) { return conv_plan(a).f
 // (the fold is the ping-pong kernel's, for grids that do not weigh a K split: pp_considers_split, the rule pp_splits itself uses)
 extern "C" int dts_conv_folds_skip(const dts_conv_args* a) { return conv_plan(a).folds_skip ? 1 : 0; }
 
+// (the phase form, asked with up = 2: everything conv_plan wants of it holds -- split precision, 3x3, 128- / 192-cout tiles, no second input /
+// gn_coef / skip_* / out_split2, no K split wanted or forced, whole low-resolution strips under statistics, DTS_CONV_UP_PHASES not 0)
+extern "C" int dts_conv_takes_phases(const dts_conv_args* a) {
+  if (a == nullptr || a->up != 2) return 0;
+  const ConvPlan pl = conv_plan(a);
+  return (!pl.refused && pl.phases) ? 1 : 0;
+}
+
 extern "C" int dts_conv_plan(const dts_conv_args* a, dts_conv_plan_info* out) {
   DTS_CHECK_ARG(out != nullptr, "dts_conv_plan: null output");
   const ConvPlan pl = conv_plan(a);
@@ -2031,6 +2131,7 @@ extern "C" int dts_conv2d(dts_conv_args* a, dts_stream s) {
   DTS_CHECK_ARG(a->bias_nc == nullptr || a->ld_bias_nc >= a->cout, "dts_conv2d: ld_bias_nc");
   ConvP p;
   conv_shape_from_args(a, p);
+  if (pl.phases) p.taps = 4;                                 // four 2x2-tap weights of K = 4 * cin each
   DTS_CHECK_ARG(a->stats_out == nullptr || ((p.hout * p.wout) % 64 == 0 && (uintptr_t)a->stats_out % 16 == 0),
                 "dts_conv2d: strip statistics need hout*wout to be a multiple of 64 and a 16-byte aligned buffer");
   DTS_CHECK_ARG(a->workspace == nullptr || ((uintptr_t)a->workspace % 16 == 0 && a->workspace_bytes >= 0), "dts_conv2d: workspace");
@@ -2066,3 +2167,4 @@ extern "C" int dts_conv2d(dts_conv_args* a, dts_stream s) {
   a->stats_written = pl.stats_written ? 1 : 0;
   return rc;
 }
+#endif  // DTS_CONV_PHASE_TU

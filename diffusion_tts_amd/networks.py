@@ -123,7 +123,10 @@ class EDMPrecond:
                 self.blocks[n] = P
                 continue
             P.g0, P.b0 = f(g('norm0.weight')), f(g('norm0.bias'))
-            P.w0, P.cb0 = ops.pack_conv_weight(f(g('conv0.weight')), dt), f(g('conv0.bias'))
+            # split-precision mode, nearest-up blocks: conv0 also carries its four 2x2 phase weights (ops.conv2d takes the phase form -- 4/9 of
+            # the multiply-adds -- wherever ops.conv_takes_phases says so; DTS_CONV_UP_PHASES=0 keeps the nine-tap gather)
+            ph0 = self.x3 and b.up and not self.fir
+            P.w0, P.cb0 = ops.pack_conv_weight(f(g('conv0.weight')), dt, up_phases=ph0), f(g('conv0.bias'))
             caff = b.cout * (2 if self.adm else 1)
             aff_w.append(g('affine.weight'))
             aff_b.append(g('affine.bias'))

@@ -35,11 +35,13 @@ class X3Weight:
     """A conv weight packed for the split-precision mode: `packed` [O][kh][kw][2*I] float16 = per 32 input channels hi(32) | lo(32) of
     w * 2^k (k chosen per layer so that 2^13 < max|w| * 2^k <= 2^14: the lo parts of all weights that matter are normal f16 numbers;
     the matrix cores flush subnormal inputs), `acc_scale` = 2^-k.  The kernels scale the hi fragment by 2^-11 in registers where it meets
-    the activations' lo * 2^11 half."""
+    the activations' lo * 2^11 half.  `phases` (pack_conv_weight(.., up_phases=True), else None): the same 3x3 layer under a nearest 2x
+    upsample as four 2x2 weights [4][O][2][2][2*I] in the same form, with their own `phase_acc_scale` (dts.h: dts_conv_args.up == 2)."""
 
     def __init__(self, packed, acc_scale, shape):
         self.packed, self.acc_scale, self.shape = packed, float(acc_scale), tuple(shape)
         self.device, self.dtype = packed.device, F16X3
+        self.phases, self.phase_acc_scale = None, 0.0
 
     def numel(self):
         return self.packed.numel()
@@ -147,23 +149,53 @@ def nhwc_to_nchw(x):
     return out
 
 
-def pack_conv_weight(w, dtype, out_perm=None):
-    """OIHW float32 (device) -> [O][kh][kw][I] in `dtype`; out_perm: int32 device tensor of source rows."""
+def _x3_split_pack(w_ohwi):
+    """float32 [O][kh][kw][I] -> (packed float16 [O][kh][kw][2*I] = per 32 input channels hi(32) | lo(32) of w * 2^k, 2^-k): exact scaling by
+    the power of two that puts max|w| in (2^13, 2^14], two roundings"""
+    O, kh, kw, I = w_ohwi.shape
+    amax = float(w_ohwi.abs().max())
+    k = 0 if amax == 0.0 else max(-24, min(24, int(math.floor(math.log2(16384.0 / amax)))))
+    ws = (w_ohwi * (2.0 ** k)).contiguous()                                # exact (power of two)
+    hi = ws.to(torch.float16)
+    lo = (ws - hi.to(torch.float32)).to(torch.float16)
+    packed = torch.stack([hi.view(O, kh, kw, I // 32, 32), lo.view(O, kh, kw, I // 32, 32)], dim=-2)      # [.., I/32, 2, 32]: hi(32) | lo(32)
+    return packed.reshape(O, kh, kw, 2 * I).contiguous(), 2.0 ** -k
+
+
+# rows of a 3x3 kernel that fall on the two low-resolution rows an output row of parity py sees under a nearest 2x upsample:
+# UP_PHASE_ROWS[py][ty][kh], tap ty at the low-resolution offset ty - 1 + py (py = 0: {w0, w1 + w2}; py = 1: {w0 + w1, w2}); columns alike
+UP_PHASE_ROWS = (((1, 0, 0), (0, 1, 1)), ((1, 1, 0), (0, 0, 1)))
+
+
+def up_phase_weights(w):
+    """OIHW 3x3 weight -> [4][O][2][2][I] in w's dtype: conv2d(nearest_up2(x), w, padding=1) as four 2x2 convolutions over x, one per output
+    phase 2*py + px; the tap sums are formed in float64 and rounded once."""
+    R = torch.tensor(UP_PHASE_ROWS, dtype=torch.float64, device=w.device)            # [p][t][k]
+    ph = torch.einsum('ayh,bxw,oihw->aboyxi', R, R, w.to(torch.float64))              # [py][px][O][ty][tx][I]
+    O, I = w.shape[:2]
+    return ph.reshape(4, O, 2, 2, I).to(w.dtype)
+
+
+def pack_conv_weight(w, dtype, out_perm=None, up_phases=False):
+    """OIHW float32 (device) -> [O][kh][kw][I] in `dtype`; out_perm: int32 device tensor of source rows.
+    up_phases (F16X3, 3x3): the X3Weight also carries `phases` [4][O][2][2][2*I] (the four 2x2 weights of up_phase_weights(), split and
+    interleaved like `packed`, scaled by their own power of two: `phase_acc_scale`) for conv2d(..., up=True)."""
     if w.dim() == 3:                      # conv1d weight [O, I, 1]
         w = w.unsqueeze(-1)
     w = w.contiguous()
     O, I, kh, kw = w.shape
+    if up_phases and (dtype != F16X3 or (kh, kw) != (3, 3)):
+        raise ValueError('pack_conv_weight: up_phases is the split-precision mode\'s, for 3x3 weights')
     if dtype == F16X3:                    # load-time preparation in float32 on the device: exact scaling, two roundings
         wp = w if out_perm is None else w[out_perm.long()]
-        amax = float(wp.abs().max())
-        k = 0 if amax == 0.0 else max(-24, min(24, int(math.floor(math.log2(16384.0 / amax)))))
-        ws = (wp * (2.0 ** k)).permute(0, 2, 3, 1).contiguous()            # [O][kh][kw][I], exact (power of two)
         if I % 32:
             raise ValueError(f'pack_conv_weight(F16X3): {I} input channels are not a multiple of 32 (one K step of the split image)')
-        hi = ws.to(torch.float16)
-        lo = (ws - hi.to(torch.float32)).to(torch.float16)
-        packed = torch.stack([hi.view(O, kh, kw, I // 32, 32), lo.view(O, kh, kw, I // 32, 32)], dim=-2)      # [.., I/32, 2, 32]: hi(32) | lo(32)
-        return X3Weight(packed.reshape(O, kh, kw, 2 * I).contiguous(), 2.0 ** -k, (O, kh, kw, I))
+        packed, acc_scale = _x3_split_pack(wp.permute(0, 2, 3, 1))         # [O][kh][kw][I]
+        xw = X3Weight(packed, acc_scale, (O, kh, kw, I))
+        if up_phases:
+            pp, xw.phase_acc_scale = _x3_split_pack(up_phase_weights(wp).reshape(4 * O, 2, 2, I))
+            xw.phases = pp.reshape(4, O, 2, 2, 2 * I)
+        return xw
     out = torch.empty((O, kh, kw, I), dtype=dtype, device=w.device)
     _call('dts_pack_conv_weight', _ptr(w, 'w', torch.float32), _ptr(out), dt_code(dtype), O, I, kh, kw,
           _ptr(out_perm, 'perm', torch.int32))
@@ -192,15 +224,43 @@ def _conv_args(x1, w, x2, up):
     return a
 
 
-def conv_kernel(x1, w, x2=None, up=False, residual=None, gn_coef=None):
-    """Which kernel ops.conv2d launches for these arguments: 0 = 4-wave implicit GEMM, 6 / 4 = ping-pong kernel with 192- / 128-cout
-    blocks (dts_conv_kernel; measurement aid for bench.py)."""
+def conv_kernel(x1, w, x2=None, up=False, residual=None, gn_coef=None, gn_stats=False):
+    """Which kernel ops.conv2d launches for these arguments: 0 = 4-wave implicit GEMM (its phase form included), 6 / 4 = ping-pong kernel
+    with 192- / 128-cout blocks (dts_conv_kernel; measurement aid for bench.py)."""
     a = _conv_args(x1, w, x2, up)
     if isinstance(w, X3Weight):           # the launch sees one 16-bit source of 2*(c1+c2) channels
         a.c1, a.c2, a.dtype = 2 * (a.c1 + a.c2), 0, L.DTS_F16X3
     a.residual = _ptr(residual)
     a.gn_coef = _ptr(gn_coef, 'gn_coef', torch.float32)
+    if up and x2 is None and getattr(w, 'phases', None) is not None:
+        # as conv2d routes it (pointers are never dereferenced by the queries: presence is all that counts)
+        a.workspace, a.workspace_bytes = 16, CONV_WS_BYTES
+        if gn_stats and (4 * a.hin * a.win) % 64 == 0:
+            a.stats_out = 16
+        _route_phases(a, w, None)
     return int(L.load().dts_conv_kernel(C.byref(a)))
+
+
+def _route_phases(a, w, phases):
+    """conv2d(.., up=True) with a weight that carries phase-packed tensors: the dts_conv_args become the phase form's (up = 2, the four 2x2
+    weights and their power of two) where dts_conv_takes_phases says yes (phases=None), always (True: the library refuses what it cannot
+    run) or never (False); returns whether they did."""
+    if phases is False or getattr(w, 'phases', None) is None or a.up != 1:
+        return False
+    keep = (a.up, a.w, a.acc_scale)
+    a.up, a.w, a.acc_scale = 2, (w.phases.data_ptr() if w.phases.is_cuda else None), w.phase_acc_scale
+    if phases is None and not L.load().dts_conv_takes_phases(C.byref(a)):
+        a.up, a.w, a.acc_scale = keep
+        return False
+    return True
+
+
+def conv_takes_phases(x1, w, bias=None, **kw):
+    """True if conv2d(same arguments, up=True) runs the phase form: the 3x3 convolution over the nearest-2x upsampled input as four 2x2
+    convolutions over the input itself (dts_conv_takes_phases; `w` packed with up_phases=True)."""
+    kw.pop('up', None)
+    a, *_keep = _conv2d_args(x1, w, bias, up=True, **kw)
+    return a.up == 2
 
 
 def conv_fuses_gn(x1, w, *, x2=None, up=False):
@@ -233,7 +293,7 @@ def conv_folds_skip(x1, w, skip):
 
 
 def _conv2d_args(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, out_scale=1.0, out=None, gn_stats=False,
-                 timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None):
+                 timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None, phases=None):
     """the dts_conv_args of conv2d(...) (and of conv_plan(...): one builder, so the two cannot differ): (args, out, statistics buffer or None,
     out_split2, tensors the arguments point into)"""
     n, hin, win, c1 = x1.shape
@@ -287,13 +347,15 @@ def _conv2d_args(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=F
         if tuple(gn_coef.shape) != (n, c1 + c2, 2):
             raise ValueError(f'conv2d: gn_coef shape {tuple(gn_coef.shape)} != {(n, c1 + c2, 2)}')
         a.gn_coef, a.gn_silu = _ptr(gn_coef, 'gn_coef', torch.float32), int(gn_silu)
+    if x3 and up:
+        _route_phases(a, w, phases)
     return a, out, st, out_split2, (xs, ws)
 
 
 def conv_plan(*args, **kw):
     """The launch plan of conv2d(same arguments) as a dict of dts_conv_plan_info's fields (kernel, tile, waves, stages, pf, gn, sk, dbg, splits,
     ks_per_split, n_ct, n_pt, nblk, threads, lds_bytes, stats_in_kernel, stats_in_reduce, stats_written, epi_rows, fuses_gn, folds_skip,
-    refused): what the launcher derives, nothing is launched.  Test and measurement aid."""
+    refused, phases): what the launcher derives, nothing is launched.  Test and measurement aid."""
     a, *_keep = _conv2d_args(*args, **kw)
     info = L.ConvPlanInfo()
     _call('dts_conv_plan', C.byref(a), C.byref(info))
@@ -301,8 +363,10 @@ def conv_plan(*args, **kw):
 
 
 def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, out_scale=1.0, out=None, gn_stats=False,
-           timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None):
-    """skip=(SplitAct, X3Weight, up): the block's 1x1 skip convolution of that operand accumulated by this launch (only where conv_folds_skip()
+           timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None, phases=None):
+    """phases (up=True with a weight packed with up_phases=True): None = the phase form where conv_takes_phases() says so, False = never,
+    True = always (the library refuses what it cannot run).
+    skip=(SplitAct, X3Weight, up): the block's 1x1 skip convolution of that operand accumulated by this launch (only where conv_folds_skip()
     says so; `bias` is then the sum of the two layers' biases and there is no `residual`).
     timing_events=(start, stop): raw hipEvent_t handles attached to the conv kernel's own dispatch (measurement only).
     gn_stats=True: the epilogue also emits the GroupNorm moments of the output (per 64-pixel strip and channel); they
@@ -310,7 +374,7 @@ def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, 
     group_norm(), which then skips its own pass over the tensor."""
     a, out, st, out_split2, _keep = _conv2d_args(x1, w, bias, x2=x2, bias_nc=bias_nc, residual=residual, up=up, out_scale=out_scale, out=out,
                                                  gn_stats=gn_stats, timing_events=timing_events, gn_coef=gn_coef, gn_silu=gn_silu,
-                                                 out_split2=out_split2, skip=skip)
+                                                 out_split2=out_split2, skip=skip, phases=phases)
     _call('dts_conv2d', C.byref(a))
     if out_split2:
         return SplitQKV(out, (out.shape[0], out.shape[1], out.shape[2], out.shape[3] // 2))

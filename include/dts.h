@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 119        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 120        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -55,7 +55,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      116: dts_group_rows (the SD U-Net's distinct text contexts, grouped on the device);
                                      117: dts_attention_masked, dts_text_tokens (the CLIP text tower: SD's text encoder and the CLIP scorer's text side);
                                      118: dts_layer_norm_x3, dts_gelu_x3, dts_patchify_x3, dts_vit_tokens_f32, dts_vit_head_f32 (the CLIP vision tower in DTS_F16X3);
-                                     119: dts_conv_plan (the whole launch plan of a dts_conv2d call, as a query)) */
+                                     119: dts_conv_plan (the whole launch plan of a dts_conv2d call, as a query);
+                                     120: dts_conv_args.up == 2 (phase-packed weights), dts_conv_takes_phases, dts_conv_plan_info.phases) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -90,7 +91,13 @@ typedef struct dts_conv_args {
   int32_t n, hin, win;
   int32_t cout;
   int32_t ksize;                  /* 1 or 3 (pad ksize/2, stride 1) */
-  int32_t up;                     /* 1: nearest 2x upsample of the input fused into the gather (networks.py:82-83) */
+  int32_t up;                     /* 1: nearest 2x upsample of the input fused into the gather (networks.py:82-83);
+                                     2 (DTS_F16X3, ksize 3 only): the same convolution as four 2x2 convolutions over the low-resolution input, one
+                                     per output phase (py, px) = (y & 1, x & 1).  `w` is then the phase-packed weight [4][cout][2][2][c1]: phase
+                                     2*py + px, taps (ty, tx) row-major at the low-resolution offsets (ty - 1 + py, tx - 1 + px), each tap the sum
+                                     of the 3x3 taps that fall on that input pixel (rows, py = 0: {w0, w1+w2}; py = 1: {w0+w1, w2}; columns
+                                     alike), `acc_scale` that tensor's power of two; the output is [n][2*hin][2*win][cout] as for 1, 4/9 of the
+                                     multiply-adds.  Only launches for which dts_conv_takes_phases() returns 1 accept it */
   float out_scale;                /* out = (conv + bias + bias_nc + residual) * out_scale  (networks.py:179,186 skip_scale) */
   int32_t dtype;
   void* workspace;                /* optional scratch (16-byte aligned) for split-K partial sums; NULL disables split-K */
@@ -125,6 +132,10 @@ int dts_conv_fuses_gn(const dts_conv_args* a);
 /* 1 if dts_conv2d accepts a->skip_* for this launch (DTS_F16X3, 3x3 on the ping-pong kernel with a grid that needs no K split, no residual /
  * out_split2 / upsample of x1), else 0: the caller then runs the 1x1 layer as its own launch and passes its output as `residual`. */
 int dts_conv_folds_skip(const dts_conv_args* a);
+/* 1 if dts_conv2d accepts a->up == 2 for this launch (DTS_F16X3, 3x3, cout a multiple of 128 or 192, no x2 / gn_coef / skip_* / out_split2,
+ * a grid that neither wants nor is forced to a K split, hin*win % 64 == 0 when stats_out is given, DTS_CONV_UP_PHASES not 0), else 0: the
+ * caller then passes the 3x3 weight with up = 1.  A residual is allowed. */
+int dts_conv_takes_phases(const dts_conv_args* a);
 /* which kernel dts_conv2d takes for these arguments (shape, dtype, residual / gn_coef presence; tuning knobs included): 0 = the 4-wave
  * implicit-GEMM kernel, 6 / 4 = the 8-wave ping-pong / halo kernel with 192- / 128-cout blocks, -1 = invalid arguments.  Measurement aid:
  * bench.py attributes its per-launch times and algorithmic bytes to the kernel name a trace will show. */
@@ -139,12 +150,13 @@ typedef struct dts_conv_plan_info {
   int32_t tile, waves, stages, pf;        /* conv_igemm_kernel: cout tile 64 | 128 | 192, waves 4 | 8, LDS ring depth 2 | 3 | 4, fragment prefetch; 0 otherwise */
   int32_t gn, sk, dbg;                    /* conv_pp_kernel: fused GroupNorm apply, folded skip convolution, diagnostic form (0 in the product library) */
   int32_t splits, ks_per_split;           /* K split (grid.y; > 1: f32 partial slabs + the reduce pass) and K steps per split */
-  int32_t n_ct, n_pt, nblk;               /* cout tiles, pixel tiles, grid.x = n_ct * n_pt */
+  int32_t n_ct, n_pt, nblk;               /* cout tiles, pixel tiles, grid.x = n_ct * n_pt (phases = 1: tiles of low-resolution pixels, grid.x = 4 * n_ct * n_pt) */
   int32_t threads, lds_bytes;             /* block size, dynamic LDS */
   int32_t stats_in_kernel, stats_in_reduce, stats_written;      /* who writes stats_out; stats_written as dts_conv2d will report it */
   int32_t epi_rows;                       /* f32 outputs: 1 / 2 = a row-layout epilogue, 0 = the accumulator-layout one */
   int32_t fuses_gn, folds_skip;           /* as dts_conv_fuses_gn / dts_conv_folds_skip */
   int32_t refused;
+  int32_t phases;                         /* 1: the phase form of conv_igemm_kernel (up == 2), else 0 */
 } dts_conv_plan_info;
 int dts_conv_plan(const dts_conv_args* a, dts_conv_plan_info* out);
 int dts_conv2d(dts_conv_args* a, dts_stream s);      /* writes a->stats_written; no state is kept between calls (thread-safe) */

@@ -2,8 +2,14 @@
 """Per-shape throughput of dts_conv2d on the ADM-64 / classifier layer shapes (tuning harness, GPU box only).
 Times each shape with HIP events (GPU kept busy ahead of the measured launch) and prints TFLOP/s.  `--variants` times kernel
 variants (tuning knobs, dts_set_tuning) INTERLEAVED in one process, round by round, on random data, and checks that every variant
-produces bit-identical outputs:   python tools/conv_bench.py --stats --variants conv_variant=0 conv_variant=1"""
+produces bit-identical outputs:   python tools/conv_bench.py --stats --variants conv_variant=0 conv_variant=1
+With --up --dtype f16x3 the weights carry their phase tensors (pack_conv_weight(.., up_phases=True)), so conv_up_phases=0 / 1 is the
+nine-tap gather against the phase form (another summation order: the outputs' largest difference is printed instead of "identical"):
+    python tools/conv_bench.py --up --dtype f16x3 --stats --only 384-\>384 576-\>576 768-\>768 \
+        --variants conv_up_phases=0 conv_up_phases=1 conv_up_phases=0 --json out.json
+(the same variant listed twice gives the spread of repeated runs in that process)."""
 import argparse
+import json
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,9 +41,13 @@ def main():
     ap.add_argument('--no-res', action='store_true', help='no residual input')
     ap.add_argument('--up', action='store_true', help='fused nearest-2x upsample of the input (the listed resolution is the INPUT; implies --no-res)')
     ap.add_argument('--variants', nargs='*', default=None, help='e.g. conv_variant=0 conv_variant=1 (interleaved A/B)')
+    ap.add_argument('--only', nargs='*', default=None, help='only the shapes whose name contains one of these')
+    ap.add_argument('--json', default=None, help='(with --variants) also write the rows to this file')
     a = ap.parse_args()
     if a.set == '128':
         SHAPES[:] = SHAPES_128
+    if a.only:
+        SHAPES[:] = [s_ for s_ in SHAPES if any(o in s_[0] for o in a.only)]
     if a.variants:
         return ab(a)
     dt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[a.dtype]
@@ -74,11 +84,12 @@ def ab(a):
     dt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32, 'f16x3': torch.float32}[a.dtype]
     variants = [dict((kv.split('=')[0], int(kv.split('=')[1])) for kv in v.split(',')) for v in a.variants]
     tot = [[0.0, 0.0] for _ in variants]
+    rows = []
     for name, r, cin, cout, k in SHAPES:
         x = torch.randn(a.n, r, r, cin, device='cuda').to(dt)
         w = (torch.randn(cout, k, k, cin, device='cuda') / (cin * k * k) ** 0.5).to(dt)
         if x3:
-            w = ops.pack_conv_weight(torch.randn(cout, cin, k, k, device='cuda') / (cin * k * k) ** 0.5, ops.F16X3)
+            w = ops.pack_conv_weight(torch.randn(cout, cin, k, k, device='cuda') / (cin * k * k) ** 0.5, ops.F16X3, up_phases=a.up and k == 3)
             x = ops.SplitAct(ops.split3_f16(x), cin)
         b = torch.randn(cout, device='cuda')
         ro = 2 * r if a.up else r
@@ -86,10 +97,13 @@ def ab(a):
         outs = [torch.empty(a.n, ro, ro, cout, device='cuda', dtype=dt) for _ in variants]
         ts = [[] for _ in variants]
         stats = [None] * len(variants)
+        phased = [0] * len(variants)
         for rnd in range(a.iters + 1):
             for vi, v in enumerate(variants):
                 for kk, val in v.items():
                     _lib.set_tuning(kk, val)
+                if rnd == 0:
+                    phased[vi] = ops.conv_plan(x, w, b, residual=res, out=outs[vi], gn_stats=a.stats, up=a.up)['phases']
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda._sleep(200_000)
                 e0.record()
@@ -103,13 +117,32 @@ def ab(a):
                     _lib.set_tuning(kk, -1)
         fl = 2.0 * a.n * ro * ro * cout * cin * k * k
         same = all(torch.equal(outs[0], o) for o in outs[1:])
-        same_st = all((stats[0] is None) == (s_ is None) and (s_ is None or torch.allclose(stats[0], s_, rtol=1e-5, atol=1e-3)) for s_ in stats[1:])
+        mixed = len(set(phased)) > 1         # the phase form sums in another order and files its strips per phase: not bit-identical to the gather
+        if mixed:
+            img = lambda s_: None if s_ is None else s_.double().view(a.n, -1, cout, 2).sum(1)        # per-image moments are layout-free
+            same_st = all((stats[0] is None) == (s_ is None) and (s_ is None or torch.allclose(img(stats[0]), img(s_), rtol=1e-5, atol=1e-2)) for s_ in stats[1:])
+        else:
+            same_st = all((stats[0] is None) == (s_ is None) and (s_ is None or torch.allclose(stats[0], s_, rtol=1e-5, atol=1e-3)) for s_ in stats[1:])
         row = f'{name:22s} P={a.n * ro * ro:7d} K={cin * k * k:6d}'
+        rec = dict(shape=name, n=a.n, up=bool(a.up), dtype=a.dtype, stats=bool(a.stats), variants=[])
         for vi in range(len(variants)):
-            ms = sorted(ts[vi])[len(ts[vi]) // 2]
+            t_ = sorted(ts[vi])
+            ms = t_[len(t_) // 2]
             tot[vi][0] += fl; tot[vi][1] += ms
-            row += f' | {a.variants[vi]}: {ms * 1e3:7.1f} us {fl / ms / 1e9:7.1f} TF/s'
-        print(row + f' | outputs {"identical" if same else "DIFFER"}, stats {"ok" if same_st else "DIFFER"}', flush=True)
+            row += f' | {a.variants[vi]}{" [phases]" if phased[vi] else ""}: {ms * 1e3:7.1f} us ({t_[0] * 1e3:.1f}..{t_[-1] * 1e3:.1f}) {fl / ms / 1e9:7.1f} TF/s'
+            rec['variants'].append(dict(knobs=a.variants[vi], phases=int(phased[vi]), us_median=ms * 1e3, us_min=t_[0] * 1e3, us_max=t_[-1] * 1e3))
+        if mixed:
+            diff = max(float((outs[0] - o).abs().max()) for o in outs[1:])
+            verdict = f'outputs differ by at most {diff:.2e} (max |out| {float(outs[0].abs().max()):.2f})'
+            rec['max_abs_diff'] = diff
+        else:
+            verdict = f'outputs {"identical" if same else "DIFFER"}'
+        rec['stats_ok'] = bool(same_st)
+        rows.append(rec)
+        print(row + f' | {verdict}, stats {"ok" if same_st else "DIFFER"}', flush=True)
+    if a.json:
+        with open(a.json, 'w') as f:
+            json.dump(dict(tool='tools/conv_bench.py', iters=a.iters, rows=rows), f, indent=1)
     print('unweighted totals: ' + ' | '.join(f'{a.variants[vi]}: {tot[vi][0] / tot[vi][1] / 1e9:.1f} TF/s' for vi in range(len(variants))))
 
 

@@ -13,9 +13,9 @@ LIB = os.path.join(ROOT, 'diffusion_tts_amd', 'libdts_hip_stamps.so')
 def build():
     csrc = os.path.join(ROOT, 'diffusion_tts_amd', 'csrc')
     objs = []
-    for src in ['conv_igemm.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip']:
+    for src in ['conv_igemm.hip', 'conv_igemm_phase.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip']:
         o = os.path.join('/tmp', 'stamps_' + src.replace('.hip', '.o'))
-        if src == 'conv_igemm.hip' or not os.path.exists(o) or os.path.getmtime(os.path.join(csrc, src)) > os.path.getmtime(o):
+        if src.startswith('conv_igemm') or not os.path.exists(o) or os.path.getmtime(os.path.join(csrc, src)) > os.path.getmtime(o):
             extra = ['-mllvm', '-amdgpu-mfma-vgpr-form=1'] if src == 'attention.hip' else []
             subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-DDTS_STAMPS', '-DDTS_DIAG_KERNELS', *extra, '-c',
                                    os.path.join(csrc, src), '-o', o], stderr=subprocess.DEVNULL)
