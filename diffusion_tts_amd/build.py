@@ -88,7 +88,8 @@ def check_m0(obj):
         return -1
     with tempfile.TemporaryDirectory() as tmp:
         dev = _device_object(obj, tmp)
-        dis = subprocess.run([OBJDUMP, '-d', dev], capture_output=True, text=True).stdout
+        # (by its name inside the directory: objdump's header line repeats the path it was given, and a random directory name can contain "m0")
+        dis = subprocess.run([OBJDUMP, '-d', os.path.basename(dev)], capture_output=True, text=True, cwd=tmp).stdout
         notes = subprocess.run([READELF, '--notes', dev], capture_output=True, text=True).stdout if os.path.exists(READELF) else ''
     name = os.path.basename(obj)
     # our statement is `s_mov_b32 m0, <scalar operand>`; under SGPR pressure hipcc hands it vcc_lo / vcc_hi as that operand

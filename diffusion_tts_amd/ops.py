@@ -401,22 +401,33 @@ def split2_f16(x):
     return out
 
 
-def conv_in3(x, w, bias, cout, dtype):
-    """x f32 NCHW [n,3,h,w]; w f32 OIHW [cout,3,3,3] -> NHWC [n,h,w,cout]."""
-    n, c, h, wd = x.shape
-    assert c == 3
-    out = torch.empty((n, h, wd, cout), dtype=dtype, device=x.device)
-    _call('dts_conv_in3', _ptr(x, 'x', torch.float32), _ptr(w, 'w', torch.float32), _ptr(bias, 'bias', torch.float32),
-          _ptr(out), dt_code(dtype), n, h, wd, cout)
+def _out(who, out, shape, dtype, device):
+    """the output tensor of an op: a fresh one, or the caller's `out` -- a contiguous GPU tensor (_ptr checks that where it is passed on) of
+    exactly this shape and type on the inputs' device -- which is then what the op returns"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not torch.is_tensor(out) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device:
+        raise ValueError(f'{who}: out {tuple(out.shape)} {out.dtype} on {out.device} != {tuple(shape)} {dtype} on {device}'
+                         if torch.is_tensor(out) else f'{who}: out is a {type(out).__name__}')
     return out
 
 
-def conv_out3(x, w_ohwi, bias):
-    """x NHWC [n,h,w,c]; w f32 [3,3,3,c] (O,kh,kw,I) -> f32 NCHW [n,3,h,w]."""
+def conv_in3(x, w, bias, cout, dtype, out=None):
+    """x f32 NCHW [n,3,h,w]; w f32 OIHW [cout,3,3,3] -> NHWC [n,h,w,cout] (written into `out` where given)."""
+    n, c, h, wd = x.shape
+    assert c == 3
+    out = _out('conv_in3', out, (n, h, wd, cout), dtype, x.device)
+    _call('dts_conv_in3', _ptr(x, 'x', torch.float32), _ptr(w, 'w', torch.float32), _ptr(bias, 'bias', torch.float32),
+          _ptr(out, 'out', dtype), dt_code(dtype), n, h, wd, cout)
+    return out
+
+
+def conv_out3(x, w_ohwi, bias, out=None):
+    """x NHWC [n,h,w,c]; w f32 [3,3,3,c] (O,kh,kw,I) -> f32 NCHW [n,3,h,w] (written into `out` where given)."""
     n, h, wd, c = x.shape
-    out = torch.empty((n, 3, h, wd), dtype=torch.float32, device=x.device)
+    out = _out('conv_out3', out, (n, 3, h, wd), torch.float32, x.device)
     _call('dts_conv_out3', _ptr(x), dt_code(x.dtype), _ptr(w_ohwi, 'w', torch.float32), _ptr(bias, 'bias', torch.float32),
-          _ptr(out), n, h, wd, c)
+          _ptr(out, 'out', torch.float32), n, h, wd, c)
     return out
 
 
@@ -629,15 +640,16 @@ def attention_x3_ok(t, d):
     return d == 64 and t >= 128 and os.environ.get('DTS_X3_FUSE_IMAGES', '1') != '0'     # (0: A/B aid -- f32 tensors + split passes)
 
 
-def cross_attention(q, kv, heads, scale, kv_rows=None):
+def cross_attention(q, kv, heads, scale, kv_rows=None, out=None):
     """q [n, tq, heads*d], kv [m, tk, 2*heads*d] (k | v blocks; 1 <= tk <= 128) -> [n, tq, heads*d] (dts_cross_attention; float16 / bfloat16).
-    kv_rows: int32 [n] on the device, sample i attends to kv[kv_rows[i]] (entries in [0, m)); None: m == n, row for row."""
+    kv_rows: int32 [n] on the device, sample i attends to kv[kv_rows[i]] (entries in [0, m)); None: m == n, row for row.
+    out: written and returned where given."""
     n, tq, c = q.shape
     m, tk, c2 = kv.shape
     if c2 != 2 * c or c % heads or (kv_rows is None and m != n) or (kv_rows is not None and tuple(kv_rows.shape) != (n,)):
         raise ValueError(f'cross_attention: q {tuple(q.shape)}, kv {tuple(kv.shape)}, {heads} heads' + ('' if kv_rows is None else f', kv_rows {tuple(kv_rows.shape)}'))
-    out = torch.empty((n, tq, c), dtype=q.dtype, device=q.device)
-    _call('dts_cross_attention', _ptr(q, 'q'), _ptr(kv, 'kv', q.dtype), _ptr(kv_rows, 'kv_rows', torch.int32), m, _ptr(out), dt_code(q.dtype),
+    out = _out('cross_attention', out, (n, tq, c), q.dtype, q.device)
+    _call('dts_cross_attention', _ptr(q, 'q'), _ptr(kv, 'kv', q.dtype), _ptr(kv_rows, 'kv_rows', torch.int32), m, _ptr(out, 'out', q.dtype), dt_code(q.dtype),
           n, tq, tk, heads, c // heads, float(scale))
     return out
 

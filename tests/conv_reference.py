@@ -149,7 +149,8 @@ CASES = collections.OrderedDict()
 
 def _case(name, form, modes, n, h, w, c1, cout, k=3, c2=0, up=False, ep='b', scale=1.0, stats=False, knobs=(), variants=('int',), gn=False,
           skip=None, split2=False, splits=None, note=''):
-    """ep: which epilogue operands are present -- b bias, n bias_nc, N bias_nc as a column slice of a [n, 2*cout] tensor, r residual.
+    """ep: which epilogue operands are present -- b bias, B bias handed over ONE FLOAT INTO ITS STORAGE (not 16-byte aligned: the first
+    convolution's route depends on it), n bias_nc, N bias_nc as a column slice of a [n, 2*cout] tensor, r residual.
     h, w: the INPUT size (the output is twice that with up).  knobs: ((name, value), ...) set around the launch.
     splits: how K is split, which decides whether the kernel's OWN epilogue runs or the reduce pass's (ops.conv_kernel cannot tell them
     apart, and left alone the launchers split most small grids by an estimate of their own):
@@ -212,6 +213,19 @@ for _s in (2, 3, 8):
     for _nk, _c16 in ((18, 128), (27, 192)):
         _case(f'split{_s}_nk{_nk}_16bit', 'igemm_splitk', H16, 2, 8, 8, _c16, 128, ep='b', splits=_s)
         _case(f'split{_s}_nk{_nk}_32bit', 'igemm_splitk', W32, 2, 8, 8, _c16 // 2, 128, ep='b', splits=_s)
+# the reduce pass is a template over its slab count (conv_splitk_reduce_kernel<T, SPLITS> and conv_splitk_reduce_stats_kernel<T, SPLITS>,
+# SPLITS 2..8); the cases above end at 2, 3, 6 and 7 slabs.  SPLITS 4 and 5 at nk = 18 (4 -> 5 + 5 + 5 + 3, 5 -> 4 + 4 + 4 + 4 + 2), SPLITS 8 at
+# nk = 36 (8 -> seven splits of 5 and one of 1); each once through the plain reduce kernel and once (`_stats`: 2 strips of 64 pixels) through
+# the one that also writes the strip statistics
+for _s, _nk, _c16 in ((4, 18, 128), (5, 18, 128), (8, 36, 256)):
+    for _st in (False, True):
+        _sfx = '_stats' if _st else ''
+        _case(f'split{_s}_nk{_nk}_16bit{_sfx}', 'igemm_splitk', H16, 2, 8, 8, _c16, 128, ep='b', stats=_st, splits=_s)
+        _case(f'split{_s}_nk{_nk}_32bit{_sfx}', 'igemm_splitk', W32, 2, 8, 8, _c16 // 2, 128, ep='b', stats=_st, splits=_s)
+# the plain reduce kernel's grid-stride loop: P * cout / 4 = 32775 * 16 = 524,400 threads' worth against the cap of 2048 blocks x 256 =
+# 524,288: 112 threads take a SECOND trip (the last 7 pixels: 448 output elements).  32775 pixels are no whole strips, so the plain kernel
+# runs whatever is asked.  Two f32 slabs of 32775 x 64: 16.8 MB of the 96 MB workspace.  nk = 9 (16-bit: 5 + 4) / 18 (9 + 9).
+_case('split2_reduce_2trips', 'igemm_splitk', ALL, 1, 75, 437, 64, 64, ep='bnr', splits=2)
 _case('split3_full_16bit', 'igemm_splitk', H16, 2, 8, 8, 192, 192, ep='bNr', scale=0.5, stats=True, splits=3)
 _case('split3_full_32bit', 'igemm_splitk', W32, 2, 8, 8, 96, 192, ep='bNr', scale=0.5, stats=True, splits=3)
 _case('split2_ragged', 'igemm_splitk', ALL, 3, 5, 7, 128, 64, ep='bnr', splits=2)
@@ -278,6 +292,10 @@ _case('pp192_split2_c192', 'pp_splitk', PPM, 1, 16, 16, 192, 192, ep='b', knobs=
 _case('pp128_split3_c192', 'pp_splitk', PPM, 1, 16, 16, 192, 128, ep='bnr', stats=True, knobs=_PP, splits=3)
 _case('pp192_split3_c320', 'pp_splitk', PPM, 1, 16, 16, 320, 192, ep='bnr', scale=0.5, stats=True, knobs=_PP, splits=3)
 _case('pp128_split2_c320', 'pp_splitk', PPM, 2, 16, 16, 320, 128, ep='b', knobs=_PP, splits=2)
+# the reduce pass at 5 and 8 slabs behind the ping-pong kernel: 5 chunks -> 1 + 1 + 1 + 1 + 1 (f16x3: 10 -> five splits of 2), 8 chunks -> eight
+# splits of 1 (f16x3: 16 -> eight of 2); the first with the strip statistics (the reduce pass's statistics kernel), the second without
+_case('pp192_split5_c320', 'pp_splitk', PPM, 1, 16, 16, 320, 192, ep='br', stats=True, knobs=_PP, splits=5)
+_case('pp128_split8_c512', 'pp_splitk', PPM, 1, 16, 16, 512, 128, ep='bn', knobs=_PP, splits=8)
 _case('pp192x2_32x32_cat_split2', 'pp_splitk', PPM, 1, 32, 32, 64, 384, c2=64, ep='bn', stats=True, knobs=_PP, splits=2)
 _case('pp128x2_16x16_n2_split2', 'pp_splitk', PPM, 2, 16, 16, 128, 256, ep='bN', scale=0.5, stats=True, knobs=_PP, splits=2)
 _case('pp_auto_c128', 'pp192', PPM, 2, 16, 16, 128, 192, ep='bnr', stats=True, knobs=_PP, splits=-1, note='whatever the launcher\'s estimate picks')
@@ -304,6 +322,32 @@ _case('out3_tiled_16x16', 'out3_tiled', F3, 2, 16, 16, 64, 3, ep='b')
 _case('out3_tiled_32x48', 'out3_tiled', F3, 1, 32, 48, 192, 3, ep='b')
 _case('out3_direct_12x20', 'out3_direct', F3, 2, 12, 20, 64, 3, ep='b')
 _case('out3_direct_12x20_c192', 'out3_direct', F3, 1, 12, 20, 192, 3, ep='b')
+# The loops of these kernels whose trip count the launcher derives from the size (small_trips() restates the rules; tests/test_conv_reference.py
+# asserts every number written here).  In the cases above every such loop makes ONE trip.
+# conv_in3_mfma_kernel, `seg += gridDim.x * 4`: 67 x 62 = 4154 segments of 16 pixels, 2 per wave -> 520 blocks = 2080 waves; 2074 waves take a
+# second segment, the last 6 take one
+_case('in3_mfma_67x992', 'in3_mfma', F3, 1, 67, 992, 3, 64, ep='b')
+# 260 x 253 = 65780 segments, 8 per wave -> 2056 blocks, CAPPED at 2048 = 8192 waves: eight trips for every wave and a NINTH for 244 of them
+# (65780 - 8 * 8192).  One mode: the float64 reference takes 2.3 GB.
+_case('in3_mfma_260x4048', 'in3_mfma', ('bf16',), 1, 260, 4048, 3, 64, ep='b')
+# conv_in3_kernel, `pbase += gridDim.x * 256`: 1,048,640 pixels against the cap of 4096 blocks x 256 = 1,048,576: block 0 takes a second trip
+# of 64 pixels, through the LDS staging slab its first trip left behind
+_case('in3_direct_928x1130_c8', 'in3_direct', F3, 1, 928, 1130, 3, 8, ep='b')
+# its staging in groups of GRP = 8 output chunks of 16 bytes: cout 40 = 5 chunks in 16-bit (one ragged group), 10 in f32 (a full group and a
+# ragged one of 2).  (cout 64 / 128 / 192 above: whole groups only)
+_case('in3_direct_12x20_c40', 'in3_direct', F3, 2, 12, 20, 3, 40, ep='b')
+# a shape the matrix-core kernel takes (w % 16 == 0, cout 64) with a bias that is not 16-byte aligned: the launcher must take the direct kernel
+# (the other one reads the bias as float4)
+_case('in3_direct_16x16_unaligned_bias', 'in3_direct', F3, 1, 16, 16, 3, 64, ep='B')
+# conv_out3_kernel (4 lanes per pixel), `pix0 += gridDim.x * 64`: 524,320 pixels against the cap of 8192 blocks x 64 = 524,288: 32 pixels in a
+# second trip
+_case('out3_direct_464x1130_c8', 'out3_direct', F3, 1, 464, 1130, 8, 3, ep='b')
+# c = 48: three channel chunks of 16 in the tiled f32 kernel; 48 % 32 != 0 sends the 16-bit modes to the direct kernel (6 chunks over 4 lanes)
+_case('out3_tiled_16x16_c48', 'out3_tiled', ('f32',), 1, 16, 16, 48, 3, ep='b')
+_case('out3_direct_16x16_c48', 'out3_direct', H16, 1, 16, 16, 48, 3, ep='b')
+
+# the cases whose float64 reference is large (hundreds of MB to 2.3 GB): computed where they are used and dropped, never cached
+LARGE = ('in3_mfma_260x4048', 'in3_direct_928x1130_c8', 'out3_direct_464x1130_c8')
 
 
 def launches():
@@ -343,6 +387,71 @@ def effective_splits(case, mode):
         return 1, nk
     per = -(-nk // s)
     return -(-nk // per), per
+
+
+def small_route(case, mode):
+    """the kernel a first / last convolution takes -- the launchers' rules restated (dts_conv_in3, dts_conv_out3: conv_small.hip).  The first:
+    the matrix-core kernel iff w % 16 == 0, cout is 64 / 128 / 192 and the bias (if any) is 16-byte aligned.  The last: the tiled kernel iff
+    h % 16 == 0, w % 16 == 0 and c is whole chunks of 4 vectors (16 channels in f32, 32 in 16-bit)."""
+    if case.form.startswith('in3'):
+        return 'in3_mfma' if case.w % 16 == 0 and case.cout in (64, 128, 192) and 'B' not in case.ep else 'in3_direct'
+    assert case.form.startswith('out3')
+    return 'out3_tiled' if case.h % 16 == 0 and case.w % 16 == 0 and case.c1 % (16 if mode == 'f32' else 32) == 0 else 'out3_direct'
+
+
+Trips = collections.namedtuple('Trips', 'units per_wave blocks per_pass trips last_start')
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def small_trips(case, mode):
+    """The size-driven loop of the kernel small_route() names, from the launchers' rules restated: units = what the loop walks (segments of 16
+    pixels in conv_in3_mfma_kernel, pixels elsewhere), per_wave = segments a wave is meant to take (the matrix-core kernel only: nseg / 2048
+    clamped to 1..8), blocks = the grid after its cap (2048 / 4096 / 8192), per_pass = units the whole grid covers in one trip, trips = the
+    most trips any thread makes, last_start = the first output PIXEL of the last trip.  The tiled last convolution has no such loop."""
+    route, npix = small_route(case, mode), case.n * case.h * case.w
+    if route == 'in3_mfma':
+        nseg = case.n * case.h * (case.w // 16)
+        spw = max(1, min(8, nseg // 2048))
+        blocks = min(_ceil(nseg, 4 * spw), 2048)
+        trips = _ceil(nseg, 4 * blocks)
+        return Trips(nseg, spw, blocks, 4 * blocks, trips, (trips - 1) * 4 * blocks * 16)
+    if route == 'in3_direct':
+        blocks = min(_ceil(npix, 256), 4096)
+        trips = _ceil(npix, 256 * blocks)
+        return Trips(npix, None, blocks, 256 * blocks, trips, (trips - 1) * 256 * blocks)
+    if route == 'out3_direct':
+        blocks = min(_ceil(4 * npix, 256), 8192)
+        trips = _ceil(npix, 64 * blocks)
+        return Trips(npix, None, blocks, 64 * blocks, trips, (trips - 1) * 64 * blocks)
+    return Trips(npix, None, case.n * (case.h // 16) * (case.w // 16), npix, 1, 0)
+
+
+def in3_direct_groups(case, mode):
+    """chunks per staging round of conv_in3_kernel: cout / (channels of a 16-byte chunk) in groups of GRP = 8, the last one ragged"""
+    nchunk = case.cout // (4 if mode == 'f32' else 8)
+    return [min(8, nchunk - c0) for c0 in range(0, nchunk, 8)]
+
+
+def reduce_trips(case, mode):
+    """the grid-stride loop of conv_splitk_reduce_kernel (launch_reduce_n restated): one thread per 4 couts of a pixel, 2048 blocks of 256 at
+    the most.  Trips(units = P * cout / 4, -, blocks, per_pass, trips, last_start = first output pixel of the last trip)."""
+    ho, wo = out_hw(case)
+    total = case.n * ho * wo * (case.cout // 4)
+    blocks = min(_ceil(total, 256), 2048)
+    trips = _ceil(total, 256 * blocks)
+    return Trips(total, None, blocks, 256 * blocks, trips, (trips - 1) * 256 * blocks * 4 // case.cout)
+
+
+def last_trip_values(case, mode, o):
+    """the elements of the result o (NCHW) that the LAST trip of the case's size-driven loop writes (every channel of the pixels from
+    last_start on): if they were all zero, a launch that never made the trip could still equal the reference on a zeroed buffer"""
+    t = small_trips(case, mode) if case.splits == 0 else reduce_trips(case, mode)
+    n, _, h, w = o.shape
+    pix = torch.arange(t.last_start, n * h * w)
+    return o[pix // (h * w), :, (pix // w) % h, pix % w]
 
 
 def last_split_mask(case, mode):
@@ -394,7 +503,7 @@ def exact_inputs(case, mode, seed=0, variant='int'):
         wt = wt + _sparse(gen, wt.shape, d, [1, -1]) * 2.0 ** -12
     a = dict(x1=x[:, :case.c1].contiguous(), x2=x[:, case.c1:].contiguous() if case.c2 else None, w=wt, bias=None, bias_nc=None, residual=None,
              up=case.up, out_scale=case.scale, gn=None, skip=None)
-    if 'b' in case.ep:
+    if 'b' in case.ep or 'B' in case.ep:
         a['bias'] = _ints(gen, (cout,))
     if 'n' in case.ep:
         a['bias_nc'] = _ints(gen, (n, cout))

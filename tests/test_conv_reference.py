@@ -104,9 +104,20 @@ def test_the_route_table_is_complete():
     ups = [c for c in CASES.values() if c.form == 'igemm' and c.up]
     assert any(c.h % 2 and c.w % 2 for c in ups) and any(c.c2 for c in ups) and any('r' in c.ep for c in ups) and any(c.k == 1 for c in ups)
     assert all(c.up for c in CASES.values() if c.name.startswith('up_') or '_up' in c.name)
+    # the K split, implicit-GEMM kernel: the reduce pass is instantiated per slab count 2..8, and every one of them is reached -- by the
+    # plain reduce kernel and, at 4, 5 and 8 (the counts no other case has), by the one that writes the strip statistics too
+    ig = [c for c in CASES.values() if c.form == 'igemm_splitk']
+    assert {R.effective_splits(c, m)[0] for c in ig for m in c.modes} == set(range(2, 9))
+    with_stats = lambda c: c.stats and (R.out_hw(c)[0] * R.out_hw(c)[1]) % 64 == 0
+    for want in (False, True):
+        assert {R.effective_splits(c, m)[0] for c in ig for m in c.modes if with_stats(c) == want} >= {2, 3, 4, 5, 8}, want
+    assert {R.effective_splits(c, m)[0] for c in CASES.values() if c.form == 'pp_splitk' for m in c.modes} >= {2, 3, 5, 8}
+    # the cases that exist to pass a grid cap (SIZE_LOOPS below) cost what their cap makes them cost; every other launch stays cheap
+    sized = {name for name, *_ in SIZE_LOOPS if R.small_trips(CASES[name], CASES[name].modes[0]).trips > 1} | {'split2_reduce_2trips'}
+    assert set(R.LARGE) <= sized
     for c in CASES.values():
         ho, wo = R.out_hw(c)
-        assert 2.0 * c.n * ho * wo * c.cout * c.k * c.k * (c.c1 + c.c2) < 1.5e9, c.name
+        assert 2.0 * c.n * ho * wo * c.cout * c.k * c.k * (c.c1 + c.c2) < (4e9 if c.name in sized else 1.5e9), c.name
         assert all(k in ('conv_tile', 'conv_waves', 'conv_stages', 'conv_epi32', 'conv_splits', 'conv_variant') for k, _ in c.knobs)
         if 'N' in c.ep:
             assert c.n >= 2, 'a wider bias_nc shows only from the second sample on'
@@ -128,6 +139,90 @@ def test_the_route_table_is_complete():
     assert {dict(c.knobs).get('conv_epi32') for c in CASES.values() if c.split2 and (c.h * c.w) % 64 == 0} >= {0, 1, 2}
     # a launch asked for statistics it cannot give
     assert any(c.stats and (R.out_hw(c)[0] * R.out_hw(c)[1]) % 64 for c in CASES.values())
+
+
+# ---- loops whose trip count the launcher derives from the size ------------------------------------------------------------------------
+# (case, units the loop walks, segments per wave, blocks, most trips of a thread, units left for the last trip): the numbers the comments of
+# conv_reference.py state, here from its restatement of the launchers' rules (small_trips).  A changed cap or segments-per-wave rule in
+# conv_small.hip must be restated there, and then fails HERE unless the shapes still pass it.
+SIZE_LOOPS = [
+    ('in3_mfma_67x992', 4154, 2, 520, 2, 2074),                 # 2080 waves: 2074 take a second segment, 6 take one
+    ('in3_mfma_260x4048', 65780, 8, 2048, 9, 244),              # 2056 blocks asked for, 2048 given: a ninth trip for 244 waves
+    ('in3_direct_928x1130_c8', 1048640, None, 4096, 2, 64),     # cap 4096 * 256 = 1,048,576, + 64
+    ('out3_direct_464x1130_c8', 524320, None, 8192, 2, 32),     # cap 8192 * 64 = 524,288, + 32
+]
+
+
+def test_first_and_last_convolution_routes_and_trip_counts():
+    """every in3 / out3 case takes the kernel its form names, in every mode; the size-driven loops make the trips the table says; every OTHER
+    case makes exactly one (so the table is the whole multi-trip coverage); the ragged staging groups of conv_in3_kernel are reached"""
+    small = [c for c in CASES.values() if c.form.startswith('in3') or c.form.startswith('out3')]
+    for c in small:
+        for m in c.modes:
+            assert R.small_route(c, m) == c.form, (c.name, m)
+    table = {row[0]: row[1:] for row in SIZE_LOOPS}
+    for c in small:
+        for m in c.modes:
+            t = R.small_trips(c, m)
+            if c.name in table:
+                units, spw, blocks, trips, last = table[c.name]
+                assert (t.units, t.per_wave, t.blocks, t.trips) == (units, spw, blocks, trips), (c.name, t)
+                assert t.units - (trips - 1) * t.per_pass == last and 0 < last < t.per_pass, (c.name, t)
+                assert t.last_start == (trips - 1) * t.per_pass * (16 if c.form == 'in3_mfma' else 1)       # (a segment is 16 pixels)
+            else:
+                assert t.trips == 1, (c.name, t)
+    # the cap is passed by less than a block's worth of a wave each: the smallest shapes that take the trip
+    assert R.small_trips(CASES['in3_direct_928x1130_c8'], 'f32').units - 4096 * 256 == 64
+    assert R.small_trips(CASES['out3_direct_464x1130_c8'], 'f32').units - 8192 * 64 == 32
+    assert 65780 // 2048 >= 8 and -(-65780 // 32) == 2056 > 2048
+    # conv_in3_kernel's staging groups: whole groups in the older cases, ragged ones (5; 8 + 2) at cout 40, a single short group at cout 8
+    groups = {(c.name, m): R.in3_direct_groups(c, m) for c in small if c.form == 'in3_direct' for m in c.modes}
+    assert groups[('in3_direct_12x20_c40', 'bf16')] == [5] and groups[('in3_direct_12x20_c40', 'f16')] == [5]
+    assert groups[('in3_direct_12x20_c40', 'f32')] == [8, 2]
+    assert all(g == [8] * len(g) for (name, _), g in groups.items() if CASES[name].cout in (64, 128, 192))
+    # the bias of the unaligned case is what keeps it off the matrix-core kernel
+    c = CASES['in3_direct_16x16_unaligned_bias']
+    assert R.small_route(c._replace(ep='b'), 'f32') == 'in3_mfma' and R.small_route(c, 'f32') == 'in3_direct'
+    # c = 48 at 16 x 16: tiled in f32 (three chunks of 16), direct in 16-bit
+    assert R.small_route(CASES['out3_tiled_16x16_c48'], 'f32') == 'out3_tiled' and CASES['out3_tiled_16x16_c48'].c1 // 16 == 3
+    assert all(R.small_route(CASES['out3_tiled_16x16_c48'], m) == 'out3_direct' for m in R.H16)
+
+
+def test_the_reduce_pass_takes_its_second_trip():
+    """conv_splitk_reduce_kernel's grid-stride loop: 524,400 threads' worth against 2048 blocks of 256; every other split case makes one
+    trip; two slabs fit the workspace; the split is honoured in every mode"""
+    c = CASES['split2_reduce_2trips']
+    for m in c.modes:
+        t = R.reduce_trips(c, m)
+        assert (t.units, t.blocks, t.trips, t.units - t.per_pass) == (524400, 2048, 2, 112)
+        assert t.last_start == 32768 and 32775 - t.last_start == 7
+        assert R.effective_splits(c, m)[0] == 2
+    assert (75 * 437) % 64 != 0, 'whole strips would send a statistics request to the other reduce kernel'
+    assert 2 * 32775 * 64 * 4 < 96 << 20
+    for o in CASES.values():
+        if o.splits > 1 and o.name != c.name:
+            assert all(R.reduce_trips(o, m).trips == 1 for m in o.modes), o.name
+
+
+@pytest.mark.parametrize('name', [row[0] for row in SIZE_LOOPS] + ['split2_reduce_2trips'])
+def test_the_last_trip_writes_nonzero_values(name):
+    """what the last trip of a size-driven loop writes is not all zero in the reference (in every pixel; in every group of 4 couts of every
+    pixel for the reduce pass: one thread's float4), so a launch that skipped the trip cannot equal it; and the case stays inside the exactness
+    conditions with room (S <= 85 on the 3- and 8-channel inputs, where nearly every activation is nonzero)"""
+    case = CASES[name]
+    for mode in case.modes:
+        a, ref = _args_ref(name, mode)
+        last = R.last_trip_values(case, mode, ref.o)
+        t = R.small_trips(case, mode) if case.splits == 0 else R.reduce_trips(case, mode)
+        assert last.shape[0] == case.n * R.out_hw(case)[0] * R.out_hw(case)[1] - t.last_start > 0
+        nz = int((last != 0).sum())
+        print(f'{name} [{mode}]: last trip writes {last.numel()} elements, {nz} nonzero; max S {float(ref.S.max())}')
+        per_thread = last.reshape(-1, 4) if case.splits > 1 else last          # (the small kernels: a thread or a wave owns whole pixels)
+        assert bool((per_thread != 0).any(1).all()), 'what one thread writes in the last trip is all zero'
+        assert 2 * nz > last.numel()
+        if case.splits == 0:
+            assert float(ref.S.max()) <= 85.0
+        del a, ref, last
 
 
 # ---- teeth: mistakes a kernel could make, made HERE on the reference's own steps ----------------------------------------------------

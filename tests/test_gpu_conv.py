@@ -5,7 +5,10 @@ reference that shares no code with the library.  Two legs.
 EXACT LEG (test_exact).  The inputs of conv_reference.exact_inputs make every product and every partial sum, in any order, exactly
 representable in float32 and the result representable in the output type (conv_reference.assert_exact_conditions, asserted for every
 launch).  The output must EQUAL the reference; there is no tolerance in this leg.  The output tensor is the middle of a NaN-filled buffer:
-every element must have been written and the guard bands on both sides must still be NaN.  Where the launch reports GroupNorm strip
+every element must have been written and the guard bands on both sides must still be NaN (the first and last convolutions too: `out=`).
+Loops whose trip count a launcher derives from the size (the first / last convolutions' grids under their caps, the reduce pass) have cases
+that take the second trip; conv_reference.small_trips / reduce_trips restate the rules and each such case asserts, before it runs, that
+the reference is nonzero where only the last trip writes.  Where the launch reports GroupNorm strip
 statistics they must equal the float64 moments of the stored output (per 64-pixel strip for the implicit-GEMM kernel and the reduce pass,
 per image for the ping-pong kernel, whose strips are patch rows); where it cannot, `_gn_stats` must be None.  Each case asserts
 ops.conv_kernel's answer and the whole route of ops.conv_plan (tile, waves, ring depth, K split, who wrote the statistics:
@@ -197,25 +200,36 @@ def _launch(ops, case, mode, a, want_stats):
 
 
 def _small(ops, case, mode, a):
-    """the first / last convolution of a network (conv_small.hip): output NCHW on the CPU.  Nothing reports which kernel ran: the shapes
-    follow the launchers' rules -- dts_conv_in3 takes the matrix-core kernel iff w % 16 == 0 and cout is 64 / 128 / 192 (16-byte aligned
-    bias), else the direct one; dts_conv_out3 takes the tiled kernel iff h % 16 == 0, w % 16 == 0 and c % 32 == 0 (16 in f32), else the
-    direct one.  The ops allocate these outputs themselves, so there is no guard band here: equality only."""
+    """the first / last convolution of a network (conv_small.hip): (output NCHW on the CPU, the guard buffer).  Nothing reports which kernel
+    ran: the shapes follow the launchers' rules -- dts_conv_in3 takes the matrix-core kernel iff w % 16 == 0 and cout is 64 / 128 / 192 (16-byte
+    aligned bias), else the direct one; dts_conv_out3 takes the tiled kernel iff h % 16 == 0, w % 16 == 0 and c % 32 == 0 (16 in f32), else the
+    direct one (conv_reference.small_route restates them and tests/test_conv_reference.py holds every case's form to it).  The output is the
+    middle of a NaN-filled buffer handed over as `out=`, like every other launch of this file."""
     dt = STORE[mode]
     bias = None if a['bias'] is None else a['bias'].float().to(DEV)
+    if 'B' in case.ep:          # the same bias one float into its storage
+        store = torch.zeros(case.cout + 1, device=DEV)
+        store[1:] = bias
+        bias = store[1:]
+        assert bias.data_ptr() % 16 == 4 and bias.is_contiguous()
     if case.form.startswith('in3'):
-        out = ops.conv_in3(a['x1'].float().to(DEV).contiguous(), a['w'].float().to(DEV).contiguous(), bias, case.cout, dt)
+        buf, view = _guarded((case.n, case.h, case.w, case.cout), dt)
+        out = ops.conv_in3(a['x1'].float().to(DEV).contiguous(), a['w'].float().to(DEV).contiguous(), bias, case.cout, dt, out=view)
         torch.cuda.synchronize()
-        return R.nchw(out.cpu())
-    out = ops.conv_out3(R.nhwc(a['x1']).to(dt).to(DEV), a['w'].permute(0, 2, 3, 1).float().contiguous().to(DEV), bias)
+        assert out is view
+        return R.nchw(out.cpu()), torch.cat([buf[:GUARD], buf[-GUARD:]]).cpu()        # (the bands alone: the large cases' buffers stay on the device)
+    buf, view = _guarded((case.n, 3, case.h, case.w), torch.float32)
+    out = ops.conv_out3(R.nhwc(a['x1']).to(dt).to(DEV), a['w'].permute(0, 2, 3, 1).float().contiguous().to(DEV), bias, out=view)
     torch.cuda.synchronize()
-    return out.cpu()
+    assert out is view
+    return out.cpu(), torch.cat([buf[:GUARD], buf[-GUARD:]]).cpu()
 
 
 @pytest.mark.parametrize('name,mode,variant', R.launches(), ids=lambda v: str(v))
 def test_exact(ops, name, mode, variant):
     case = CASES[name]
-    a, ref = _exact(name, variant)
+    # (the large cases' references, up to 2.3 GB, live for this one test: _exact.__wrapped__ is the function without its cache)
+    a, ref = _exact.__wrapped__(name, variant) if name in R.LARGE else _exact(name, variant)
     small = case.form.startswith('in3') or case.form.startswith('out3')
     out_dt = torch.float32 if case.form.startswith('out3') else STORE[mode]
     ho, wo = R.out_hw(case)
@@ -226,10 +240,21 @@ def test_exact(ops, name, mode, variant):
         stats64 = R.image_stats64(want) if case.form.startswith('pp') else R.strip_stats64(want)
     R.assert_exact_conditions(ref, out_dt, stats64, a)
     if small:
-        got = _small(ops, case, mode, a)
-        print(f'{name} [{mode}]: {case.form}')
-        assert got.dtype == out_dt and torch.equal(got, want)
+        assert R.small_route(case, mode) == case.form
+        t = R.small_trips(case, mode)
+        if t.trips > 1:         # what only the last trip writes is not all zero: a launch without it cannot equal the reference
+            assert bool((R.last_trip_values(case, mode, want) != 0).any(1).all())
+        got, bands = _small(ops, case, mode, a)
+        print(f'{name} [{mode}]: {case.form}, {t.blocks} blocks, {t.trips} trip(s) of the size-driven loop'
+              + (f', staging groups {R.in3_direct_groups(case, mode)}' if case.form == 'in3_direct' else ''))
+        assert got.dtype == out_dt
+        assert not bool(torch.isnan(got).any()), 'an output element was never written'
+        assert torch.equal(got, want), f'{int((got != want).sum())} of {want.numel()} elements differ'
+        assert bool(torch.isnan(bands[:GUARD]).all()) and bool(torch.isnan(bands[-GUARD:]).all()), 'a store outside the output'
         return
+    if name == 'split2_reduce_2trips':
+        t = R.reduce_trips(case, mode)
+        assert t.trips == 2 and bool((R.last_trip_values(case, mode, want).reshape(-1, 4) != 0).any(1).all())
     got, st, buf, kernel = _launch(ops, case, mode, a, want_stats)
     split = {-1: 'by the launcher', 0: 'none'}.get(case.splits, case.splits)
     print(f'{name} [{mode}, {variant}]: kernel {kernel} ({case.form}), K split {split}, knobs {dict(case.knobs)}')
@@ -255,6 +280,26 @@ def test_exact(ops, name, mode, variant):
             assert torch.equal(st, R.strip_stats64(want).float())
         else:
             assert torch.equal(st, stats64.float())
+
+
+def test_first_and_last_convolution_refuse_a_wrong_out(ops):
+    """out= of conv_in3 / conv_out3 (every exact case above hands one over): a tensor of another shape, type, device or layout raises; the
+    allocating form gives the same bits"""
+    x = torch.randn(1, 3, 12, 20, generator=torch.Generator().manual_seed(1)).to(DEV)
+    w = torch.randn(64, 3, 3, 3, generator=torch.Generator().manual_seed(2)).to(DEV)
+    good = torch.empty(1, 12, 20, 64, dtype=torch.bfloat16, device=DEV)
+    assert ops.conv_in3(x, w, None, 64, torch.bfloat16, out=good) is good and torch.equal(good, ops.conv_in3(x, w, None, 64, torch.bfloat16))
+    for bad in (torch.empty(1, 12, 20, 128, dtype=torch.bfloat16, device=DEV), torch.empty(1, 12, 20, 64, dtype=torch.float16, device=DEV),
+                torch.empty(1, 12, 20, 64, dtype=torch.bfloat16), torch.empty(1, 12, 20, 128, dtype=torch.bfloat16, device=DEV)[..., ::2]):
+        with pytest.raises(ValueError):
+            ops.conv_in3(x, w, None, 64, torch.bfloat16, out=bad)
+    xl, wl = good, torch.randn(3, 3, 3, 64, generator=torch.Generator().manual_seed(3)).to(DEV)
+    o3 = torch.empty(1, 3, 12, 20, device=DEV)
+    assert ops.conv_out3(xl, wl, None, out=o3) is o3 and torch.equal(o3, ops.conv_out3(xl, wl, None))
+    for bad in (torch.empty(1, 3, 20, 12, device=DEV), torch.empty(1, 3, 12, 20, dtype=torch.float16, device=DEV), torch.empty(1, 3, 12, 20),
+                torch.empty(1, 3, 12, 40, device=DEV)[..., ::2]):
+        with pytest.raises(ValueError):
+            ops.conv_out3(xl, wl, None, out=bad)
 
 
 ROUTES = [  # (route, case, modes): one representative shape per route

@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import launch_rules as LR
 from gn_reference import FLOOR, K, REGIMES, bound, err, gn_ref64, groups_of, ref32, regime_input
 
 pytestmark = pytest.mark.gpu
@@ -269,12 +270,18 @@ def test_split_precision_output_is_the_normalised_tensor(ops, shape, form, pool)
     float32 pass): the float32 bound + 2^-22 (dts.h: the pair carries about 22 bits); the raw image reconstructs the un-normalised input
     (2x2-averaged in float64 when pooled) to 2^-22 * max |x|.  Both store forms: 16-byte lane-pair stores (default) and gn_fuse = 2.
     Largest ratio measured on an MI355X: 1.49."""
-    from diffusion_tts_amd import _lib
     n, c1, c2, h, w, adm = shape
     if pool and (h % 2 or w % 2):
         h, w = h + h % 2, w + w % 2                     # (5 x 7 -> 6 x 8)
-    cs = case('network_lo', n, c1, c2, h, w, adm)
+    check_split_images(ops, case('network_lo', n, c1, c2, h, w, adm), form, pool)
+
+
+def check_split_images(ops, cs, form, pool):
+    """the checks of test_split_precision_output_is_the_normalised_tensor on one case: -> the largest ratio of the split images"""
+    from diffusion_tts_amd import _lib
+    n, c1, c2, h, w = cs.n, cs.c1, cs.c2, cs.h, cs.w
     ref = cs.ref(pool)
+    worst = 0.0
     if form == 'gn_fuse2':
         _lib.set_tuning('gn_fuse', 2)
     try:
@@ -283,7 +290,7 @@ def test_split_precision_output_is_the_normalised_tensor(ops, shape, form, pool)
             only, _ = run(ops, cs, route, pool=pool, split_out=True)
             assert isinstance(img, ops.SplitAct) and tuple(img.shape) == tuple(ref[0].permute(0, 2, 3, 1).shape)
             assert torch.equal(only.data, img.data)
-            check_out(cs, route, split_value(img), ref, extra=2.0 ** -22, what=f'split image ({form})')
+            worst = max(worst, check_out(cs, route, split_value(img), ref, extra=2.0 ** -22, what=f'split image ({form})'))
             x = (cs.x1 if cs.x2 is None else torch.cat([cs.x1, cs.x2], 1)).double()
             if pool:
                 x = x.reshape(n, cs.c, h // 2, 2, w // 2, 2).sum((3, 5)) / 4.0
@@ -292,6 +299,69 @@ def test_split_precision_output_is_the_normalised_tensor(ops, shape, form, pool)
             assert eraw <= 2.0 ** -22
     finally:
         _lib.set_tuning('gn_fuse', -1)
+    return worst
+
+
+# ---- the second trip of the apply kernels' size-driven loops -----------------------------------------------------------------------------
+# At every shape above, a thread of gn_apply_rows_kernel makes ONE pair trip (n * hw <= 4096 * 2k) and a thread of gn_apply_kernel ONE
+# grid-stride trip (at most 98304 threads' worth against 4096 * 256).  launch_rules.gn_apply_plan restates gn_apply_impl; each case below
+# asserts which kernel serves it and the trips it makes before it runs (tests/test_launch_rules.py asserts the same without a GPU).
+DT = {'f32': torch.float32, 'bf16': torch.bfloat16, 'f16': torch.float16}
+
+
+def _sized(table, name, dt, **kw):
+    """the Case of a launch_rules entry, after asserting that the restated launcher sends it where the entry says"""
+    e = table[name]
+    plan = LR.gn_apply_plan(e.n, e.c1, e.c2, e.h, e.w, dt == 'f32', e.pool, **kw)
+    for field, want in e.expect.items():
+        assert getattr(plan, field) == want, (name, field, plan)
+    assert plan.trips == 2
+    return case('network_lo', e.n, e.c1, e.c2, e.h, e.w, True, dtype=DT[dt]), plan
+
+
+ROWS_CASES = [(name, dt) for name, e in LR.GN_ROWS_TWO_TRIPS.items() for dt in e.dtypes]
+
+
+@pytest.mark.parametrize('name,dt', ROWS_CASES, ids=[f'{n}-{d}' for n, d in ROWS_CASES])
+def test_row_apply_second_pair_trip(ops, name, dt):
+    """gn_apply_rows_kernel where every thread makes TWO pair trips (the stride p += 2k) at k = 1, 3 and 5 pixels per block pass, and the
+    ragged last block of a sample: one pair and the single-pixel tail (k = 1), a pair for every pixel row and the tail for two (k = 5).
+    Largest ratio measured on an MI355X: 1.03 (coefficient a of the bf16 case; outputs: 0.50 at k = 1, 0.73 at k = 5)."""
+    cs, plan = _sized(LR.GN_ROWS_TWO_TRIPS, name, dt)
+    assert plan.kernel == 'rows'
+    check_route(ops, cs, 'split')
+
+
+@pytest.mark.parametrize('name,form', [('c192', 'default'), ('c192', 'gn_fuse2'), ('c100+92', 'default')])
+def test_row_apply_second_pair_trip_split_images(ops, name, form):
+    """the same loop in the split-image instantiations, normalised and raw image: <float, SPLIT, W16> (16-byte lane-pair stores), <float,
+    SPLIT> under gn_fuse = 2, and <float, SPLIT> because c1 % 8 != 0 (a lane pair would straddle the concat).
+    Largest ratio measured on an MI355X: 0.99 (all three forms give the same image)."""
+    cs, plan = _sized(LR.GN_ROWS_TWO_TRIPS, name, 'f32', split=True, gn_fuse=2 if form == 'gn_fuse2' else -1)
+    assert plan.kernel == 'rows' and plan.w16 == (name == 'c192' and form == 'default')
+    check_split_images(ops, cs, form, False)
+
+
+GRID_CASES = [(name, dt) for name, e in LR.GN_GRID_TWO_TRIPS.items() for dt in e.dtypes]
+
+
+@pytest.mark.parametrize('name,dt', GRID_CASES, ids=[f'{n}-{d}' for n, d in GRID_CASES])
+def test_grid_stride_apply_second_trip(ops, name, dt):
+    """gn_apply_kernel past its cap of 4096 blocks x 256 threads by less than a block: the threads of the first blocks take a second trip
+    (idx += gridDim.x * blockDim.x), pooled (<T, true>) in all three types and unpooled (<float, false>: 384 chunks per row).
+    Largest ratio measured on an MI355X: 0.95 (coefficient a of the bf16 case; float32 outputs: 0.46 pooled, 0.50 unpooled)."""
+    cs, plan = _sized(LR.GN_GRID_TWO_TRIPS, name, dt)
+    assert plan.kernel == 'grid' and 0 < plan.threads - 4096 * 256 < 256
+    check_route(ops, cs, 'split', pool=LR.GN_GRID_TWO_TRIPS[name].pool)
+
+
+@pytest.mark.parametrize('name', ['pool_f32', 'wide_f32'])
+def test_grid_stride_apply_second_trip_split_images(ops, name):
+    """the same as split images: gn_apply_kernel<float, true, true> and <float, false, true>.
+    Largest ratio measured on an MI355X: 0.68 (unpooled; pooled 0.51)."""
+    cs, plan = _sized(LR.GN_GRID_TWO_TRIPS, name, 'f32', split=True)
+    assert plan.kernel == 'grid'
+    check_split_images(ops, cs, 'default', LR.GN_GRID_TWO_TRIPS[name].pool)
 
 
 # ---- exact cases ---------------------------------------------------------------------------------------------------------------

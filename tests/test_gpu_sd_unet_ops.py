@@ -38,6 +38,8 @@ import math
 import pytest
 import torch
 
+import launch_rules as LR
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
@@ -127,6 +129,59 @@ def test_cross_attention_shared_contexts_padded_heads_and_odd_lengths(ops, dtype
         assert float(((out.double() - ref).abs() / bound).max()) <= 1.0, tk
 
 
+GUARD = 4096
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+@pytest.mark.parametrize('case', LR.XATTN_CHUNK_LOOP, ids=lambda c: f'n{c.n}-h{c.heads}-d{c.d}-tq{c.tq}-tk{c.tk}')
+def test_cross_attention_chunk_loop(ops, dtype, case):
+    """The loop `for (qc = 0; qc < qchunks; ++qc)` of cross_attention_kernel at qchunks = 2, 4 and 8 (every other test of this file runs it
+    at 1; the SD U-Net at 16 candidates runs 8): q0 = (qblk * qchunks + qc) * 64 + wid * 16 for qc > 0, a ragged last chunk, and a last
+    block whose chunks run past tq (the wave-uniform break).  Nothing reports which form ran: launch_rules.xattn_plan restates the
+    launcher's rule and the table says what each shape must reach (asserted here and, without a GPU, in tests/test_launch_rules.py).
+    The output is the middle of a NaN-filled buffer: every row written, nothing outside.  xattn_reference and its bound, unchanged.
+    Measured on an MI355X (a record, not the source of the bound): max err/bound 0.34 .. 0.40 over the ten cases (the older cases of this
+    file: the same range), 0.30 .. 0.40 in every chunk slot of a block."""
+    n, heads, d, tq, tk = case.n, case.heads, case.d, case.tq, case.tk
+    assert LR.xattn_plan(n, heads, tq) == (case.chunks, case.qchunks, case.qblocks) and case.qchunks > 1
+    gen = g(1000 * tk + tq + d + n)
+    c = heads * d
+    q = (torch.randn(n, tq, c, generator=gen) * 1.5).to(DEV, dtype)
+    m = n if case.contexts is None else case.contexts
+    kv = torch.randn(m, tk, 2 * c, generator=gen).to(DEV, dtype)
+    rows = None if case.contexts is None else (torch.arange(n, dtype=torch.int32) * 7 % m).to(DEV)
+    scale = 1.0 / math.sqrt(d)
+    buf = torch.full((n * tq * c + 2 * GUARD,), float('nan'), dtype=dtype, device=DEV)
+    view = buf[GUARD:GUARD + n * tq * c].view(n, tq, c)
+    out = ops.cross_attention(q, kv, heads, scale, kv_rows=rows, out=view)
+    assert out is view
+    assert not bool(torch.isnan(out).any()), 'an output row was never written'
+    assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all()), 'a store outside the output'
+    ref, bound = xattn_reference(q, kv, heads, scale, dtype, kv_rows=rows)
+    ratio = (out.double() - ref).abs() / bound
+    del ref, bound
+    worst = float(ratio.max())
+    # per chunk position inside a block: a fault in the q0 of one qc shows there
+    per_qc = [float(ratio[:, [t for t in range(tq) if (t // 64) % case.qchunks == qc]].max()) for qc in range(case.qchunks)]
+    print(f'cross_attention chunk loop {str(dtype).split(".")[-1]} n={n} heads={heads} d={d} tq={tq} tk={tk}: qchunks {case.qchunks}, qblocks '
+          f'{case.qblocks}; max err/bound {worst:.3f}; per chunk slot {" ".join(f"{r:.3f}" for r in per_qc)}')
+    assert worst <= 1.0
+    if rows is not None:
+        assert rows.unique().numel() == m
+
+
+def test_cross_attention_out_argument(ops):
+    """out=: the op writes and returns the caller's tensor, and refuses one of another shape, type or layout"""
+    q = torch.randn(2, 70, 128, generator=g(3)).to(DEV, torch.float16)
+    kv = torch.randn(2, 9, 256, generator=g(4)).to(DEV, torch.float16)
+    out = torch.empty_like(q)
+    assert ops.cross_attention(q, kv, 2, 0.125, out=out) is out and torch.equal(out, ops.cross_attention(q, kv, 2, 0.125))
+    for bad in (torch.empty(2, 70, 64, dtype=torch.float16, device=DEV), torch.empty(2, 70, 128, dtype=torch.bfloat16, device=DEV),
+                torch.empty(2, 70, 128, dtype=torch.float16), torch.empty(2, 70, 256, dtype=torch.float16, device=DEV)[..., ::2]):
+        with pytest.raises(ValueError):
+            ops.cross_attention(q, kv, 2, 0.125, out=bad)
+
+
 def test_cross_attention_refuses_what_it_cannot_compute(ops):
     c = 128
     q = torch.zeros(1, 16, c, dtype=torch.float16, device=DEV)
@@ -141,8 +196,14 @@ def test_cross_attention_refuses_what_it_cannot_compute(ops):
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
-@pytest.mark.parametrize('c', [64, 320, 1280])
+@pytest.mark.parametrize('c', [8, 64, 320, 1280, 1544, 2048])
 def test_layer_norm(ops, dtype, c):
+    """c = 8: one lane holds the row; 1544 = 193 vectors: the fourth register vector (i = 3) on a single lane; 2048: all four whole
+    (launch_rules.LAYER_NORM_WIDTHS).  The widths up to 1280 stay inside three.
+    Measured on an MI355X (float16 / bfloat16; a record, not the source of the bound, which the output rounding u |y| nearly fills by
+    itself): c = 8: 0.928 / 0.943, c = 1544: 0.956 / 0.991, c = 2048: 0.983 / 0.990."""
+    if c in LR.LAYER_NORM_WIDTHS:
+        assert LR.layer_norm_vectors(c) == LR.LAYER_NORM_WIDTHS[c]
     gen = g(20 + c)
     rows = 37
     x = torch.randn(rows, c, generator=gen) * 1.5 + 0.3
