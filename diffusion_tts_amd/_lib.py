@@ -70,6 +70,7 @@ SIGNATURES = {
     'dts_pos_embedding': [_p, _p, _p, _i, _i, _i, _p],
     'dts_edm_precond_in': [_p, _p, _i, _f, _p, _p, _i, _i, _p],
     'dts_edm_precond_out': [_p, _p, _p, _p, _i, _i, _p],
+    'dts_precond_in': [_i, _p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p],
     'dts_split3_f16': [_p, _i, _p, _i, _p, _i64, _p],
     'dts_split2_f16': [_p, _i, _p, _i64, _p],
     'dts_attention_x3': [_p, _p, _i, _i, _i, _i, _i, _f, _p],
@@ -97,7 +98,7 @@ OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 120              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 121              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

@@ -11,9 +11,12 @@ a stub that keeps `class_name` and `state`, the module tree is walked through th
 with the reference's own state-dict key names.  Globals are resolved through an exact (module, name) allow-list of data constructors; everything else is refused, and the
 nested storage bytes are read by torch's restricted (`weights_only`) loader.
 
-Scope = the hot path's nets: EDMPrecond over DhariwalUNet (ADM) or SongUNet with the DDPM++ or the NCSN++
-options (Fourier embedding, residual encoder, [1,3,3,1] resampling: the `*-ve.pkl` files); VP/VE/iDDPM preconditioners, the 'skip'
-encoder / decoder and any other resampling filter raise NotImplementedError.
+Scope = the hot path's nets: any of the four preconditioner classes (EDMPrecond, VPPrecond, VEPrecond,
+iDDPMPrecond: networks.py:469-671; `EDMConfig.precond` = 'edm' | 'vp' | 've' | 'iddpm' with the scalars the class records, sigma_min /
+sigma_max from the file, and for iDDPM the file's own `u` table) over DhariwalUNet (ADM) or SongUNet with the DDPM++ or the NCSN++ options
+(Fourier embedding, residual encoder, [1,3,3,1] resampling: the `*-ve.pkl` files).  A preconditioner state that lacks an attribute its
+class's forward reads, an iDDPM denoiser whose out_channels is not 2 * img_channels, the 'skip' encoder / decoder and any other resampling
+filter raise NotImplementedError; an iDDPM table that is not M + 1 strictly decreasing levels ending in 0 raises ValueError.
 """
 import collections
 import io
@@ -149,9 +152,39 @@ _SONG_SUPPORTED = dict(embedding_type=('positional', 'fourier'), encoder_type=('
                        resample_filter=([1, 1], [1, 3, 3, 1]))
 
 
+# the four preconditioner classes (networks.py:469-671): config name, and the attributes of the pickled `__dict__` that the class's `forward`,
+# `round_sigma` and the sampler read (besides img_resolution / img_channels / label_dim, which every class records)
+_PRECONDS = {
+    'EDMPrecond': ('edm', ('sigma_data', 'sigma_min', 'sigma_max')),
+    'VPPrecond': ('vp', ('beta_d', 'beta_min', 'M', 'sigma_min', 'sigma_max')),
+    'VEPrecond': ('ve', ('sigma_min', 'sigma_max')),
+    'iDDPMPrecond': ('iddpm', ('M', 'sigma_min', 'sigma_max')),
+}
+_PRECOND_OPTIONAL = ('epsilon_t', 'C_1', 'C_2', 'sigma_data')      # recorded by some classes, read by no forward: kept when present
+
+
+def _precond_fields(net: Persisted) -> Dict[str, Any]:
+    """precond + its recorded scalars as EDMConfig keywords.  A state that lacks an attribute its class's forward reads is refused."""
+    if net.class_name not in _PRECONDS:
+        raise NotImplementedError(f'preconditioner {net.class_name}: one of {sorted(_PRECONDS)} expected')
+    kind, needed = _PRECONDS[net.class_name]
+    st = net.state
+    for k in ('img_resolution', 'img_channels', 'label_dim') + needed:
+        if k not in st:
+            raise NotImplementedError(f'{net.class_name} without the attribute {k!r} its forward reads: not a state this loader can express')
+    out = dict(precond=kind, use_fp16=bool(st.get('use_fp16', False)), sigma_min=float(st['sigma_min']), sigma_max=float(st['sigma_max']))
+    for k in needed + tuple(k for k in _PRECOND_OPTIONAL if k in st):
+        if k == 'M':
+            if int(st[k]) != st[k] or int(st[k]) < 2:
+                raise ValueError(f'{net.class_name}.M = {st[k]!r}')
+            out[k] = int(st[k])
+        elif k not in out:
+            out[k] = float(st[k])
+    return out
+
+
 def _config(net: Persisted) -> EDMConfig:
-    if net.class_name != 'EDMPrecond':
-        raise NotImplementedError(f'preconditioner {net.class_name}: only EDMPrecond is on the search path (SURVEY.md section 8 a3)')
+    pre = _precond_fields(net)
     st = net.state
     model = (st.get('_modules') or {}).get('model')
     if not isinstance(model, Persisted) or model.class_name not in ('DhariwalUNet', 'SongUNet'):
@@ -162,6 +195,11 @@ def _config(net: Persisted) -> EDMConfig:
     if recorded is None:
         raise ValueError('the pickled denoiser did not record its constructor arguments (persistence.py:106-108)')
     kw.update({k: v for k, v in dict(recorded).items() if k in kw})
+    if pre['precond'] == 'iddpm':
+        # the denoiser also predicts the variances (networks.py:592); D reads the first img_channels outputs only (:614)
+        if 'out_channels' not in dict(recorded) or int(dict(recorded)['out_channels']) != 2 * int(st['img_channels']):
+            raise NotImplementedError(f'iDDPMPrecond over a denoiser with out_channels={dict(recorded).get("out_channels")!r}: '
+                                      f'2 * img_channels = {2 * int(st["img_channels"])} expected')
     extra = {}
     if not adm:
         kw['resample_filter'] = [int(t) if float(t) == int(t) else float(t) for t in kw['resample_filter']]
@@ -170,11 +208,10 @@ def _config(net: Persisted) -> EDMConfig:
                 raise NotImplementedError(f'SongUNet option {k}={kw[k]!r}: supported are {list(ok)}')
         extra = dict(embedding_type=kw['embedding_type'], channel_mult_noise=int(kw['channel_mult_noise']), encoder_type=kw['encoder_type'],
                      resample_filter=kw['resample_filter'])
-    return EDMConfig(**extra, arch='adm' if adm else 'ddpmpp', img_resolution=int(st['img_resolution']), img_channels=int(st['img_channels']),
+    return EDMConfig(**extra, **pre, arch='adm' if adm else 'ddpmpp', img_resolution=int(st['img_resolution']), img_channels=int(st['img_channels']),
                      label_dim=int(st['label_dim']), model_channels=int(kw['model_channels']), channel_mult=list(kw['channel_mult']),
                      channel_mult_emb=int(kw['channel_mult_emb']), num_blocks=int(kw['num_blocks']),
-                     attn_resolutions=list(kw['attn_resolutions']), augment_dim=int(kw['augment_dim']),
-                     sigma_data=float(st['sigma_data']), sigma_min=float(st['sigma_min']), sigma_max=float(st['sigma_max']))
+                     attn_resolutions=list(kw['attn_resolutions']), augment_dim=int(kw['augment_dim']))
 
 
 def load_edm_pickle(source, key: str = 'ema') -> Tuple[EDMConfig, 'collections.OrderedDict[str, torch.Tensor]']:
@@ -214,3 +251,18 @@ def _check_buffers(cfg, sd):
         fr = sd.get('model.map_noise.freqs')
         if fr is None or fr.numel() != cfg.noise_channels // 2:
             raise ValueError(f'Fourier embedding: model.map_noise.freqs with {cfg.noise_channels // 2} values expected')
+    if cfg.precond == 'iddpm':
+        check_iddpm_table(sd.get('u'), cfg.M)
+
+
+def check_iddpm_table(u, M):
+    """The `u` buffer of an iDDPMPrecond is the file's own (a top-level key, not under `model.`): c_noise = M - 1 - argmin_j |sigma - u[j]|
+    (networks.py:610, 621-625) and sigma_min / sigma_max = u[M-1] / u[0] only mean what the reference means by them for M + 1 strictly
+    decreasing levels ending in u[M] = 0."""
+    if u is None:
+        raise NotImplementedError("iDDPMPrecond without the buffer 'u' its forward reads")
+    u = u.detach().to('cpu', torch.float32).reshape(-1)
+    if u.numel() != M + 1:
+        raise ValueError(f'iDDPMPrecond: u has {u.numel()} entries, M + 1 = {M + 1} expected')
+    if not bool(torch.isfinite(u).all()) or not bool((u[1:] < u[:-1]).all()) or float(u[M]) != 0.0:
+        raise ValueError('iDDPMPrecond: u must be finite, strictly decreasing and end in u[M] == 0')

@@ -30,6 +30,20 @@ class EDMConfig:
     channel_mult_noise: int = 1
     encoder_type: str = 'standard'          # 'standard' | 'residual'
     resample_filter: List[int] = field(default_factory=lambda: [1, 1])
+    # the preconditioner wrapped around the denoiser (networks.py:469-671) and the scalars its class records, with the reference's defaults
+    precond: str = 'edm'                    # 'edm' | 'vp' | 've' | 'iddpm'
+    beta_d: float = 19.9                    # VPPrecond: extent / initial slope of the noise schedule, minimum training t
+    beta_min: float = 0.1
+    epsilon_t: float = 1e-5
+    M: int = 1000                           # VPPrecond, iDDPMPrecond: timesteps of the original DDPM formulation
+    C_1: float = 0.001                      # iDDPMPrecond: timestep adjustments at low / high noise levels
+    C_2: float = 0.008
+    use_fp16: bool = False                  # what the checkpoint records (networks.py:474); the compute mode here is chosen at construction
+
+    @property
+    def out_channels(self):
+        """channels of the denoiser's last convolution: iDDPM also predicts the variances (networks.py:592), which D never reads (:614)"""
+        return self.img_channels * (2 if self.precond == 'iddpm' else 1)
 
     @property
     def emb_channels(self):
@@ -67,6 +81,27 @@ def ncsnpp_cifar10(label_dim=10) -> EDMConfig:
 def ncsnpp_ffhq64() -> EDMConfig:
     """--arch=ncsnpp --cres=1,2,2,2 at 64x64, unconditional: the network of `edm-ffhq-64x64-uncond-ve.pkl` / `edm-afhqv2-64x64-uncond-ve.pkl`."""
     return EDMConfig('ddpmpp', 64, 3, 0, 128, [1, 2, 2, 2], 4, 4, [16], 9, **_NCSNPP)
+
+
+def vp_cifar10(label_dim=10) -> EDMConfig:
+    """edm/train.py --precond=vp --arch=ddpmpp: VPPrecond over DDPM++, the network of the published `baseline-cifar10-32x32-*-vp.pkl` files.
+    sigma_min / sigma_max are what VPPrecond.__init__ computes from its defaults (networks.py:491-492: float(sigma(epsilon_t)), float(sigma(1)))."""
+    from .init import vp_sigma_range
+    lo, hi = vp_sigma_range(19.9, 0.1, 1e-5)
+    return EDMConfig('ddpmpp', 32, 3, label_dim, 128, [2, 2, 2], 4, 4, [16], 9, sigma_min=lo, sigma_max=hi, precond='vp')
+
+
+def ve_cifar10(label_dim=10) -> EDMConfig:
+    """edm/train.py --precond=ve --arch=ncsnpp: VEPrecond over NCSN++ (`baseline-cifar10-32x32-*-ve.pkl`); its range is 0.02 .. 100 (networks.py:534-535)"""
+    return EDMConfig('ddpmpp', 32, 3, label_dim, 128, [2, 2, 2], 4, 4, [16], 9, sigma_min=0.02, sigma_max=100, precond='ve', **_NCSNPP)
+
+
+def iddpm_imagenet64(label_dim=1000) -> EDMConfig:
+    """iDDPMPrecond over ADM: the network of `baseline-imagenet-64x64-cond-adm.pkl`.  sigma_min = u[M-1], sigma_max = u[0] of the table the
+    constructor builds (networks.py:594-599)."""
+    from .init import iddpm_u
+    u = iddpm_u(1000, 0.001, 0.008)
+    return EDMConfig('adm', 64, 3, label_dim, 192, [1, 2, 3, 4], 4, 3, [32, 16, 8], 0, sigma_min=float(u[999]), sigma_max=float(u[0]), precond='iddpm')
 
 
 @dataclass

@@ -118,6 +118,66 @@ __global__ void precond_in_kernel(const double* __restrict__ x, const double* __
     }
   }
 }
+// ---- K8b: the VP / VE / iDDPM preconditioners (networks.py:495-509, 548-562, 601-625) -------------------------------------------------
+// The coefficients once per row (one wavefront per row), then the scaling pass.  Every tensor operation of the reference's expression is
+// one float32 rounding here, in its order: `fp contract(off)` keeps the compiler from fusing a product into the addition that follows it
+// (hipcc's __fmul_rn / __fadd_rn are plain operators and would be contracted; its __fsqrt_rn is the approximate square root).
+// The float32 logarithm as an IEEE operation would give it: taken in double and rounded once.  VP multiplies it by (M - 1) ~ 1000 on its way
+// into c_noise, and the positional embedding's highest frequency turns every ulp of c_noise into phase: ONE ulp of this logarithm moves the
+// end of an 18-step search on the tiny VP test network (|x| ~ 470) by 1.4e-3, three times the reference's own float32-vs-float64 distance
+// (measured on the reference itself, whose host logarithm is correctly rounded on those inputs).  Once per row: no cost.
+__device__ __forceinline__ float log32(float v) { return (float)log((double)v); }
+struct precond_params { float m1, bmin2, bd2, bmin, bd; };       // M - 1, beta_min^2, 2 beta_d, beta_min, beta_d: rounded once on the host
+__global__ void __launch_bounds__(256) precond_coef_kernel(int kind, precond_params p, const float* __restrict__ table, int table_n,
+                                                            const double* __restrict__ sigma, int nsigma, float* __restrict__ coef, int n) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= n) return;                                           // whole waves leave together: the shuffles below see all 64 lanes
+  const float sg = (float)sigma[nsigma == 1 ? 0 : row];
+  float c_noise;
+  if (kind == DTS_PRECOND_IDDPM) {
+    // argmin_j |sg - table[j]|, first index on a tie.  The distance is taken in double: the difference of two floats is exact there unless
+    // their exponents lie more than 29 binades apart; then it is rounded, monotonically, and can only tie entries that lie on one side of
+    // sg and far below it, where the first index (the largest entry of a decreasing table) is the nearest one as well.
+    double best = INFINITY;
+    int bj = 0x7fffffff;
+    for (int j = lane; j < table_n; j += 64) {
+      const double d = fabs((double)sg - (double)table[j]);
+      if (d < best || bj == 0x7fffffff) { best = d; bj = j; }     // ascending j per lane: strict < keeps the lane's lowest index
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double od = __shfl_xor(best, o, 64);
+      const int oj = __shfl_xor(bj, o, 64);
+      if (od < best || (od == best && oj < bj) || (oj != 0x7fffffff && bj == 0x7fffffff)) { best = od; bj = oj; }
+    }
+    c_noise = p.m1 - (float)bj;
+  } else if (kind == DTS_PRECOND_VP) {
+    const float s2 = sg * sg;
+    const float a = 1.0f + s2;                                    // 1 + sigma ** 2
+    const float t = p.bd2 * log32(a);                             // 2 * beta_d * (.).log()
+    const float r = sqrtf(p.bmin2 + t);                           // (beta_min ** 2 + .).sqrt()
+    c_noise = p.m1 * ((r - p.bmin) / p.bd);                       // (M - 1) * (((.) - beta_min) / beta_d)
+  } else {
+    c_noise = log32(0.5f * sg);                                   // (0.5 * sigma).log()
+  }
+  if (lane == 0) {
+    const float s2 = sg * sg;
+    const bool ve = kind == DTS_PRECOND_VE;
+    coef[row * 4 + 0] = 1.0f;
+    coef[row * 4 + 1] = ve ? sg : -sg;
+    coef[row * 4 + 2] = ve ? 1.0f : 1.0f / sqrtf(s2 + 1.0f);   // 1 / (sigma ** 2 + 1).sqrt()
+    coef[row * 4 + 3] = c_noise;
+  }
+}
+__global__ void precond_scale_kernel(const double* __restrict__ x, const float* __restrict__ coef, float* __restrict__ xin, int n, int chw) {
+  const long long total = (long long)n * chw;
+  GSL(i, total) {
+    const int ni = (int)(i / chw);
+    xin[i] = coef[ni * 4 + 2] * (float)x[i];
+  }
+}
 __global__ void precond_out_kernel(const double* __restrict__ x, const float* __restrict__ F, const float* __restrict__ coef,
                                    float* __restrict__ D, int n, int chw) {
   const long long total = (long long)n * chw;
@@ -656,6 +716,22 @@ extern "C" int dts_edm_precond_in(const double* x, const double* sigma, int nsig
   hipLaunchKernelGGL(precond_in_kernel, dim3(grid1d((long long)n * chw)), dim3(256), 0, st, x, sigma, nsigma, sigma_data, xin, coef, n,
                      chw);
   DTS_CHECK_LAUNCH("dts_edm_precond_in");
+  return DTS_OK;
+}
+extern "C" int dts_precond_in(int kind, const float* params, const float* table, int table_n, const double* x, const double* sigma,
+                              int nsigma, float* xin, float* coef, int n, int chw, dts_stream s) {
+  DTS_CHECK_ARG(kind == DTS_PRECOND_VP || kind == DTS_PRECOND_VE || kind == DTS_PRECOND_IDDPM, "dts_precond_in: kind %d", kind);
+  DTS_CHECK_ARG(x && sigma && xin && coef && n > 0 && chw > 0, "dts_precond_in: bad args");
+  DTS_CHECK_ARG(nsigma == 1 || nsigma == n, "dts_precond_in: nsigma=%d n=%d", nsigma, n);
+  DTS_CHECK_ARG(kind == DTS_PRECOND_VE || params, "dts_precond_in: kind %d needs params", kind);
+  DTS_CHECK_ARG(kind != DTS_PRECOND_IDDPM || (table && table_n >= 1), "dts_precond_in: the iDDPM kind needs its table (table_n=%d)", table_n);
+  precond_params p = {0.f, 0.f, 0.f, 0.f, 1.f};
+  if (params) p = {params[0], params[1], params[2], params[3], params[4]};
+  ST;
+  hipLaunchKernelGGL(precond_coef_kernel, dim3((n + 3) / 4), dim3(256), 0, st, kind, p, table, table_n, sigma, nsigma, coef, n);
+  DTS_CHECK_LAUNCH("dts_precond_in (coefficients)");
+  hipLaunchKernelGGL(precond_scale_kernel, dim3(grid1d((long long)n * chw)), dim3(256), 0, st, x, coef, xin, n, chw);
+  DTS_CHECK_LAUNCH("dts_precond_in");
   return DTS_OK;
 }
 extern "C" int dts_edm_precond_out(const double* x, const float* F, const float* coef, float* D, int n, int chw, dts_stream s) {

@@ -57,10 +57,36 @@ def resample_filter_2d(taps):
     return f.ger(f).unsqueeze(0).unsqueeze(1) / f.sum().square()
 
 
+def vp_sigma_range(beta_d=19.9, beta_min=0.1, epsilon_t=1e-5):
+    """(sigma_min, sigma_max) of a VPPrecond (networks.py:491-492, 511-513): float(sigma(epsilon_t)), float(sigma(1)) with sigma(t) evaluated
+    on a default-dtype (float32) scalar tensor, as `torch.as_tensor(<python number>)` makes it"""
+    def sigma(t):
+        t = torch.as_tensor(t, dtype=torch.float32)
+        return ((0.5 * beta_d * (t ** 2) + beta_min * t).exp() - 1).sqrt()
+    return float(sigma(epsilon_t)), float(sigma(1.0))
+
+
+def iddpm_u(M=1000, C_1=0.001, C_2=0.008):
+    """The `u` buffer of an iDDPMPrecond (networks.py:594-597, 617-619): the noise levels of the M + 1 DDPM timesteps, u[M] = 0, built
+    backwards in float32 -- alpha_bar(j) = sin(pi/2 * j / M / (C_2 + 1))^2 on an integer tensor times a Python float, i.e. in float32 --
+    with the reference's own sequence of tensor operations, so the table is the constructor's bit for bit on the same host (a float32 sine is
+    not rounded alike by every CPU's vector library: a checkpoint's table is the file's own, never this one)."""
+    def alpha_bar(j):
+        j = torch.as_tensor(j)
+        return (0.5 * np.pi * j / M / (C_2 + 1)).sin() ** 2
+    u = torch.zeros(M + 1)
+    for j in range(M, 0, -1):
+        u[j - 1] = ((u[j] ** 2 + 1) / (alpha_bar(j - 1) / alpha_bar(j)).clip(min=C_1) - 1).sqrt()
+    return u
+
+
 def edm_state_dict(cfg: EDMConfig, seed: int = 0, prefix: str = 'model.'):
     """Parameters of the reference constructor, draw for draw.  With the NCSN++ options the buffers travel too, in state_dict() order: the
     Fourier embedding's `map_noise.freqs` is a random draw the network needs (networks.py:215), and the [1, 3, 3, 1] `resample_filter`s are
-    what checkpoint.load_edm_pickle checks a file's filter by.  (The DDPM++ dict keeps its historical form: parameters only.)"""
+    what checkpoint.load_edm_pickle checks a file's filter by.  (The DDPM++ dict keeps its historical form: parameters only.)
+    The VP and VE wrappers add nothing to the denoiser's draws; iDDPM (cfg.precond == 'iddpm') draws the last convolution with
+    2 * img_channels outputs (networks.py:592) and carries the wrapper's own `u` buffer, first in the dict and without `prefix`, as in
+    state_dict() order (a module's buffers precede its children)."""
     torch.manual_seed(seed)
     adm = cfg.arch == 'adm'
     mc, emb = cfg.model_channels, cfg.emb_channels
@@ -114,11 +140,15 @@ def edm_state_dict(cfg: EDMConfig, seed: int = 0, prefix: str = 'model.'):
     r = cfg.img_resolution
     if adm:
         B.norm('out_norm', cfin)
-        B.conv('out_conv', cfin, cfg.img_channels, 3, **zero)
+        B.conv('out_conv', cfin, cfg.out_channels, 3, **zero)
     else:
         B.norm(f'dec.{r}x{r}_aux_norm', cfin)
-        B.conv(f'dec.{r}x{r}_aux_conv', cfin, cfg.img_channels, 3, **zero)
-    return OrderedDict((prefix + k, v.to(torch.float32)) for k, v in B.sd.items())
+        B.conv(f'dec.{r}x{r}_aux_conv', cfin, cfg.out_channels, 3, **zero)
+    out = OrderedDict()
+    if cfg.precond == 'iddpm':
+        out['u'] = iddpm_u(cfg.M, cfg.C_1, cfg.C_2)
+    out.update((prefix + k, v.to(torch.float32)) for k, v in B.sd.items())
+    return out
 
 
 def classifier_state_dict(cfg: ClassifierConfig, seed: int = 1):

@@ -17,6 +17,10 @@ own between the norm and conv0 and in front of the 1x1 skip conv (dts_resample_f
 gather inside the conv; and after every down block the residual encoder's `x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2)` is
 space-to-depth + ONE conv launch (ops.fused_down_weight).  The ADM and DDPM++ sequences are untouched by those branches.
 
+The other three preconditioners (VPPrecond, VEPrecond, iDDPMPrecond: networks.py:469-625) are the same class with cfg.precond = 'vp' | 've' |
+'iddpm': only the first launch differs (ops.precond_in instead of ops.edm_precond_in; same coefficient layout, so ops.edm_precond_out closes
+every kind), iDDPM's last convolution keeps its first img_channels rows, and its round_sigma is the reference's table lookup on the host.
+
 Per UNetBlock (networks.py:166-187) the launch sequence is
   gn_coef+gn_apply(SiLU, [2x2 pool]) -> conv0 [fused nearest-up gather] -> gn_coef(+scale/shift)+gn_apply(SiLU)
   -> [1x1 skip conv | resample] -> conv1 (+residual, *skip_scale)
@@ -47,7 +51,7 @@ class _BlockParams:
 
 
 class EDMPrecond:
-    """EDMPrecond + DhariwalUNet / SongUNet(DDPM++ or NCSN++) forward on MI355X."""
+    """EDMPrecond -- or, by cfg.precond, VPPrecond / VEPrecond / iDDPMPrecond -- + DhariwalUNet / SongUNet(DDPM++ or NCSN++) forward on MI355X."""
 
     def __init__(self, cfg: EDMConfig, state_dict: Dict[str, torch.Tensor], device='cuda', dtype=ops.F16X3):
         if not torch.cuda.is_available():
@@ -60,6 +64,9 @@ class EDMPrecond:
         self.img_resolution, self.img_channels, self.label_dim = cfg.img_resolution, cfg.img_channels, cfg.label_dim
         self.sigma_min, self.sigma_max, self.sigma_data = cfg.sigma_min, cfg.sigma_max, cfg.sigma_data
         self.use_fp16 = dtype == torch.float16
+        if cfg.precond not in ('edm', 'vp', 've', 'iddpm'):
+            raise NotImplementedError(f'preconditioner {cfg.precond!r}')
+        self.precond = cfg.precond
         self.adm = cfg.arch == 'adm'
         self.eps = 1e-5 if self.adm else 1e-6
         self.skip_scale = 1.0 if self.adm else math.sqrt(0.5)
@@ -77,6 +84,7 @@ class EDMPrecond:
         self._graphs = GraphCache(self._device_forward)     # HIP-graph replay of the fixed-shape forward (graphs.py)
         sd = {k[len('model.'):]: v for k, v in state_dict.items() if k.startswith('model.')}
         self._load(sd)
+        self._load_precond(state_dict)
 
     # ------------------------------------------------------------------------------------------
     def _dev(self, t):
@@ -153,10 +161,30 @@ class EDMPrecond:
         r = cfg.img_resolution
         on, oc = ('out_norm', 'out_conv') if self.adm else (f'dec.{r}x{r}_aux_norm', f'dec.{r}x{r}_aux_conv')
         self.out_g, self.out_b = f(sd[f'{on}.weight']), f(sd[f'{on}.bias'])
-        self.out_w = f(sd[f'{oc}.weight']).permute(0, 2, 3, 1).contiguous()          # [3][kh][kw][c]
-        self.out_cb = f(sd[f'{oc}.bias'])
+        # iDDPM: the denoiser has 2 * img_channels outputs, of which D reads the first img_channels (networks.py:614): the variance rows of the
+        # last convolution are dropped here, once
+        ow, ob = sd[f'{oc}.weight'], sd[f'{oc}.bias']
+        if ow.shape[0] != cfg.out_channels or ob.shape[0] != cfg.out_channels:
+            raise ValueError(f'{oc}: {ow.shape[0]} output channels, {cfg.out_channels} expected for precond={cfg.precond!r}')
+        self.out_w = f(ow[:cfg.img_channels]).permute(0, 2, 3, 1).contiguous()       # [3][kh][kw][c]
+        self.out_cb = f(ob[:cfg.img_channels])
         self.cfin = cfin
         torch.cuda.synchronize(dev)
+
+    def _load_precond(self, state_dict):
+        """what the VP / VE / iDDPM forwards need besides the denoiser: the host array of scalars dts_precond_in reads and, for iDDPM, the `u`
+        table -- the state dict's own top-level entry -- on the device (the forward's index search) and on the host (round_sigma)"""
+        cfg = self.cfg
+        self.u = self.u_dev = None
+        if self.precond == 'edm':
+            return
+        self.pre_params = ops.precond_params(self.precond, M=cfg.M, beta_d=cfg.beta_d, beta_min=cfg.beta_min)
+        if self.precond == 'iddpm':
+            from .checkpoint import check_iddpm_table
+            check_iddpm_table(state_dict.get('u'), cfg.M)
+            self.u = state_dict['u'].detach().to('cpu', torch.float32).reshape(-1).contiguous()
+            self.u_dev = self.u.to(self.device).contiguous()
+            torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------------------------------
     def to(self, device):
@@ -165,8 +193,17 @@ class EDMPrecond:
     def eval(self):
         return self
 
-    def round_sigma(self, sigma):
-        return torch.as_tensor(sigma)
+    def round_sigma(self, sigma, return_index=False):
+        """Host side, the reference's own expression: the identity for EDM / VP / VE (networks.py:519, 564, 670); for iDDPM the nearest entry
+        of `u` by torch.cdist on the CPU (networks.py:621-625), so a schedule and every t_hat are the reference's CPU run's bit for bit."""
+        sigma = torch.as_tensor(sigma)
+        if self.precond != 'iddpm':
+            if return_index:
+                raise TypeError('round_sigma(return_index=True): iDDPMPrecond only')
+            return sigma
+        index = torch.cdist(sigma.to('cpu', torch.float32).reshape(1, -1, 1), self.u.reshape(1, -1, 1)).argmin(2)
+        result = index if return_index else self.u[index.flatten()].to(sigma.dtype)
+        return result.reshape(sigma.shape).to(sigma.device)
 
     @staticmethod
     def _groups(c):
@@ -295,7 +332,10 @@ class EDMPrecond:
     @torch.no_grad()
     def _device_forward(self, x, sigma, class_labels):
         """The fixed-shape device part of the forward (all inputs already on the GPU): what graphs.GraphCache captures."""
-        xin, coef = ops.edm_precond_in(x, sigma, self.sigma_data)
+        if self.precond == 'edm':
+            xin, coef = ops.edm_precond_in(x, sigma, self.sigma_data)
+        else:
+            xin, coef = ops.precond_in(self.precond, x, sigma, self.pre_params, self.u_dev)
         F = self.unet(xin, coef[:, 3].contiguous(), class_labels)
         return ops.edm_precond_out(x, F, coef)
 

@@ -938,6 +938,37 @@ def edm_precond_in(x, sigma, sigma_data):
     return xin, coef
 
 
+PRECOND_KINDS = {'vp': 1, 've': 2, 'iddpm': 3}          # dts.h dts_precond_kind
+
+
+def precond_params(kind, M=1000, beta_d=19.9, beta_min=0.1):
+    """The host array dts_precond_in reads: the Python-scalar sub-expressions of the reference's forward (networks.py:504, 517, 610), each
+    evaluated in double and rounded to float32 once -- what torch does with a Python scalar that meets a float32 tensor."""
+    import ctypes
+    if kind == 'vp':
+        v = (M - 1, beta_min ** 2, 2 * beta_d, beta_min, beta_d)
+    elif kind == 'iddpm':
+        v = (M - 1, 0.0, 0.0, 0.0, 1.0)
+    else:
+        return None
+    return (ctypes.c_float * 5)(*[float(t) for t in v])
+
+
+def precond_in(kind, x, sigma, params=None, table=None):
+    """The VP / VE / iDDPM twin of edm_precond_in: x f64 NCHW, sigma f64 [1] or [n] -> (c_in*x f32 NCHW, coef f32 [n,4]).  params:
+    precond_params(...); table: the iDDPM `u` buffer, f32 on the device."""
+    if kind not in PRECOND_KINDS:
+        raise ValueError(f'precond_in: kind {kind!r}, one of {sorted(PRECOND_KINDS)}')
+    if (kind != 've' and params is None) or (kind == 'iddpm' and table is None):
+        raise ValueError(f'precond_in: kind {kind!r} needs its params' + (' and table' if kind == 'iddpm' else ''))
+    n = x.shape[0]
+    xin = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    coef = torch.empty((n, 4), dtype=torch.float32, device=x.device)
+    _call('dts_precond_in', PRECOND_KINDS[kind], params, _ptr(table, 'table', torch.float32), 0 if table is None else table.numel(),
+          _ptr(x, 'x', torch.float64), _ptr(sigma, 'sigma', torch.float64), sigma.numel(), _ptr(xin), _ptr(coef), n, x[0].numel())
+    return xin, coef
+
+
 def edm_precond_out(x, F, coef):
     n = x.shape[0]
     D = torch.empty(x.shape, dtype=torch.float32, device=x.device)

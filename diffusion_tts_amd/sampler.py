@@ -51,31 +51,38 @@ def load_network(spec, device='cuda', dtype=ops.F16X3):
     (edm/main.py:69-70); URLs cannot be fetched here, so accepted forms are: a ready network object; the local path of
     an EDM network pickle (`*.pkl`, read by checkpoint.load_edm_pickle without executing its embedded source); a
     torch-saved dict {'cfg': EDMConfig kwargs, 'state_dict': {...reference keys...}}; or 'random:<preset>[:seed]'
-    with preset in {adm_imagenet64, ddpmpp_cifar10, ncsnpp_cifar10, ncsnpp_ffhq64} (random init + the documented weight rule)."""
+    with preset in {adm_imagenet64, ddpmpp_cifar10, ncsnpp_cifar10, ncsnpp_ffhq64, vp_cifar10, ve_cifar10, iddpm_imagenet64} (random init +
+    the documented weight rule; the last three are the VP, VE and iDDPM preconditioners over DDPM++, NCSN++ and ADM).  A pickle or bundle
+    carries its preconditioner (`EDMConfig.precond`) with it.  dtype='auto': float16 when the file records use_fp16=True, else ops.F16X3."""
     from . import init as dinit
-    from .config import EDMConfig, adm_imagenet64, ddpmpp_cifar10, ncsnpp_cifar10, ncsnpp_ffhq64
+    from .config import (EDMConfig, adm_imagenet64, ddpmpp_cifar10, ncsnpp_cifar10, ncsnpp_ffhq64, vp_cifar10, ve_cifar10,
+                         iddpm_imagenet64)
     from .networks import EDMPrecond
     if callable(spec) and hasattr(spec, 'round_sigma'):
         return spec
+
+    def mode(cfg):
+        return dtype if dtype != 'auto' else (torch.float16 if cfg.use_fp16 else ops.F16X3)
     if isinstance(spec, str) and spec.startswith('random:'):
         parts = spec.split(':')
         presets = {'adm_imagenet64': adm_imagenet64, 'ddpmpp_cifar10': ddpmpp_cifar10, 'ncsnpp_cifar10': ncsnpp_cifar10,
-                   'ncsnpp_ffhq64': ncsnpp_ffhq64}
+                   'ncsnpp_ffhq64': ncsnpp_ffhq64, 'vp_cifar10': vp_cifar10, 've_cifar10': ve_cifar10, 'iddpm_imagenet64': iddpm_imagenet64}
         if parts[1] not in presets:
             raise ValueError(f'unknown preset {parts[1]!r}: one of {sorted(presets)}')
         preset = presets[parts[1]]()
         seed = int(parts[2]) if len(parts) > 2 else 0
         sd, _ = dinit.refill_degenerate(dinit.edm_state_dict(preset, seed), seed)
-        return EDMPrecond(preset, sd, device=device, dtype=dtype)
+        return EDMPrecond(preset, sd, device=device, dtype=mode(preset))
     if isinstance(spec, str) and spec.endswith(('.pt', '.pth')):
         blob = torch.load(spec, map_location='cpu')
-        return EDMPrecond(EDMConfig(**blob['cfg']), blob['state_dict'], device=device, dtype=dtype)
+        cfg = EDMConfig(**blob['cfg'])
+        return EDMPrecond(cfg, blob['state_dict'], device=device, dtype=mode(cfg))
     if isinstance(spec, str) and spec.endswith('.pkl'):
         # an NVIDIA EDM network pickle, e.g. a downloaded edm-imagenet-64x64-cond-adm.pkl (the reference's `network_pkl`,
         # main.py:157-158): weights and constructor arguments are read without executing the source embedded in the file
         from .checkpoint import load_edm_pickle
         cfg, sd = load_edm_pickle(spec)
-        return EDMPrecond(cfg, sd, device=device, dtype=dtype)
+        return EDMPrecond(cfg, sd, device=device, dtype=mode(cfg))
     raise ValueError(f'cannot load network from {spec!r}: pass a network object, an EDM network .pkl (local path), a .pt '
                      f'state-dict bundle or "random:<preset>[:seed]" (URLs cannot be fetched here)')
 

@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 120        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 121        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -56,7 +56,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      117: dts_attention_masked, dts_text_tokens (the CLIP text tower: SD's text encoder and the CLIP scorer's text side);
                                      118: dts_layer_norm_x3, dts_gelu_x3, dts_patchify_x3, dts_vit_tokens_f32, dts_vit_head_f32 (the CLIP vision tower in DTS_F16X3);
                                      119: dts_conv_plan (the whole launch plan of a dts_conv2d call, as a query);
-                                     120: dts_conv_args.up == 2 (phase-packed weights), dts_conv_takes_phases, dts_conv_plan_info.phases) */
+                                     120: dts_conv_args.up == 2 (phase-packed weights), dts_conv_takes_phases, dts_conv_plan_info.phases;
+                                     121: dts_precond_in (the VP, VE and iDDPM preconditioners)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -316,6 +317,21 @@ int dts_pos_embedding(const float* v, const float* freqs, float* out, int n, int
 /* coef[n][4] = (c_skip, c_out, c_in, c_noise) in f32 from sigma (f64, nsigma = 1 or n); xin = c_in * f32(x) */
 int dts_edm_precond_in(const double* x, const double* sigma, int nsigma, float sigma_data,
                        float* xin, float* coef, int n, int chw, dts_stream s);
+/* The other three preconditioners (networks.py:495-509 VP, 548-562 VE, 601-625 iDDPM): the same coef[n][4] = (c_skip, c_out, c_in, c_noise)
+ * and xin = c_in * f32(x), so dts_edm_precond_out serves every kind.  c_skip = 1 throughout;
+ *   VP:    c_out = -s, c_in = 1 / sqrt(s^2 + 1), c_noise = (M-1) * ((sqrt(beta_min^2 + 2 beta_d * log(1 + s^2)) - beta_min) / beta_d)
+ *   VE:    c_out =  s, c_in = 1,                 c_noise = log(0.5 * s)
+ *   iDDPM: c_out, c_in as VP,                    c_noise = (M-1) - j, j = the index of the entry of table[0:table_n] (f32, device) nearest to s:
+ *          the exact |s - table[j]|, the first index on a tie (the reference's torch.cdist takes a matrix-product route for a long table and
+ *          can miss the nearest entry of a near-tie: INTEGRATION.md section 1)
+ * with s = f32(sigma[row]).  float32 arithmetic, one rounding per tensor operation of the reference's expression and in its order, no fused
+ * multiply-add.  params: HOST array of DTS_PRECOND_NPARAMS floats, read during the call, each a Python-scalar sub-expression of the reference
+ * evaluated in double and rounded once: {M-1, beta_min^2, 2*beta_d, beta_min, beta_d} (VP: all five; iDDPM: [0]; VE: unread, may be NULL).
+ * Two launches on `s` (coefficients: one wavefront per row; then the scaling pass), no host read: capturable into a HIP graph. */
+enum dts_precond_kind { DTS_PRECOND_VP = 1, DTS_PRECOND_VE = 2, DTS_PRECOND_IDDPM = 3 };
+#define DTS_PRECOND_NPARAMS 5
+int dts_precond_in(int kind, const float* params, const float* table, int table_n, const double* x, const double* sigma, int nsigma,
+                   float* xin, float* coef, int n, int chw, dts_stream s);
 /* D = c_skip*f32(x) + c_out*F  (f32, NCHW) */
 int dts_edm_precond_out(const double* x, const float* F, const float* coef, float* D, int n, int chw, dts_stream s);
 /* split-precision operand image for dts_conv2d(dtype = DTS_F16X3): row p of concat(x1, x2) (f32 rows of c1 / c2 channels, x2 may be NULL

@@ -10,12 +10,15 @@ Arguments (verbatim from the reference):
     --prompt, --output, --N, --lambda_, --eps, --K, --B, --S, --seed, --device
 Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is no network here):
     --network   : 'random:adm_imagenet64[:seed]' (default), 'random:ddpmpp_cifar10[:seed]', 'random:ncsnpp_cifar10[:seed]',
-                  'random:ncsnpp_ffhq64[:seed]', the local path of an NVIDIA EDM network pickle (*.pkl, read without executing its
-                  embedded source: EDMPrecond over the ADM, DDPM++ or NCSN++ U-Net, i.e. the published edm-*-adm.pkl, edm-*-vp.pkl
-                  and edm-*-ve.pkl files), or a .pt bundle
+                  'random:ncsnpp_ffhq64[:seed]', 'random:vp_cifar10[:seed]', 'random:ve_cifar10[:seed]', 'random:iddpm_imagenet64[:seed]'
+                  (the VP, VE and iDDPM preconditioners), the local path of an NVIDIA EDM network pickle (*.pkl, read without executing
+                  its embedded source: EDMPrecond, VPPrecond, VEPrecond or iDDPMPrecond over the ADM, DDPM++ or NCSN++ U-Net, i.e. the
+                  published edm-*.pkl and baseline-*.pkl files), or a .pt bundle.  sigma_min / sigma_max of the schedule (0.002, 80) are
+                  clamped to the network's range, as the reference's edm/generate.py:31-32 does (the identity for EDMPrecond)
     --dtype     : f16x3 (default: split precision on the 16-bit matrix cores -- the reference's fp32 rewards and therefore its selected
                   candidates on the same seed, ~2.6x the f32 mode's speed) | f32 (parity mode, f32 matrix instruction) | bf16 | f16
                   (throughput modes: ~2.8x faster again, but a near-tied pick differs after ~10 decisions and the result is another sample)
+                  | auto (f16 when the network pickle records use_fp16=True, f16x3 otherwise; the choice is printed)
     --unet      : SD backend: diffusers (default: the stock UNet2DConditionModel) | hip (sd_unet.SDUNet on this build's kernels, read from
                   $DTS_SD_UNET_DIR or the cached snapshot's unet/; no fallback).  --vae hip|diffusers likewise (default hip)
     --text-encoder: SD backend: transformers (default: the stock CLIPTextModel) | hip (clip_text.CLIPTextTower on this build's kernels, read
@@ -198,7 +201,7 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=0, help='Random seed')
     parser.add_argument('--device', type=str, default='cuda', help='Device')
     parser.add_argument('--network', type=str, default='random:adm_imagenet64', help='EDM network spec (see module docstring)')
-    parser.add_argument('--dtype', type=str, default='f16x3', choices=['bf16', 'f16', 'f32', 'f16x3'], help='compute mode (see the module docstring)')
+    parser.add_argument('--dtype', type=str, default='f16x3', choices=['bf16', 'f16', 'f32', 'f16x3', 'auto'], help='compute mode (see the module docstring)')
     parser.add_argument('--vae', type=str, default='hip', choices=['hip', 'diffusers'],
                         help="SD backend: 'hip' = this build's VAE decoder (an error if its safetensors cannot be read), 'diffusers' = the stock module")
     parser.add_argument('--unet', type=str, default='diffusers', choices=['hip', 'diffusers'],
@@ -247,9 +250,16 @@ def main(argv=None):
 
     from diffusion_tts_amd.sampler import SamplingMethod, generate_image_grid, load_network
     from diffusion_tts_amd.ops import F16X3
-    dtype = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32, 'f16x3': F16X3}[args.dtype]
-    scorer = get_scorer('edm', args.scorer, device, compute_dtype=dtype, jpeg_codec=getattr(args, 'jpeg_codec', 'pil'))
+    dtype = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32, 'f16x3': F16X3, 'auto': 'auto'}[args.dtype]
     net = load_network(args.network, device=device, dtype=dtype)
+    if args.dtype == 'auto':
+        dtype = net.dtype
+        args.dtype = 'f16' if dtype == torch.float16 else 'f16x3'
+        print(f'[EDM] --dtype auto: {args.dtype} (the network records use_fp16={net.cfg.use_fp16})')
+    scorer = get_scorer('edm', args.scorer, device, compute_dtype=dtype, jpeg_codec=getattr(args, 'jpeg_codec', 'pil'))
+    # edm/generate.py:31-32: the schedule's end points inside the network's range (EDMPrecond: 0 .. inf, the identity).  Without it an iDDPM
+    # network rounds 0.002 to u[M] = 0 and the last Heun step divides by t_hat = 0, as the reference's would
+    sigma_min, sigma_max = max(0.002, net.sigma_min), min(80, net.sigma_max)
     if args.seeds is not None:                                                        # bulk mode: seeds sharded over the ranks
         from diffusion_tts_amd.bulk import generate_seeds
         mm = {'naive': SamplingMethod.NAIVE, 'rejection': SamplingMethod.REJECTION_SAMPLING, 'beam': SamplingMethod.BEAM_SEARCH,
@@ -259,7 +269,7 @@ def main(argv=None):
             sp.update(N=args.N, K=args.K, lambda_param=args.lambda_, eps=args.eps, B=args.B, S=args.S)
         done = generate_seeds(net, args.seeds, args.outdir, sampling_method=mm[args.method], sampling_params=sp,
                               class_idx=args.class_idx, subdirs=args.subdirs, device=device, compute_dtype=dtype,
-                              num_steps=18, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003)
+                              num_steps=18, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003, sigma_min=sigma_min, sigma_max=sigma_max)
         print(f'[EDM] rank {os.environ.get("RANK", "0")}: {len(done)} images -> {args.outdir}')
         if world > 1:
             dist.barrier()
@@ -285,7 +295,7 @@ def main(argv=None):
         sampling_params.update(N=args.N, K=args.K, lambda_param=args.lambda_, eps=args.eps, B=args.B, S=args.S)
     outname = args.output or f'edm_{args.method}_{args.scorer}.png'
     res = generate_image_grid(net, outname, latents, class_labels, seed=args.seed, gridw=1, gridh=1, device=device,
-                              num_steps=18, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003,
+                              num_steps=18, sigma_min=sigma_min, sigma_max=sigma_max, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003,
                               sampling_method=method_map[args.method], sampling_params=sampling_params, compute_dtype=dtype)
     if int(os.environ.get('RANK', '0')) == 0:
         print(f'\n[EDM] Saved: {outname}  (denoiser rows: {res["net_rows"]}, reward collectives: {res["collectives"]})')
