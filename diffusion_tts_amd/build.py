@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libdts_hip.so')
-SOURCES = ['conv_igemm.hip', 'conv_igemm_phase.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip', 'resample.hip', 'transformer.hip', 'group_rows.hip', 'vit.hip', 'vit_x3.hip', 'jpeg.hip']
+SOURCES = ['conv_igemm.hip', 'conv_igemm_phase.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip', 'resample.hip', 'transformer.hip', 'group_rows.hip', 'vit.hip', 'jpeg.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 # per-source extras.  attention: keep the MFMA accumulators in VGPRs -- the online-softmax rescale reads and rewrites them
@@ -23,7 +23,7 @@ def _newer(a, b):
 
 
 def build(force=False, verbose=False):
-    hdrs = [os.path.join(CSRC, 'dts_common.h'), os.path.join(HERE, '..', 'include', 'dts.h')]
+    hdrs = [os.path.join(CSRC, 'dts_common.h'), os.path.join(CSRC, 'row_forms.h'), os.path.join(HERE, '..', 'include', 'dts.h')]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -14,7 +14,7 @@ Every decoded candidate of a search passes through these 24 layers at 257 tokens
 Activations are [n, tokens, 1, channels] in `dtype`.  float16 / bfloat16: a 16-bit THROUGHPUT mode of the scorer (the reference scores in
 float32).  CLIPVisionTowerX3 (dtype ops.F16X3, 'f16x3'): the PARITY-GRADE mode -- float32 activations, every matrix product in split precision on the 16-bit matrix
 cores (dts_conv2d in DTS_F16X3; dts_attention_x3 at head dim 64 and >= 128 tokens, the float32 dts_attention otherwise), and between them
-the float32 twins of the kernels above, which write the next product's operand image themselves:
+the float32 forms of the kernels above, which write the next product's operand image themselves:
   patch rows -> dts_patchify_x3; tokens -> dts_vit_tokens_f32; pre_layrnorm, layer_norm1 / 2 -> dts_layer_norm_x3; activation -> dts_gelu_x3;
   head -> dts_vit_head_f32 + dts_linear
 It is held to the float32 module's own distance from float64 (tests/test_gpu_clip_vision_x3.py).  torch.float32 itself is refused: there is

@@ -915,8 +915,8 @@ extern "C" int dts_attention_masked(const void* qkv, void* out, int dtype, int n
   }
   AttP p{(const char*)qkv, (char*)out, n, t, heads, d, scale * 1.4426950408889634f, 0, 1, 0, key_len, causal ? 1 : 0};
   const size_t lds = (size_t)2 * 64 * (64 * 2 + 32);
-  return dtype == DTS_BF16 ? launch_att(attention16_kernel<bf16_t, 64, 1, 64, true, false, false, true>, p, lds, to_stream(s), 64, 1, "dts_attention_masked")
-                           : launch_att(attention16_kernel<f16_t, 64, 1, 64, true, false, false, true>, p, lds, to_stream(s), 64, 1, "dts_attention_masked");
+  DTS_DISPATCH_16BIT("dts_attention_masked", dtype,
+                     return launch_att(attention16_kernel<T, 64, 1, 64, true, false, false, true>, p, lds, to_stream(s), 64, 1, "dts_attention_masked"));
 }
 
 extern "C" int dts_attention(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, dts_stream s) {

@@ -290,13 +290,7 @@ extern "C" int dts_conv_in3(const float* x, const float* w, const float* bias, v
     if (g > 2048) g = 2048;
 #define DTS_IN3_MFMA(TT, NT_)                                                                                                    \
   hipLaunchKernelGGL((conv_in3_mfma_kernel<TT, NT_>), dim3((int)g), dim3(256), 0, st, x, w, bias, (TT*)out, (int)nseg, h, w_)
-    if (dtype == DTS_BF16) {
-      if (cout == 192) DTS_IN3_MFMA(bf16_t, 12); else if (cout == 128) DTS_IN3_MFMA(bf16_t, 8); else DTS_IN3_MFMA(bf16_t, 4);
-    } else if (dtype == DTS_F32) {
-      if (cout == 192) DTS_IN3_MFMA(float, 12); else if (cout == 128) DTS_IN3_MFMA(float, 8); else DTS_IN3_MFMA(float, 4);
-    } else {
-      if (cout == 192) DTS_IN3_MFMA(f16_t, 12); else if (cout == 128) DTS_IN3_MFMA(f16_t, 8); else DTS_IN3_MFMA(f16_t, 4);
-    }
+    DTS_DISPATCH_DTYPE(dtype, { if (cout == 192) DTS_IN3_MFMA(T, 12); else if (cout == 128) DTS_IN3_MFMA(T, 8); else DTS_IN3_MFMA(T, 4); });
 #undef DTS_IN3_MFMA
     DTS_CHECK_LAUNCH("dts_conv_in3");
     return DTS_OK;

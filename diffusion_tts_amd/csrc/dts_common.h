@@ -180,3 +180,10 @@ template <typename F> __device__ __forceinline__ F wave_sum(F v) {
     case DTS_F16: { using T = f16_t; __VA_ARGS__; } break;               \
     default: dts_set_error("bad dtype %d", (int)(dtype)); return DTS_ERR_ARG; \
   }
+// the same for entry points that take the 16-bit types only; `name` is the entry point's, for the refusal
+#define DTS_DISPATCH_16BIT(name, dtype, ...)                             \
+  switch (dtype) {                                                       \
+    case DTS_BF16: { using T = bf16_t; __VA_ARGS__; } break;             \
+    case DTS_F16: { using T = f16_t; __VA_ARGS__; } break;               \
+    default: dts_set_error("%s: dtype %d (16-bit types only)", name, (int)(dtype)); return DTS_ERR_ARG; \
+  }

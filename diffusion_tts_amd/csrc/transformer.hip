@@ -1,7 +1,9 @@
 // The three primitives of the SD U-Net's transformer blocks (diffusers BasicTransformerBlock: attention.py, attention_processor.py, activations.py
 // of the reference's vendored diffusers) that the EDM networks never needed: attention over a SHORT foreign sequence (the 77 text tokens),
-// LayerNorm over channels, and GEGLU.  16-bit storage (bf16 / f16), f32 arithmetic, gfx950 only.
-#include "dts_common.h"
+// LayerNorm over channels, and GEGLU.  16-bit storage (bf16 / f16), f32 arithmetic, gfx950 only.  LayerNorm also serves the CLIP towers,
+// and has a second form for the split-precision vision tower (dts.h DTS_F16X3): float32 rows, float64 arithmetic, the result as float32
+// rows and / or the next convolution's operand image (row_forms.h holds the one kernel behind both forms and behind dts_vit_head).
+#include "row_forms.h"
 #include <math.h>
 #include <map>
 #include <mutex>
@@ -201,53 +203,6 @@ int xatt(const XAttP& p, int d, unsigned grid, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// LayerNorm over the channels of a row: one wave per row, the row held in registers (<= 4 vectors of 8 per lane = 2048 channels), so the
-// variance is the mean of (x - mean)^2 with the mean already known -- no E[x^2] - E[x]^2 cancellation for rows with a large mean.
-template <typename T>
-__global__ __launch_bounds__(256) void layer_norm_kernel(const T* __restrict__ x, T* __restrict__ out, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, long long rows, int c, float eps) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int nvec = c >> 3;
-  const uint4* xr = reinterpret_cast<const uint4*>(x + row * c);
-  float f[4][8];
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int v = lane + 64 * i;
-    if (v < nvec) {
-      unpack16<T>(xr[v], f[i]);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum += f[i][e];
-    }
-  }
-  const float mean = wave_sum(sum) / (float)c;
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (lane + 64 * i < nvec) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float dlt = f[i][e] - mean; sq += dlt * dlt; }
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)c + eps);
-  uint4* orow = reinterpret_cast<uint4*>(out + row * c);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int v = lane + 64 * i;
-    if (v < nvec) {
-      const float4 g0 = reinterpret_cast<const float4*>(gamma)[2 * v], g1 = reinterpret_cast<const float4*>(gamma)[2 * v + 1];
-      const float4 b0 = reinterpret_cast<const float4*>(beta)[2 * v], b1 = reinterpret_cast<const float4*>(beta)[2 * v + 1];
-      const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w}, b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-      float y[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) y[e] = fmaf((f[i][e] - mean) * rstd, g[e], b[e]);
-      orow[v] = pack16<T>(y);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // GEGLU: out[r][j] = x[r][j] * gelu(x[r][inner + j]), gelu(g) = g * Phi(g) with Phi(g) = erfc(-g / sqrt 2) / 2 -- the erf form
 // 0.5 * (1 + erf(g / sqrt 2)) written without its cancellation for negative g (at g = -6 the sum 1 + erf keeps no correct bit in f32).
 template <typename T>
@@ -273,7 +228,8 @@ extern "C" int dts_cross_attention(const void* q, const void* kv, const int32_t*
   DTS_CHECK_ARG(q && kv && out, "dts_cross_attention: null pointer");
   DTS_CHECK_ARG(n > 0 && tq > 0 && tk > 0 && heads > 0 && kv_n > 0, "dts_cross_attention: bad shape");
   DTS_CHECK_ARG(kv_rows != nullptr || kv_n == n, "dts_cross_attention: %d key/value rows for %d samples need a kv_rows map", kv_n, n);
-  DTS_CHECK_ARG(dtype == DTS_BF16 || dtype == DTS_F16, "dts_cross_attention: dtype %d (16-bit types only)", dtype);
+  int (*run)(const XAttP&, int, unsigned, hipStream_t) = nullptr;
+  DTS_DISPATCH_16BIT("dts_cross_attention", dtype, run = xatt<T>);
   DTS_CHECK_ARG(d == 64 || d == 128 || d == 256, "dts_cross_attention: head dim %d unsupported (64/128/256)", d);
   DTS_CHECK_ARG(scale > 0.f && isfinite(scale), "dts_cross_attention: scale must be positive and finite");
   DTS_CHECK_ARG(((uintptr_t)q | (uintptr_t)kv | (uintptr_t)out) % 16 == 0, "dts_cross_attention: pointers must be 16-byte aligned");
@@ -288,7 +244,7 @@ extern "C" int dts_cross_attention(const void* q, const void* kv, const int32_t*
   p.qblocks = (int)((chunks + p.qchunks - 1) / p.qchunks);
   const long long grid = nh * p.qblocks;
   DTS_CHECK_ARG(grid < (1ll << 31), "dts_cross_attention: grid too large");
-  int r = dtype == DTS_BF16 ? xatt<bf16_t>(p, d, (unsigned)grid, to_stream(s)) : xatt<f16_t>(p, d, (unsigned)grid, to_stream(s));
+  int r = run(p, d, (unsigned)grid, to_stream(s));
   if (r == DTS_ERR_UNSUPPORTED) dts_set_error("dts_cross_attention: head dim %d unsupported", d);
   return r;
 }
@@ -296,31 +252,31 @@ extern "C" int dts_cross_attention(const void* q, const void* kv, const int32_t*
 extern "C" int dts_layer_norm(const void* x, void* out, int dtype, int64_t rows, int c, float eps, const float* gamma, const float* beta,
                               dts_stream s) {
   DTS_CHECK_ARG(x && out && gamma && beta, "dts_layer_norm: null pointer");
-  DTS_CHECK_ARG(dtype == DTS_BF16 || dtype == DTS_F16, "dts_layer_norm: dtype %d (16-bit types only)", dtype);
-  DTS_CHECK_ARG(rows > 0 && rows < (1ll << 32), "dts_layer_norm: bad row count");
-  DTS_CHECK_ARG(c > 0 && c % 8 == 0 && c <= 2048, "dts_layer_norm: %d channels (a multiple of 8, at most 2048)", c);
-  DTS_CHECK_ARG(eps >= 0.f, "dts_layer_norm: eps");
-  DTS_CHECK_ARG(((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0, "dts_layer_norm: pointers must be 16-byte aligned");
-  const unsigned grid = (unsigned)((rows + 3) / 4);
-  if (dtype == DTS_BF16)
-    hipLaunchKernelGGL(layer_norm_kernel<bf16_t>, dim3(grid), dim3(256), 0, to_stream(s), (const bf16_t*)x, (bf16_t*)out, gamma, beta, (long long)rows, c, eps);
-  else
-    hipLaunchKernelGGL(layer_norm_kernel<f16_t>, dim3(grid), dim3(256), 0, to_stream(s), (const f16_t*)x, (f16_t*)out, gamma, beta, (long long)rows, c, eps);
-  DTS_CHECK_LAUNCH("dts_layer_norm");
-  return DTS_OK;
+  DTS_DISPATCH_16BIT("dts_layer_norm", dtype, {
+    DTS_CHECK_ARG(rows > 0 && rows < (1ll << 32), "dts_layer_norm: bad row count");
+    return row_norm<float>("dts_layer_norm", (const T*)x, c, Out16<T>{(T*)out}, gamma, beta, rows, c, 8, eps, s);
+  });
+}
+
+// LayerNorm over f32 rows [rows][c]; out_f32 (nullable): the normalised rows; out_split (nullable): their operand image [rows][2c].
+// The two outputs come from the same registers, so the image is the split of the f32 rows whether or not those are written.
+extern "C" int dts_layer_norm_x3(const float* x, float* out_f32, void* out_split, int64_t rows, int c, float eps, const float* gamma,
+                                 const float* beta, dts_stream s) {
+  DTS_CHECK_ARG(x && gamma && beta, "dts_layer_norm_x3: null pointer");
+  DTS_CHECK_ARG(out_f32 || out_split, "dts_layer_norm_x3: neither out_f32 nor out_split");
+  DTS_CHECK_ARG(rows > 0 && rows < (1ll << 32), "dts_layer_norm_x3: bad row count");
+  return row_norm<double>("dts_layer_norm_x3", x, c, OutF32X3{out_f32, (uint4*)out_split}, gamma, beta, rows, c, 32, eps, s);
 }
 
 extern "C" int dts_geglu(const void* x, void* out, int dtype, int64_t rows, int inner, dts_stream s) {
   DTS_CHECK_ARG(x && out, "dts_geglu: null pointer");
-  DTS_CHECK_ARG(dtype == DTS_BF16 || dtype == DTS_F16, "dts_geglu: dtype %d (16-bit types only)", dtype);
-  DTS_CHECK_ARG(rows > 0 && inner > 0 && inner % 8 == 0, "dts_geglu: %lld rows x %d (inner a multiple of 8)", (long long)rows, inner);
-  DTS_CHECK_ARG(((uintptr_t)x | (uintptr_t)out) % 16 == 0, "dts_geglu: pointers must be 16-byte aligned");
-  const long long nvec = rows * (inner / 8), grid = (nvec + 255) / 256;
-  DTS_CHECK_ARG(grid < (1ll << 31), "dts_geglu: grid too large");
-  if (dtype == DTS_BF16)
-    hipLaunchKernelGGL(geglu_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), (const bf16_t*)x, (bf16_t*)out, (long long)rows, inner);
-  else
-    hipLaunchKernelGGL(geglu_kernel<f16_t>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), (const f16_t*)x, (f16_t*)out, (long long)rows, inner);
+  DTS_DISPATCH_16BIT("dts_geglu", dtype, {
+    DTS_CHECK_ARG(rows > 0 && inner > 0 && inner % 8 == 0, "dts_geglu: %lld rows x %d (inner a multiple of 8)", (long long)rows, inner);
+    DTS_CHECK_ARG(((uintptr_t)x | (uintptr_t)out) % 16 == 0, "dts_geglu: pointers must be 16-byte aligned");
+    const long long nvec = rows * (inner / 8), grid = (nvec + 255) / 256;
+    DTS_CHECK_ARG(grid < (1ll << 31), "dts_geglu: grid too large");
+    hipLaunchKernelGGL(geglu_kernel<T>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), (const T*)x, (T*)out, (long long)rows, inner);
+  });
   DTS_CHECK_LAUNCH("dts_geglu");
   return DTS_OK;
 }

@@ -676,14 +676,18 @@ def group_rows(x):
     return slot, reps, count
 
 
+def _norm_pair(who, gamma, beta, c):
+    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
+        raise ValueError(f'{who}: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} for {c} channels')
+    return _ptr(gamma, 'gamma', torch.float32), _ptr(beta, 'beta', torch.float32)
+
+
 def layer_norm(x, gamma, beta, eps=1e-5):
     """LayerNorm over the last dimension of a contiguous float16 / bfloat16 tensor; gamma, beta float32 [c] (dts_layer_norm)."""
     c = x.shape[-1]
-    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
-        raise ValueError(f'layer_norm: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} for {c} channels')
+    gp, bp = _norm_pair('layer_norm', gamma, beta, c)
     out = torch.empty_like(x)
-    _call('dts_layer_norm', _ptr(x, 'x'), _ptr(out), dt_code(x.dtype), x.numel() // c, c, float(eps), _ptr(gamma, 'gamma', torch.float32),
-          _ptr(beta, 'beta', torch.float32))
+    _call('dts_layer_norm', _ptr(x, 'x'), _ptr(out), dt_code(x.dtype), x.numel() // c, c, float(eps), gp, bp)
     return out
 
 
@@ -703,17 +707,25 @@ def patch_kpad(patch):
     return (3 * patch * patch + 63) // 64 * 64
 
 
+def _patch_rows(who, x, patch, kpad, kmul=None):
+    """what ops.patchify and ops.patchify_x3 ask of their arguments: -> (n, S, S // patch, kpad).  kmul: the multiple kpad is held to HERE
+    (the operand image's 32); the 16-bit form leaves that refusal to the library."""
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError(f'{who}: x {tuple(x.shape)} is not [n, 3, S, S]')
+    n, _, S, _ = x.shape
+    if patch <= 0 or S % patch:
+        raise ValueError(f'{who}: image size {S} is not a multiple of the patch size {patch}')
+    kpad = patch_kpad(patch) if kpad is None else int(kpad)
+    if kmul and (kpad % kmul or kpad < 3 * patch * patch):
+        raise ValueError(f'{who}: kpad {kpad} (a multiple of {kmul}, at least 3*patch*patch = {3 * patch * patch})')
+    return n, S, S // patch, kpad
+
+
 def patchify(x, patch, dtype, kpad=None, out=None):
     """pixel_values float32 NCHW [n, 3, S, S] -> patch rows [n, (S/patch)^2, kpad] in float16 / bfloat16: column (c*patch + py)*patch + px of
     row gy*(S/patch) + gx is x[n, c, gy*patch + py, gx*patch + px] rounded once, columns from 3*patch*patch on are zero (dts_patchify).
     kpad defaults to patch_kpad(patch)."""
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-        raise ValueError(f'patchify: x {tuple(x.shape)} is not [n, 3, S, S]')
-    n, _, S, _ = x.shape
-    if patch <= 0 or S % patch:
-        raise ValueError(f'patchify: image size {S} is not a multiple of the patch size {patch}')
-    kpad = patch_kpad(patch) if kpad is None else int(kpad)
-    g = S // patch
+    n, S, g, kpad = _patch_rows('patchify', x, patch, kpad)
     if out is None:
         out = torch.empty((n, g * g, kpad), dtype=dtype, device=x.device)
     elif tuple(out.shape) != (n, g * g, kpad):
@@ -722,12 +734,17 @@ def patchify(x, patch, dtype, kpad=None, out=None):
     return out
 
 
+def _token_tables(who, patches, cls, pos):
+    n, tp, c = patches.shape
+    if tuple(cls.shape) != (c,) or tuple(pos.shape) != (tp + 1, c):
+        raise ValueError(f'{who}: cls {tuple(cls.shape)} / pos {tuple(pos.shape)} for patches {tuple(patches.shape)}')
+    return n, tp, c
+
+
 def vit_tokens(patches, cls, pos):
     """patches [n, t-1, c] float16 / bfloat16, cls float32 [c], pos float32 [t, c] -> tokens [n, t, c]: row 0 = cls + pos[0], row 1 + p =
     patches[:, p] + pos[1 + p], summed in float32 and rounded once (dts_vit_tokens)."""
-    n, tp, c = patches.shape
-    if tuple(cls.shape) != (c,) or tuple(pos.shape) != (tp + 1, c):
-        raise ValueError(f'vit_tokens: cls {tuple(cls.shape)} / pos {tuple(pos.shape)} for patches {tuple(patches.shape)}')
+    n, tp, c = _token_tables('vit_tokens', patches, cls, pos)
     out = torch.empty((n, tp + 1, c), dtype=patches.dtype, device=patches.device)
     _call('dts_vit_tokens', _ptr(patches, 'patches'), _ptr(cls, 'cls', torch.float32), _ptr(pos, 'pos', torch.float32), _ptr(out),
           dt_code(patches.dtype), n, tp + 1, c)
@@ -778,11 +795,9 @@ def vit_head(tokens, gamma, beta, eps=1e-5):
     """tokens [n, t, c] float16 / bfloat16 -> float32 [n, c] = LayerNorm(tokens[:, 0]) * gamma + beta: the class token only, the other
     tokens are not read (dts_vit_head); gamma, beta float32 [c].  The projection follows as ops.linear."""
     n, t, c = tokens.shape
-    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
-        raise ValueError(f'vit_head: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} for {c} channels')
+    gp, bp = _norm_pair('vit_head', gamma, beta, c)
     out = torch.empty((n, c), dtype=torch.float32, device=tokens.device)
-    _call('dts_vit_head', _ptr(tokens, 'tokens'), _ptr(out), dt_code(tokens.dtype), n, t, c, float(eps), _ptr(gamma, 'gamma', torch.float32),
-          _ptr(beta, 'beta', torch.float32))
+    _call('dts_vit_head', _ptr(tokens, 'tokens'), _ptr(out), dt_code(tokens.dtype), n, t, c, float(eps), gp, bp)
     return out
 
 
@@ -793,12 +808,6 @@ def _f32_gpu(t, who, name):
     if not torch.is_tensor(t) or t.dtype != torch.float32:
         raise ValueError(f'{who}: {name} must be a float32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}')
     return _ptr(t, name, torch.float32)
-
-
-def _norm_pair(who, gamma, beta, c):
-    if tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
-        raise ValueError(f'{who}: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} for {c} channels')
-    return _ptr(gamma, 'gamma', torch.float32), _ptr(beta, 'beta', torch.float32)
 
 
 def layer_norm_x3(x, gamma, beta, eps=1e-5, want_f32=False, want_split=True):
@@ -845,15 +854,7 @@ def patchify_x3(x, patch, kpad=None):
     kpad]; dts_patchify_x3): ops.patchify's column order, columns from 3*patch*patch on are zero.  kpad defaults to patch_kpad(patch) and must
     be a multiple of 32 covering 3*patch*patch."""
     xp = _f32_gpu(x, 'patchify_x3', 'x')
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-        raise ValueError(f'patchify_x3: x {tuple(x.shape)} is not [n, 3, S, S]')
-    n, _, S, _ = x.shape
-    if patch <= 0 or S % patch:
-        raise ValueError(f'patchify_x3: image size {S} is not a multiple of the patch size {patch}')
-    kpad = patch_kpad(patch) if kpad is None else int(kpad)
-    if kpad % 32 or kpad < 3 * patch * patch:
-        raise ValueError(f'patchify_x3: kpad {kpad} (a multiple of 32, at least 3*patch*patch = {3 * patch * patch})')
-    g = S // patch
+    n, S, g, kpad = _patch_rows('patchify_x3', x, patch, kpad, 32)
     img = torch.empty((n, g, g, 2 * kpad), dtype=torch.float16, device=x.device)
     _call('dts_patchify_x3', xp, _ptr(img), n, S, patch, kpad)
     return SplitAct(img, kpad)
@@ -865,9 +866,7 @@ def vit_tokens_f32(patches, cls, pos):
     pp = _f32_gpu(patches, 'vit_tokens_f32', 'patches')
     if patches.dim() != 3:
         raise ValueError(f'vit_tokens_f32: patches {tuple(patches.shape)} is not [n, t - 1, c]')
-    n, tp, c = patches.shape
-    if tuple(cls.shape) != (c,) or tuple(pos.shape) != (tp + 1, c):
-        raise ValueError(f'vit_tokens_f32: cls {tuple(cls.shape)} / pos {tuple(pos.shape)} for patches {tuple(patches.shape)}')
+    n, tp, c = _token_tables('vit_tokens_f32', patches, cls, pos)
     if tp < 1 or c <= 0 or c % 4:
         raise ValueError(f'vit_tokens_f32: {tp} patches x {c} channels (at least one patch, channels a multiple of 4)')
     out = torch.empty((n, tp + 1, c), dtype=torch.float32, device=patches.device)

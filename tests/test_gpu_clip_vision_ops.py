@@ -165,7 +165,7 @@ def test_gelu_refuses_bad_arguments(ops):
 @pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('c', [8, 128, 1024, 1544, 2048])
 def test_head(ops, dtype, c):
-    """c = 8: one lane holds the row; 1544 = 193 vectors: the fourth register vector (i = 3 of vit_head_kernel) on a single lane; 2048: all
+    """c = 8: one lane holds the row; 1544 = 193 vectors: the fourth register vector (i = 3 of row_norm_kernel) on a single lane; 2048: all
     four whole (launch_rules.LAYER_NORM_WIDTHS).
     Measured on an MI355X (err/bound of the LayerNorm, float16 / bfloat16; a record, not the source of any bound): against the rounded token
     c = 8: 0.010 / 0.013, c = 1544: 0.010 / 0.009, c = 2048: 0.018 / 0.015; against the unrounded token 0.160 / 0.220, 0.297 / 0.301,

@@ -184,21 +184,31 @@ def test_patchify_x3_refusals(ops):
 
 
 # ---- tokens and head -------------------------------------------------------------------------------
-@pytest.mark.parametrize('t', [2, 17, 257])
-@pytest.mark.parametrize('c', [64, 1024])
-def test_vit_tokens_and_head_f32(ops, c, t):
+def f32_ulp(ref):
+    """the float32 ulp at a float64 value"""
+    return 2.0 ** (torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126))) - 23)
+
+
+def check_tokens_f32(ops, c, t):
+    """dts_vit_tokens_f32 on n = 3 samples drawn from g(c + t): half an ulp from float64 and bit for bit torch's float32 add.
+    -> (tokens, the generator, for the head's parameters)"""
     n, gen = 3, g(c + t)
     patches = torch.randn(n, t - 1, c, generator=gen).to(DEV)
     cls, pos = torch.randn(c, generator=gen).to(DEV), (0.5 * torch.randn(t, c, generator=gen)).to(DEV)
     ref = torch.cat([cls.double().expand(n, 1, c), patches.double()], 1) + pos.double()
     tok = ops.vit_tokens_f32(patches, cls, pos)
     assert tok.dtype == torch.float32 and tuple(tok.shape) == (n, t, c)
-    ulp = 2.0 ** (torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126))) - 23)
-    worst = float(((tok.double() - ref).abs() / ulp).max())
+    worst = float(((tok.double() - ref).abs() / f32_ulp(ref)).max())
     print(f'vit_tokens_f32 c={c} t={t}: max|tokens - f64| = {worst:.3f} ulp')
     assert worst <= 1.0
     assert torch.equal(tok, torch.cat([cls.expand(n, 1, c), patches], 1) + pos)               # the correctly rounded sum
-    # the head: LayerNorm of token 0 alone; a class token of mean 3 so that the mean matters
+    return tok, gen
+
+
+def check_head_f32(ops, tok, gen, c, t):
+    """dts_vit_head_f32: LayerNorm of token 0 alone; a class token of mean 3 so that the mean matters.  -> (head, its float64 reference,
+    the row it normalises, gamma, beta, eps)"""
+    n = tok.shape[0]
     tokens = tok.clone()
     tokens[:, 0] += 3.0
     gamma, beta = (1.0 + 0.3 * torch.randn(c, generator=gen)).to(DEV), (0.5 * torch.randn(c, generator=gen)).to(DEV)
@@ -211,10 +221,40 @@ def test_vit_tokens_and_head_f32(ops, c, t):
     err_k, err_t = float((head.double() - href).abs().max()), float((h32.double() - href).abs().max())
     print(f'vit_head_f32 c={c} t={t}: max|kernel - f64| {err_k:.3e}, max|torch f32 - f64| {err_t:.3e}, ratio {err_k / err_t:.3f}')
     assert err_t > 0 and err_k <= 2 * err_t
-    # the same arithmetic as layer_norm_x3 on that row, and the other tokens are not read
-    assert torch.equal(head, ops.layer_norm_x3(x0.view(1, n, c), gamma, beta, eps, want_f32=True, want_split=False).view(n, c))
-    tokens[:, 1:] = float('nan')
+    tokens[:, 1:] = float('nan')                                                              # the other tokens are not read
     assert torch.equal(ops.vit_head_f32(tokens, gamma, beta, eps), head)
+    return head, href, x0, gamma, beta, eps
+
+
+@pytest.mark.parametrize('t', [2, 17, 257])
+@pytest.mark.parametrize('c', [64, 1024])
+def test_vit_tokens_and_head_f32(ops, c, t):
+    tok, gen = check_tokens_f32(ops, c, t)
+    head, _, x0, gamma, beta, eps = check_head_f32(ops, tok, gen, c, t)
+    # the same arithmetic as layer_norm_x3 on that row
+    assert torch.equal(head, ops.layer_norm_x3(x0.view(1, -1, c), gamma, beta, eps, want_f32=True, want_split=False).view(-1, c))
+
+
+@pytest.mark.parametrize('t', [2, 17])
+def test_vit_tokens_f32_four_channel_vectors(ops, t):
+    """c = 68: a multiple of 4 but not of 8 -- the float32 form of vit_tokens_kernel owns 4 channels per thread where the 16-bit forms own 8"""
+    check_tokens_f32(ops, 68, t)
+
+
+@pytest.mark.parametrize('t', [2, 17])
+@pytest.mark.parametrize('c', [8, 1544, 2048])
+def test_vit_head_f32_widths(ops, c, t):
+    """c = 8: one lane holds the row; 1544 = 193 vectors: the fourth register vector (i = 3 of row_norm_kernel) on a single lane; 2048: every
+    lane full.  The kernel forms y in float64 and rounds once: half a float32 ulp of the float64 value plus float64 noise, asserted at one
+    ulp; the smallest |reference| on these inputs is 2.9e-5, far from where the float64 noise could reach an ulp.
+    Measured on an MI355X (a record, not the source of the bound): 0.465 to 0.500 ulp, 0.18 to 0.85 of torch-float32's error."""
+    tok, gen = check_tokens_f32(ops, c, t)
+    head, href, x0, gamma, beta, eps = check_head_f32(ops, tok, gen, c, t)
+    worst = float(((head.double() - href).abs() / f32_ulp(href)).max())
+    print(f'vit_head_f32 c={c} t={t}: max|head - f64| = {worst:.3f} ulp')
+    assert worst <= 1.0
+    if c % 32 == 0:                                                                          # dts_layer_norm_x3 takes multiples of 32 only
+        assert torch.equal(head, ops.layer_norm_x3(x0.view(1, -1, c), gamma, beta, eps, want_f32=True, want_split=False).view(-1, c))
 
 
 def test_vit_tokens_and_head_f32_refusals(ops):
