@@ -66,6 +66,7 @@ SIGNATURES = {
     'dts_patchify_x3': [_p, _p, _i, _i, _i, _i, _p],
     'dts_vit_tokens_f32': [_p, _p, _p, _p, _i, _i, _i, _p],
     'dts_vit_head_f32': [_p, _p, _i, _i, _i, _f, _p, _p, _p],
+    'dts_text_tokens_f32': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     'dts_linear': [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     'dts_pos_embedding': [_p, _p, _p, _i, _i, _i, _p],
     'dts_edm_precond_in': [_p, _p, _i, _f, _p, _p, _i, _i, _p],
@@ -74,6 +75,7 @@ SIGNATURES = {
     'dts_split3_f16': [_p, _i, _p, _i, _p, _i64, _p],
     'dts_split2_f16': [_p, _i, _p, _i64, _p],
     'dts_attention_x3': [_p, _p, _i, _i, _i, _i, _i, _f, _p],
+    'dts_attention_x3_masked': [_p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p],
     'dts_cast_from_f32': [_p, _p, _i, _i64, _p],
     'dts_cast_to_f32': [_p, _i, _p, _i64, _p],
     'dts_heun_xhat': [_p, _i, _i, _p, _i, _d, _p, _i, _i, _p],
@@ -98,7 +100,7 @@ OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 121              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 122              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

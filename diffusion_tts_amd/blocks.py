@@ -3,7 +3,7 @@ the way from a stock diffusers / transformers state dict to a launch sequence on
   Params                         f32 upload, norm pairs, conv / Linear weights packed for dts_conv2d (zero-padded where asked), stacked q | k | v
   resnet_params, resnet          diffusers' ResnetBlock2D (resnet.py), with or without the time-embedding addend and the concatenated skip
   clip_layers, clip_encoder      transformers' CLIPEncoderLayer (modeling_clip.py); the attention call is the tower's own
-  clip_encoder_x3                the same layer in the split-precision mode (the vision tower's parity-grade form)
+  clip_encoder_x3                the same layer in the split-precision mode (both towers' parity-grade forms; the text tower passes its masked attention)
   clip_config_errors, clip_section, clip_files, diffusers_weights, read_tensors, check_shapes, require_gpu
                                  the refusals and the file reading: every network names what it does not take, none guesses
 Kernels are called through the module (`ops.conv2d(...)`, never a name imported from it): the tools under tools/ time a forward by replacing
@@ -121,17 +121,23 @@ def clip_encoder(h, layers, eps, act, attend):
     return h
 
 
-def clip_encoder_x3(h, layers, eps, act, heads, scale):
+def clip_encoder_x3(h, layers, eps, act, heads, scale, attend=None):
     """clip_encoder in the split-precision mode (ops.F16X3; the layers' weights are X3Weights): the residual stream h [n, t, 1, C] is float32
     throughout, and every operand of a projection is written as its image by the kernel that produces it (layer_norm_x3, gelu_x3 and, where
     ops.attention_x3_ok, the qkv projection's and the attention's own epilogues) -- no float32 tensor exists between them, no split pass runs.
-    Plain attention only: d = 64 at t >= 128 on the split-precision kernel, every other shape on the float32 one."""
+    attend None (the vision tower): plain attention, d = 64 at t >= 128 on the split-precision kernel, every other shape on the float32 one.
+    attend a callable (the text tower: ops.attention_x3_masked with its mask, split_out=True): it receives the qkv projection's SplitQKV
+    [n, t, 3C] and returns the proj convolution's SplitAct; the fused images are then used whatever t is (the qkv epilogue takes any pixel
+    count, so no dts_split2_f16 pass is needed for the short sequences either) and ops.attention_x3_ok is not asked."""
     n, t, _, C = h.shape
-    fuse = ops.attention_x3_ok(t, C // heads)
+    fuse = attend is not None or ops.attention_x3_ok(t, C // heads)
     for P in layers:
         y = ops.layer_norm_x3(h, *P.ln1, eps=eps)
         qkv = ops.conv2d(y, P.w_qkv, P.b_qkv, out_split2=fuse)
-        a = ops.attention(qkv.view(n, t, 3 * C), heads, scale, x3=True, split_out=fuse)
+        if attend is not None:
+            a = attend(qkv.view(n, t, 3 * C))
+        else:
+            a = ops.attention(qkv.view(n, t, 3 * C), heads, scale, x3=True, split_out=fuse)
         h = ops.conv2d(a if fuse else a.view(n, t, 1, C), P.w_o, P.b_o, residual=h)
         y = ops.layer_norm_x3(h, *P.ln2, eps=eps)
         f = ops.conv2d(y, P.w_fc1, P.b_fc1)
@@ -144,7 +150,7 @@ def clip_config_errors(dtype, hidden_size, num_attention_heads, intermediate_siz
                        split_precision=False):
     """the settings of a CLIP tower that this build's kernels do not take, each with its value: the clauses both towers share.  head_dims:
     the head dims of the tower's attention kernel, head_kernel: how the message names them.  split_precision: the check of the tower's ops.F16X3
-    form (clip_vision.CLIPVisionTowerX3; the text tower has none: it would need a masked split-precision attention)."""
+    form (clip_vision.CLIPVisionTowerX3, clip_text.CLIPTextTowerX3)."""
     bad = []
     if split_precision:
         if not (isinstance(dtype, str) and dtype == ops.F16X3):

@@ -10,8 +10,16 @@ CLIPAttention with the causal mask, CLIPMLP).  The twin of clip_vision.CLIPVisio
   fc1 + activation                           -> 1x1 dts_conv2d + dts_gelu (quick-GELU or erf GELU, in place)
   last_hidden_state[b, eos position]         -> torch indexing (plumbing); the positions come from the ids on the host (pooled_positions)
   text_projection                            -> dts_cast_to_f32 + dts_linear (f32), when the state dict has one
-Activations are [n, t, 1, channels] in `dtype` (float16 or bfloat16).  There is NO float32 and no split-precision (`f16x3`) form of this
-tower -- dts_layer_norm is 16-bit only -- and NO graph capture: the tower runs once per prompt over 2 x 77 tokens, it is not a hot path.
+Activations are [n, t, 1, channels] in `dtype` (float16 or bfloat16): a 16-bit THROUGHPUT mode (SD's text encoder runs in float16 in the
+reference; its CLIP scorer embeds the prompt in float32).  CLIPTextTowerX3 (dtype ops.F16X3, 'f16x3') is the PARITY-GRADE mode, the twin of
+clip_vision.CLIPVisionTowerX3 -- float32 activations, every matrix product in split precision on the 16-bit matrix cores:
+  tokens -> dts_text_tokens_f32; layer_norm1 / 2, final_layer_norm -> dts_layer_norm_x3; projections -> dts_conv2d in DTS_F16X3 (the qkv
+  projection writes the attention's operand image); causal attention -> dts_attention_x3_masked at every t (it writes out_proj's operand
+  image); activation -> dts_gelu_x3; text_projection -> dts_linear on the float32 pooled row
+It is held to the float32 module's own distance from float64 (tests/test_gpu_clip_text_x3.py).  torch.float32 itself is refused by both
+classes: there is no float32 matrix-instruction form of this tower.  CLIPTextTower keeps refusing every dtype but the two 16-bit ones,
+'f16x3' included: the split-precision mode is a class of its own with a check of its own (check_config_x3).  NO graph capture: the tower
+runs once per prompt over 2 x 77 tokens, it is not a hot path.
 
 Parameters: a state dict with transformers' key names (`text_model.*`, `text_projection.weight`).  Shapes the kernels do not take are
 refused by name at construction (check_config); an attention mask that is not right padding is refused by name at call time.
@@ -35,6 +43,17 @@ def check_config(hidden_size, num_attention_heads, intermediate_size, hidden_act
     """Raises ValueError naming every setting of a CLIP text configuration that this build's kernels do not take, with its value."""
     bad = blocks.clip_config_errors(dtype, hidden_size, num_attention_heads, intermediate_size, hidden_act, projection_dim,
                                     (64,), 'dts_attention_masked\'s 64')
+    if vocab_size <= 0 or max_position_embeddings <= 0:
+        bad.append(f'vocab_size={vocab_size}, max_position_embeddings={max_position_embeddings}')
+    if bad:
+        raise ValueError('CLIPTextTower: ' + '; '.join(bad))
+
+
+def check_config_x3(hidden_size, num_attention_heads, intermediate_size, hidden_act, dtype, vocab_size=49408, max_position_embeddings=77,
+                    projection_dim=None):
+    """check_config for CLIPTextTowerX3, whose only dtype is ops.F16X3 (head dim 64: dts_attention_x3_masked's)"""
+    bad = blocks.clip_config_errors(dtype, hidden_size, num_attention_heads, intermediate_size, hidden_act, projection_dim,
+                                    (64,), 'dts_attention_x3_masked\'s 64', split_precision=True)
     if vocab_size <= 0 or max_position_embeddings <= 0:
         bad.append(f'vocab_size={vocab_size}, max_position_embeddings={max_position_embeddings}')
     if bad:
@@ -112,8 +131,8 @@ def read_text_tensors(path):
 
 
 class TextOutput:
-    """what the tower returns: `[0]` / `.last_hidden_state` [n, t, C] and `.pooler_output` [n, C] in the tower's dtype, and, with a
-    projection, `.text_embeds` float32 [n, projection_dim] (else None)"""
+    """what the tower returns: `[0]` / `.last_hidden_state` [n, t, C] and `.pooler_output` [n, C] in the tower's dtype (float32 from
+    CLIPTextTowerX3), and, with a projection, `.text_embeds` float32 [n, projection_dim] (else None)"""
 
     def __init__(self, last_hidden_state, pooler_output, text_embeds):
         self.last_hidden_state, self.pooler_output, self.text_embeds = last_hidden_state, pooler_output, text_embeds
@@ -123,14 +142,18 @@ class TextOutput:
 
 
 class CLIPTextTower:
+    """dtype torch.float16 / torch.bfloat16: the 16-bit modes.  The PARITY-GRADE mode is CLIPTextTowerX3 below."""
+    SPLIT_PRECISION, DEFAULT_DTYPE = False, torch.float16
+
     def __init__(self, state_dict, vocab_size=49408, hidden_size=768, num_attention_heads=12, intermediate_size=3072, num_hidden_layers=12,
                  max_position_embeddings=77, hidden_act='quick_gelu', layer_norm_eps=1e-5, eos_token_id=49407, projection_dim=None,
                  device='cuda', dtype=torch.float16):
         """The defaults are those of SD-1.5's text encoder (openai/clip-vit-large-patch14's text side).  projection_dim None: taken from
         text_projection.weight when the state dict has one (a CLIPTextModel has none: no `.text_embeds` then)."""
-        check_config(hidden_size, num_attention_heads, intermediate_size, hidden_act, dtype, vocab_size, max_position_embeddings, projection_dim)
+        (check_config_x3 if self.SPLIT_PRECISION else check_config)(hidden_size, num_attention_heads, intermediate_size, hidden_act, dtype,
+                                                                    vocab_size, max_position_embeddings, projection_dim)
         blocks.require_gpu('CLIPTextTower')
-        self.device, self.dtype = torch.device(device), dtype
+        self.device, self.dtype, self.x3 = torch.device(device), dtype, self.SPLIT_PRECISION
         self.vocab, self.hidden, self.heads, self.inter = int(vocab_size), int(hidden_size), int(num_attention_heads), int(intermediate_size)
         self.layers_n, self.max_pos, self.act, self.eps = int(num_hidden_layers), int(max_position_embeddings), hidden_act, float(layer_norm_eps)
         self.eos = int(eos_token_id)
@@ -145,9 +168,11 @@ class CLIPTextTower:
         self._load(state_dict)
 
     @classmethod
-    def from_text_model(cls, model, dtype=torch.float16, device='cuda'):
+    def from_text_model(cls, model, dtype=None, device='cuda'):
         """From a `transformers.CLIPTextModel`, `CLIPTextModelWithProjection` or `CLIPModel`: only its state dict (`text_model.*`,
-        `text_projection.weight`) and text configuration are read, no reference to the module is kept."""
+        `text_projection.weight`) and text configuration are read, no reference to the module is kept.  dtype None: the class's default
+        (float16; f16x3 for CLIPTextTowerX3)."""
+        dtype = cls.DEFAULT_DTYPE if dtype is None else dtype
         tc = getattr(model.config, 'text_config', None) or model.config
         full = model.state_dict()
         sd = {name: full[k] for k, name in text_keys(full).items()}
@@ -157,8 +182,9 @@ class CLIPTextTower:
                    eos_token_id=tc.eos_token_id, device=device, dtype=dtype)
 
     @classmethod
-    def from_pretrained(cls, path, dtype=torch.float16, device='cuda'):
+    def from_pretrained(cls, path, dtype=None, device='cuda'):
         """Reads a local directory of `config.json` + `model.safetensors` (read_text_tensors: the text tensors only)."""
+        dtype = cls.DEFAULT_DTYPE if dtype is None else dtype
         cfg, sd = read_text_tensors(path)
         cfg.pop('projection_dim')                     # the tensor's own shape decides
         return cls(sd, device=device, dtype=dtype, **cfg)
@@ -207,12 +233,27 @@ class CLIPTextTower:
         lens = mask_key_len(attention_mask, n, t)
         key_len = None if lens is None else lens.to(self.device)
         pos = pooled_positions(ids, self.eos)
+        if self.x3:
+            return self._forward_x3(ids, key_len, pos, n, t)
         h = ops.text_tokens(ids, self.tok, self.pos, self.dtype).view(n, t, 1, C)                  # checks 0 <= id < vocab on the host
         h = blocks.clip_encoder(h, self.layers, self.eps, self.act,
                                 lambda qkv: ops.attention_masked(qkv, self.heads, self.scale, causal=True, key_len=key_len))
         last = ops.layer_norm(h, *self.final_ln, eps=self.eps).view(n, t, C)                       # every token
         pooled = last[torch.arange(n, device=self.device), pos.to(self.device)].contiguous()
         embeds = None if self.w_proj is None else ops.linear(ops.cast_to_f32(pooled), self.w_proj)
+        self.rows += n
+        return TextOutput(last, pooled, embeds)
+
+    def _forward_x3(self, ids, key_len, pos, n, t):
+        """the same forward in the split-precision mode: float32 activations, X3Weight matrix products (ops.F16X3), the masked
+        split-precision attention between the qkv projection's and out_proj's operand images at every sequence length"""
+        C = self.hidden
+        h = ops.text_tokens_f32(ids, self.tok, self.pos).view(n, t, 1, C)                           # checks 0 <= id < vocab on the host
+        attend = lambda qkv: ops.attention_x3_masked(qkv, self.heads, self.scale, causal=True, key_len=key_len, split_out=True)
+        h = blocks.clip_encoder_x3(h, self.layers, self.eps, self.act, self.heads, self.scale, attend=attend)
+        last = ops.layer_norm_x3(h, *self.final_ln, eps=self.eps, want_f32=True, want_split=False).view(n, t, C)     # every token, float32
+        pooled = last[torch.arange(n, device=self.device), pos.to(self.device)].contiguous()
+        embeds = None if self.w_proj is None else ops.linear(pooled, self.w_proj)
         self.rows += n
         return TextOutput(last, pooled, embeds)
 
@@ -223,3 +264,13 @@ class CLIPTextTower:
         if self.w_proj is None:
             raise ValueError(f'CLIPTextTower: the state dict had no {PROJECTION!r} (a CLIPModel or CLIPTextModelWithProjection is needed)')
         return self(input_ids, attention_mask).text_embeds
+
+
+class CLIPTextTowerX3(CLIPTextTower):
+    """The parity-grade form of the tower: float32 activations and outputs, every matrix product in split precision (dtype ops.F16X3, its
+    only dtype), held to a small factor of the float32 transformers module's own rounding error against float64 -- use it where the
+    scorer's rewards must match the reference's.  Same constructor, state dict, from_text_model / from_pretrained as CLIPTextTower."""
+    SPLIT_PRECISION, DEFAULT_DTYPE = True, ops.F16X3
+
+    def __init__(self, state_dict, *args, dtype=ops.F16X3, **kw):
+        super().__init__(state_dict, *args, dtype=dtype, **kw)

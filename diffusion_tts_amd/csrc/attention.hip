@@ -447,8 +447,16 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
 //   P (f32 in [0,1] after exp2) * 2^14 -> ph, pl in registers;  O^T * 2^20 = Vh^T.ph + Vh^T.pl + Vl^T.ph,  l * 2^14 = ones.ph + ones.pl.
 // Structure, LDS rows (K' = Kh | Kl, V' = Vh | Vl: 256 B + 32 B pad), register prefetch, QT query tiles per wave and the transposed V
 // reads are attention16_kernel's; three MFMAs per fragment pair instead of one, and the fragment reads are what bounds it (QT = 2 halves them).
-template <int QT, int VAR = 7>
+// MASK (dts_attention_x3_masked; QT = 1): the causal and key-length mask of attention16_kernel's MASK form, by the same three rules -- a block
+// walks only the key tiles below min(kend, end of its query block) (a tile of nothing but -inf scores against a running maximum of -inf would
+// give NaN; every walked tile starts at a key that every query of the block sees, so the maximum is finite from tile 0 on), the select to
+// -inf takes the lane's own limit and is paid on the diagonal tile and on the tile that holds kend only, and a hidden key has P = 0 exactly:
+// ph = pl = 0, so it adds 0 * v to the numerator and 0 to the denominator.  Unlike there, the rows between kend and t are staged like any
+// other row (they are real, finite rows, not the zero rows past t; the buffer loads' range trick stays what it is) and removed by the select
+// alone.
+template <int QT, int VAR = 7, bool MASK = false>
 __global__ __launch_bounds__(256) void attention_x3_kernel(const AttP p) {
+  static_assert(!MASK || QT == 1, "masked form: one query tile per wave (every walked tile must start at a key the whole block sees)");
   using T = f16_t;
   // VAR (A/B aid, DTS_ATT_DB = 16 + VAR): bit 0 = K fragments of group j + 1 requested before the MFMAs of group j, bit 1 = both query tiles' maxima
   // exchanged in one round, bit 2 = the first V^T fragments requested before the softmax
@@ -489,7 +497,13 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const AttP p) {
 #pragma unroll
     for (int i = 0; i < DT; ++i) o[qt][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
-  const int ntiles = (p.t + 63) / 64;
+  // kend: the keys of this sample; lim: this lane's query sees keys < lim (>= 1); ntiles: the key tiles this block walks
+  int kend = p.t, lim = p.t, ntiles = (p.t + 63) / 64;
+  if constexpr (MASK) {
+    if (p.key_len) kend = min(p.t, max(1, p.key_len[n]));            // the caller vouches for 1 <= key_len <= t, clamped for memory safety only
+    lim = p.causal ? min(kend, q0 + lq + 1) : kend;
+    ntiles = ((p.causal ? min(kend, qblk * 64 + 64) : kend) + 63) / 64;
+  }
   uint4 pk[NCH], pv[NCH];
   // chunk c of a K' / V' row: c < 8 -> hi plane chunk c, else lo plane chunk c - 8.  Thread tid stages chunk c = tid & 15 of rows (tid >> 4) + 16 u.
   // Addressing (round 6): buffer loads -- the block's descriptor (scalar registers), per-lane 32-bit byte offsets that never change, and the
@@ -595,12 +609,15 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const AttP p) {
     float tmx[QT], t16[QT], t32[QT], t48[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-      if (key0 + 64 > p.t) {
+      // wave-uniform test: the ragged last tile; MASK: the tile that holds kend and (causal) the one that reaches past the wave's first query
+      bool edge = key0 + 64 > kend;
+      if constexpr (MASK) edge = edge || (p.causal && key0 + 63 > q0);
+      if (edge) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (key0 + j * 16 + lg * 4 + r >= p.t) sacc[qt][j][r] = -INFINITY;
+            if (key0 + j * 16 + lg * 4 + r >= lim) sacc[qt][j][r] = -INFINITY;
       }
       tmx[qt] = att_max16(sacc[qt]);
     }
@@ -896,6 +913,23 @@ extern "C" int dts_attention_x3(const void* qkv_split, void* out, int out_split3
   if (var == 0) return X3_LAUNCH(0);      // DTS_ATT_DB=16: without the three latency changes of round 6 (A/B aid, tools/att_bench.py --x3-kernel --variants 0)
   return X3_LAUNCH(7);
 #undef X3_LAUNCH
+}
+
+extern "C" int dts_attention_x3_masked(const void* qkv_split, void* out, int out_split3, int n, int t, int heads, int d, float scale, int causal,
+                                       const int32_t* key_len, dts_stream s) {
+  DTS_CHECK_ARG(qkv_split && out, "dts_attention_x3_masked: null pointer");
+  DTS_CHECK_ARG(n > 0 && t > 0 && heads > 0, "dts_attention_x3_masked: bad shape");
+  DTS_CHECK_ARG(scale > 0.f && scale <= 3.402823466e38f, "dts_attention_x3_masked: scale must be positive and finite");
+  DTS_CHECK_ARG(((uintptr_t)qkv_split | (uintptr_t)out) % 16 == 0 && (uintptr_t)key_len % 4 == 0, "dts_attention_x3_masked: pointers must be 16-byte aligned");
+  if (d != 64) {
+    dts_set_error("dts_attention_x3_masked: head dim %d unsupported (64, the head dim of every CLIP text width)", d);
+    return DTS_ERR_UNSUPPORTED;
+  }
+  // (dts_attention_x3's limit: 32-bit byte offsets inside one sample's rows)
+  DTS_CHECK_ARG((long long)t * 6 * heads * d * 2 < (1ll << 31), "dts_attention_x3_masked: %d tokens x %d heads exceed the 2 GiB a sample's rows may span", t, heads);
+  AttP p{(const char*)qkv_split, (char*)out, n, t, heads, d, scale * 1.4426950408889634f, 0, 1, out_split3 ? 1 : 0, key_len, causal ? 1 : 0};
+  const size_t lds = (size_t)2 * 64 * (2 * 64 * 2 + 32);
+  return launch_att(attention_x3_kernel<1, 7, true>, p, lds, to_stream(s), 64, 1, "dts_attention_x3_masked");
 }
 
 extern "C" int dts_attention_masked(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, int causal,

@@ -78,12 +78,12 @@ __global__ __launch_bounds__(256) void vit_tokens_kernel(const T* __restrict__ p
 
 // ------------------------------------------------------------------------------------------------
 // Text token assembly (CLIPTextEmbeddings.forward: token_embedding(input_ids) + position_embedding): out [n][t][c] = tok[ids[n][t]] + pos[t],
-// both tables f32, the sum formed in f32 and rounded once -- the text counterpart of vit_tokens_kernel.  One thread = one 16-byte vector;
-// c % 8 == 0.  An id outside [0, vocab) cannot be reported from here: it is clamped, for memory safety only (the caller checks the ids on
+// both tables f32, the sum formed in f32 and rounded once (the float32 form: one f32 add, unrounded) -- the text counterpart of
+// vit_tokens_kernel.  One thread = 8 channels, stored through the form Out (row_forms.h: Out16<T> or OutF32); c % 8 == 0.  An id outside [0, vocab) cannot be reported from here: it is clamped, for memory safety only (the caller checks the ids on
 // the host, ops.text_tokens).
-template <typename T>
+template <typename Out>
 __global__ __launch_bounds__(256) void text_tokens_kernel(const int32_t* __restrict__ ids, const float* __restrict__ tok,
-                                                           const float* __restrict__ pos, T* __restrict__ out, long long nvec, int t, int c, int vocab) {
+                                                           const float* __restrict__ pos, Out out, long long nvec, int t, int c, int vocab) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= nvec) return;
   const int vpr = c >> 3;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void text_tokens_kernel(const int32_t* __restr
   load8(pos + (long long)pt * c + 8 * v, b);
 #pragma unroll
   for (int e = 0; e < 8; ++e) y[e] = a[e] + b[e];
-  reinterpret_cast<uint4*>(out)[idx] = pack16<T>(y);
+  out.flat(idx, vpr, y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -154,6 +154,17 @@ int vit_tokens(const char* name, const T* patches, const float* cls, const float
   return DTS_OK;
 }
 
+template <typename Out>
+int text_tokens(const char* name, const int32_t* ids, const float* tok, const float* pos, Out out, int n, int t, int c, int vocab, dts_stream s) {
+  DTS_CHECK_ARG(n > 0 && t > 0 && vocab > 0 && c > 0 && c % 8 == 0, "%s: %d x %d tokens x %d channels (a multiple of 8), vocabulary %d", name, n, t, c, vocab);
+  DTS_CHECK_ARG(((uintptr_t)tok | (uintptr_t)pos | out.addr()) % 16 == 0 && (uintptr_t)ids % 4 == 0, "%s: pointers must be 16-byte aligned", name);
+  const long long nvec = (long long)n * t * (c / 8), grid = (nvec + 255) / 256;
+  DTS_CHECK_ARG(grid < (1ll << 31), "%s: grid too large", name);
+  hipLaunchKernelGGL(text_tokens_kernel<Out>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), ids, tok, pos, out, nvec, t, c, vocab);
+  DTS_CHECK_LAUNCH(name);
+  return DTS_OK;
+}
+
 // nvec vectors of 8 values, vpr of them per row (read by the image form alone)
 template <typename In, typename Out>
 int gelu(const char* name, const In* x, Out out, long long nvec, int vpr, int kind, dts_stream s) {
@@ -194,16 +205,12 @@ extern "C" int dts_vit_tokens_f32(const float* patches, const float* cls, const 
 extern "C" int dts_text_tokens(const int32_t* ids, const float* tok, const float* pos, void* out, int dtype, int n, int t, int c, int vocab,
                                dts_stream s) {
   DTS_CHECK_ARG(ids && tok && pos && out, "dts_text_tokens: null pointer");
-  DTS_DISPATCH_16BIT("dts_text_tokens", dtype, {
-    DTS_CHECK_ARG(n > 0 && t > 0 && vocab > 0 && c > 0 && c % 8 == 0, "dts_text_tokens: %d x %d tokens x %d channels (a multiple of 8), vocabulary %d",
-                  n, t, c, vocab);
-    DTS_CHECK_ARG(((uintptr_t)tok | (uintptr_t)pos | (uintptr_t)out) % 16 == 0 && (uintptr_t)ids % 4 == 0, "dts_text_tokens: pointers must be 16-byte aligned");
-    const long long nvec = (long long)n * t * (c / 8), grid = (nvec + 255) / 256;
-    DTS_CHECK_ARG(grid < (1ll << 31), "dts_text_tokens: grid too large");
-    hipLaunchKernelGGL(text_tokens_kernel<T>, dim3((unsigned)grid), dim3(256), 0, to_stream(s), ids, tok, pos, (T*)out, nvec, t, c, vocab);
-  });
-  DTS_CHECK_LAUNCH("dts_text_tokens");
-  return DTS_OK;
+  DTS_DISPATCH_16BIT("dts_text_tokens", dtype, return text_tokens("dts_text_tokens", ids, tok, pos, Out16<T>{(T*)out}, n, t, c, vocab, s));
+}
+
+extern "C" int dts_text_tokens_f32(const int32_t* ids, const float* tok, const float* pos, float* out, int n, int t, int c, int vocab, dts_stream s) {
+  DTS_CHECK_ARG(ids && tok && pos && out, "dts_text_tokens_f32: null pointer");
+  return text_tokens("dts_text_tokens_f32", ids, tok, pos, OutF32{out}, n, t, c, vocab, s);
 }
 
 extern "C" int dts_gelu(const void* x, void* out, int dtype, int64_t count, int kind, dts_stream s) {

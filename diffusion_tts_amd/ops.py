@@ -634,6 +634,30 @@ def attention_masked(qkv, heads, scale, causal=True, key_len=None):
     return out
 
 
+def attention_x3_masked(qkv, heads, scale, causal=True, key_len=None, split_out=False):
+    """attention_masked in the split-precision mode (dts_attention_x3_masked; head dim 64, any t >= 1): qkv float32 [n, t, 3*heads*64]
+    (split here by dts_split2_f16) or a SplitQKV (what conv2d(..., out_split2=True) wrote) -> float32 [n, t, heads*64], or with split_out the
+    operand image of the proj convolution (SplitAct [n, t, 1, C]).  causal / key_len as attention_masked: int32 [n] on the device with
+    1 <= key_len[b] <= t, vouched for by the caller.  Unlike attention(x3=True) no sequence length is routed to the float32 kernel."""
+    pre = isinstance(qkv, SplitQKV)
+    if not pre and not torch.is_tensor(qkv):
+        raise ValueError(f'attention_x3_masked: qkv must be a float32 tensor or a SplitQKV, got {type(qkv).__name__}')
+    if len(qkv.shape) != 3 or heads <= 0 or qkv.shape[-1] % (3 * heads):
+        raise ValueError(f'attention_x3_masked: qkv {tuple(qkv.shape)} is not [n, t, 3 * {heads} heads * d]')
+    if not pre and qkv.dtype != torch.float32:
+        raise ValueError(f'attention_x3_masked: qkv must be float32 (or a SplitQKV), got {qkv.dtype}: float16 / bfloat16 take attention_masked')
+    n, t, c3 = qkv.shape
+    c = c3 // 3
+    if key_len is not None and (not torch.is_tensor(key_len) or tuple(key_len.shape) != (n,) or key_len.dtype != torch.int32):
+        raise ValueError(f'attention_x3_masked: key_len {tuple(key_len.shape) if torch.is_tensor(key_len) else type(key_len).__name__} '
+                         f'{getattr(key_len, "dtype", "")} is not int32 [{n}]')
+    sp = qkv.data if pre else split2_f16(qkv)
+    out = torch.empty((n, t, 2 * c) if split_out else (n, t, c), dtype=torch.float16 if split_out else torch.float32, device=sp.device)
+    _call('dts_attention_x3_masked', _ptr(sp, 'qkv', torch.float16), _ptr(out), int(bool(split_out)), n, t, heads, c // heads, float(scale),
+          int(bool(causal)), _ptr(key_len, 'key_len', torch.int32))
+    return SplitAct(out.view(n, t, 1, 2 * c), c) if split_out else out
+
+
 def attention_x3_ok(t, d):
     """whether attention(..., x3=True) takes the split-precision kernel for this sequence length / head dim (so that the qkv projection may
     write its operand image directly and the proj convolution may read one)"""
@@ -751,27 +775,44 @@ def vit_tokens(patches, cls, pos):
     return out
 
 
+def _text_ids(who, ids, tok, pos):
+    """the host checks of text_tokens / text_tokens_f32 -> (int32 ids on the tables' device, n, t, c, vocab)"""
+    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.numel() == 0:
+        raise ValueError(f'{who}: ids must be an integer tensor [n, t], got {tuple(ids.shape) if torch.is_tensor(ids) else type(ids).__name__}'
+                         + (f' {ids.dtype}' if torch.is_tensor(ids) else ''))
+    n, t = ids.shape
+    if tok.dim() != 2 or pos.dim() != 2 or pos.shape[1] != tok.shape[1] or pos.shape[0] < t:
+        raise ValueError(f'{who}: tok {tuple(tok.shape)} / pos {tuple(pos.shape)} for ids {tuple(ids.shape)}')
+    vocab, c = tok.shape
+    host = ids.detach().cpu()
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 0 or hi >= vocab:
+        raise ValueError(f'{who}: token id {lo if lo < 0 else hi} is outside [0, {vocab}) (the rows of the token table)')
+    return host.to(torch.int32).to(tok.device).contiguous(), n, t, c, vocab
+
+
 def text_tokens(ids, tok, pos, dtype):
     """ids integer [n, t], tok float32 [vocab, c], pos float32 [>= t, c] (both on the device) -> [n, t, c] in float16 / bfloat16:
     tok[ids] + pos[:t], summed in float32 and rounded once (dts_text_tokens).  The kernel cannot report a bad id, so 0 <= id < vocab is
     checked HERE, on the host, before the upload: a ValueError names the offending value.  The ids come from the tokenizer as a host
     tensor; one that is already on the device is copied back for the check -- one synchronisation, acceptable where this runs (once per
     prompt)."""
-    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.numel() == 0:
-        raise ValueError(f'text_tokens: ids must be an integer tensor [n, t], got {tuple(ids.shape) if torch.is_tensor(ids) else type(ids).__name__}'
-                         + (f' {ids.dtype}' if torch.is_tensor(ids) else ''))
-    n, t = ids.shape
-    if tok.dim() != 2 or pos.dim() != 2 or pos.shape[1] != tok.shape[1] or pos.shape[0] < t:
-        raise ValueError(f'text_tokens: tok {tuple(tok.shape)} / pos {tuple(pos.shape)} for ids {tuple(ids.shape)}')
-    vocab, c = tok.shape
-    host = ids.detach().cpu()
-    lo, hi = int(host.min()), int(host.max())
-    if lo < 0 or hi >= vocab:
-        raise ValueError(f'text_tokens: token id {lo if lo < 0 else hi} is outside [0, {vocab}) (the rows of the token table)')
-    dev_ids = host.to(torch.int32).to(tok.device).contiguous()
+    dev_ids, n, t, c, vocab = _text_ids('text_tokens', ids, tok, pos)
     out = torch.empty((n, t, c), dtype=dtype, device=tok.device)
     _call('dts_text_tokens', _ptr(dev_ids, 'ids', torch.int32), _ptr(tok, 'tok', torch.float32), _ptr(pos, 'pos', torch.float32), _ptr(out),
           dt_code(dtype), n, t, c, vocab)
+    return out
+
+
+def text_tokens_f32(ids, tok, pos):
+    """text_tokens in float32 (dts_text_tokens_f32: one float32 add, nothing rounded to 16 bits) -> float32 [n, t, c]; the same host check
+    of 0 <= id < vocab before the upload; c a multiple of 8."""
+    dev_ids, n, t, c, vocab = _text_ids('text_tokens_f32', ids, tok, pos)
+    if c <= 0 or c % 8:
+        raise ValueError(f'text_tokens_f32: {c} channels (a multiple of 8)')
+    out = torch.empty((n, t, c), dtype=torch.float32, device=tok.device)
+    _call('dts_text_tokens_f32', _ptr(dev_ids, 'ids', torch.int32), _ptr(tok, 'tok', torch.float32), _ptr(pos, 'pos', torch.float32), _ptr(out),
+          n, t, c, vocab)
     return out
 
 

@@ -10,7 +10,8 @@
                        launch sequence per batch and one copy of n int32 back; the reward expression is the same host code.
   CLIPScorer           sd/scorers.py:149-213   -> HF CLIP image/text towers (third-party arithmetic, run as PyTorch-ROCm
                        modules on the GPU) + dts_cosine_rows (HIP) for the normalise-and-dot tail; with vision_tower='hip' the
-                       image tower is clip_vision.CLIPVisionTower on the HIP kernels (16-bit; the text tower stays transformers).  The reference fetches
+                       image tower is clip_vision.CLIPVisionTower[X3] and with text_tower='hip' the text tower clip_text.CLIPTextTower[X3]
+                       on the HIP kernels (16-bit throughput modes, or 'f16x3': both towers at the reference's float32 precision).  The reference fetches
                        `openai/clip-vit-large-patch14`; there is no network here, so the model / image processor / tokenizer
                        can be injected (random-init `CLIPModel(CLIPConfig)` for BASELINE config 4).
 """
@@ -218,7 +219,7 @@ class CLIPScorer(Scorer):
 
     def __init__(self, model_id='openai/clip-vit-large-patch14', dtype=torch.float32, model=None, image_processor=None,
                  tokenizer=None, processor=None, device='cuda', device_preprocess=True, vision_tower='transformers',
-                 tower_dtype=torch.float16, text_tower='transformers'):
+                 tower_dtype=torch.float16, text_tower='transformers', text_tower_dtype=None):
         """vision_tower: 'transformers' (default: `model.get_image_features`, the reference's arithmetic in the model's own precision) |
         'hip' (clip_vision.CLIPVisionTower built from `model`: the image tower on this build's kernels with `tower_dtype` = float16 /
         bfloat16 activations -- a 16-bit THROUGHPUT mode of the scorer, where the reference scores in float32 -- or ops.F16X3, the
@@ -226,7 +227,13 @@ class CLIPScorer(Scorer):
         name, there is no fallback).  The text branch, its cache and the pre-processing are the same either way.
         text_tower: 'transformers' (default: `model.get_text_features`) | 'hip' (clip_text.CLIPTextTower built from `model`, `tower_dtype`
         activations: the prompt's embedding from this build's kernels -- an opt-in 16-bit mode like vision_tower='hip'; the reference embeds
-        the text in float32; it has no split-precision form, so tower_dtype=ops.F16X3 with text_tower='hip' is refused).  The text-embedding cache and the cosine tail are unchanged.
+        the text in float32).  The text-embedding cache and the cosine tail are unchanged.
+        text_tower_dtype: the dtype of text_tower='hip'.  None (default): the text tower borrows `tower_dtype`, which selects a 16-bit
+        clip_text.CLIPTextTower only -- tower_dtype=ops.F16X3 with text_tower='hip' and no text_tower_dtype stays refused, since tower_dtype
+        alone never picked a text tower of another class.  torch.float16 / torch.bfloat16: the 16-bit text tower whatever the image tower's
+        dtype is; ops.F16X3: clip_text.CLIPTextTowerX3, the parity-grade text tower (float32 activations, split-precision matrix products,
+        the masked split-precision attention).  Both towers at the reference's precision on this build's kernels:
+        CLIPScorer(vision_tower='hip', text_tower='hip', tower_dtype='f16x3', text_tower_dtype='f16x3').
         device_preprocess: run the image processor's resize / rescale / normalise on the GPU (clip_preprocess.DevicePreprocessor:
         Pillow's integer bicubic + the processor's own value table, identical pixel_values) whenever the images are square uint8 GPU
         tensors and the processor has the stock configuration; False keeps the reference's host path (images.cpu() + PIL) always."""
@@ -257,9 +264,14 @@ class CLIPScorer(Scorer):
                 tokenizer = ByteTokenizer(tc.vocab_size)
         if vision_tower not in ('transformers', 'hip'):
             raise ValueError(f"CLIPScorer: vision_tower must be 'transformers' or 'hip', got {vision_tower!r}")
-        if text_tower == 'hip' and isinstance(tower_dtype, str) and tower_dtype == ops.F16X3:
-            raise ValueError("CLIPScorer: text_tower='hip' with tower_dtype='f16x3': the text tower has no split-precision form (it would "
-                             "need a masked split-precision attention); keep text_tower='transformers', which embeds the prompt in float32")
+        text_x3 = isinstance(text_tower_dtype, str) and text_tower_dtype == ops.F16X3
+        if text_tower_dtype is not None and not text_x3 and text_tower_dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"CLIPScorer: text_tower_dtype must be None (follow tower_dtype), torch.float16, torch.bfloat16 or 'f16x3', "
+                             f"got {text_tower_dtype!r}")
+        if text_tower == 'hip' and text_tower_dtype is None and isinstance(tower_dtype, str) and tower_dtype == ops.F16X3:
+            raise ValueError("CLIPScorer: text_tower='hip' with tower_dtype='f16x3': the text tower that borrows tower_dtype, "
+                             "clip_text.CLIPTextTower, has no split-precision form; pass text_tower_dtype='f16x3' for "
+                             "clip_text.CLIPTextTowerX3, or keep text_tower='transformers', which embeds the prompt in float32")
         self.clip = model.to(self.device).eval()
         self.vision_tower, self._tower = vision_tower, None
         if vision_tower == 'hip':
@@ -270,8 +282,9 @@ class CLIPScorer(Scorer):
             raise ValueError(f"CLIPScorer: text_tower must be 'transformers' or 'hip', got {text_tower!r}")
         self.text_tower, self._text_tower = text_tower, None
         if text_tower == 'hip':
-            from .clip_text import CLIPTextTower
-            self._text_tower = CLIPTextTower.from_text_model(self.clip, dtype=tower_dtype, device=self.device)
+            from .clip_text import CLIPTextTower, CLIPTextTowerX3
+            self._text_tower = (CLIPTextTowerX3 if text_x3 else CLIPTextTower).from_text_model(
+                self.clip, dtype=tower_dtype if text_tower_dtype is None else text_tower_dtype, device=self.device)
         self.image_processor, self.tokenizer = image_processor, tokenizer
         self._text_cache = {}
         self.device_preprocessed = 0                                   # images whose pixel_values were built on the GPU
@@ -311,7 +324,7 @@ class CLIPScorer(Scorer):
         if txt_emb is None:
             enc = self.tokenizer(prompts, padding=True, truncation=True, max_length=77, return_tensors='pt').to(dev)
             if self._text_tower is not None:
-                txt_emb = self._text_tower.get_text_features(**enc).contiguous()     # f32 [n, projection_dim] from 16-bit activations
+                txt_emb = self._text_tower.get_text_features(**enc).contiguous()     # f32 [n, projection_dim] (activations in the text tower's dtype)
             else:
                 txt_emb = _features(self.clip.get_text_features(**enc)).float().contiguous()
             if len(self._text_cache) < 64:

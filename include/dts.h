@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 121        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 122        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -57,7 +57,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      118: dts_layer_norm_x3, dts_gelu_x3, dts_patchify_x3, dts_vit_tokens_f32, dts_vit_head_f32 (the CLIP vision tower in DTS_F16X3);
                                      119: dts_conv_plan (the whole launch plan of a dts_conv2d call, as a query);
                                      120: dts_conv_args.up == 2 (phase-packed weights), dts_conv_takes_phases, dts_conv_plan_info.phases;
-                                     121: dts_precond_in (the VP, VE and iDDPM preconditioners)) */
+                                     121: dts_precond_in (the VP, VE and iDDPM preconditioners);
+                                     122: dts_attention_x3_masked, dts_text_tokens_f32 (the CLIP text tower in DTS_F16X3)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -232,6 +233,15 @@ int dts_attention_x3(const void* qkv_split, void* out, int out_split3, int n, in
  * the output.  Key tiles wholly above a query block's diagonal or wholly past key_len are skipped, not computed and masked. */
 int dts_attention_masked(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, int causal,
                          const int32_t* key_len, dts_stream s);
+/* dts_attention_masked in the split-precision mode (the CLIP text tower in DTS_F16X3): dts_attention_x3's operand (qkv_split) and output
+ * forms (f32 rows, or with out_split3 = 1 the proj convolution's operand image), its arithmetic and its 2 GiB limit on a sample's rows;
+ * dts_attention_masked's mask, causal / key_len contract and refusals (d = 64 only, scale positive and finite, tensors 16-byte and key_len
+ * 4-byte aligned); any t >= 1; causal = 0 with key_len = NULL is plain attention, bit for bit dts_attention_x3's one-query-tile form.  The
+ * mask is a select to -inf on the f32 scores: a hidden key has P = 0 exactly, so both halves of its split are 0 and finite k / v values
+ * there (|x| < 1023, the image's range) cannot change a bit of the output.  Rows between key_len and t are read like any other; key tiles
+ * wholly above a query block's diagonal or wholly past key_len are skipped, not computed and masked. */
+int dts_attention_x3_masked(const void* qkv_split, void* out, int out_split3, int n, int t, int heads, int d, float scale, int causal,
+                            const int32_t* key_len, dts_stream s);
 
 /* ---- K15-K17: the SD U-Net's transformer blocks (diffusers BasicTransformerBlock: attention.py, attention_processor.py) ---- */
 /* Attention of tq queries over a SHORT foreign sequence (the text tokens): q [n][tq][heads*d], kv [kv_n][tk][2*heads*d] laid out
@@ -307,6 +317,9 @@ int dts_vit_tokens_f32(const float* patches, const float* cls, const float* pos,
 /* dts_vit_head over f32 tokens [n][t][c] (post_layernorm of the class token): out f32 [n][c] = LayerNorm(tokens[n][0][:]) * gamma + beta with
  * dts_layer_norm_x3's arithmetic, one wave per sample; the other tokens are never read.  c % 8 == 0, c <= 2048.  dts_linear follows. */
 int dts_vit_head_f32(const float* tokens, float* out, int n, int t, int c, float eps, const float* gamma, const float* beta, dts_stream s);
+/* dts_text_tokens in f32 (the text tower's counterpart of dts_vit_tokens_f32): out f32 [n][t][c] = tok[ids[n][t]][:] + pos[t][:], one f32 add
+ * per element; ids as there (checked on the host, clamped here for memory safety only).  c % 8 == 0. */
+int dts_text_tokens_f32(const int32_t* ids, const float* tok, const float* pos, float* out, int n, int t, int c, int vocab, dts_stream s);
 
 /* ---- K7/K8: embedding MLP pieces and EDM preconditioning (networks.py:200-206,437-447,654-668) ---- */
 /* y[m][n] = act_out( act_in(x[m][:]) . w[n][:] + bias[n] (+ y[m][n] if accumulate) ); all f32; act: 0 none, 1 SiLU */

@@ -26,6 +26,11 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
     --clip-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel image tower, float32 like the reference) | hip
                   (clip_vision.CLIPVisionTower on this build's kernels; no fallback).  --clip-tower-dtype f16 (default) | bf16: 16-bit
                   throughput modes of the scorer | f16x3: the parity-grade mode (float32 activations, split-precision matrix products)
+    --clip-text-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel text tower, float32 like the reference) | hip
+                  (clip_text.CLIPTextTower on this build's kernels; no fallback).  --clip-text-tower-dtype f16 | bf16 | f16x3 (default: follow
+                  --clip-tower-dtype; f16x3 must be asked for here: clip_text.CLIPTextTowerX3, the parity-grade text tower).  Both towers at
+                  the reference's precision: --clip-tower hip --clip-tower-dtype f16x3 --clip-text-tower hip --clip-text-tower-dtype f16x3
+                  (--text-encoder hip, the SD text encoder, stays float16: the reference runs SD in float16)
     --jpeg-codec: --scorer compressibility: pil (default: the reference's host encode per image) | hip (the same byte count computed on the
                   GPU, identical rewards; image sides must be multiples of 16; no fallback)
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
@@ -48,10 +53,11 @@ CLIP_TOWER_DTYPES = {'f16': torch.float16, 'bf16': torch.bfloat16, 'f16x3': 'f16
 
 
 def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='transformers', clip_model=None, jpeg_codec='pil',
-               clip_tower_dtype='f16'):
+               clip_tower_dtype='f16', clip_text_tower='transformers', clip_text_tower_dtype=None):
     """main.py:60-71 of the reference.  compute_dtype: the search's --dtype; the ImageNet classifier runs in the search's own mode for the two parity
     modes (float32, f16x3) and in float16 otherwise (also beside a bfloat16 denoiser: scorers.ImageNetScorer).  clip_tower: --clip-tower,
-    clip_tower_dtype: --clip-tower-dtype (the activations of the 'hip' tower); clip_model: a transformers.CLIPModel to score with instead of the cached checkpoint (scorers.CLIPScorer model=).  jpeg_codec: --jpeg-codec."""
+    clip_tower_dtype: --clip-tower-dtype (the activations of the 'hip' tower); clip_model: a transformers.CLIPModel to score with instead of the cached checkpoint (scorers.CLIPScorer model=).  jpeg_codec: --jpeg-codec.
+    clip_text_tower: --clip-text-tower, clip_text_tower_dtype: --clip-text-tower-dtype (None: the text tower follows clip_tower_dtype)."""
     from diffusion_tts_amd import scorers as S
     if scorer_name == 'brightness':
         return S.BrightnessScorer(dtype=torch.float32)
@@ -61,7 +67,9 @@ def get_scorer(backend, scorer_name, device, compute_dtype=None, clip_tower='tra
         return S.ImageNetScorer(dtype=torch.float32, device=device, compute_dtype=compute_dtype if compute_dtype in (torch.float32, 'f16x3') else torch.float16)
     if scorer_name == 'clip' and backend == 'sd':
         return S.CLIPScorer(dtype=torch.float32, device=device, model=clip_model, vision_tower=clip_tower,
-                            tower_dtype=CLIP_TOWER_DTYPES[clip_tower_dtype])    # local HF cache only; raises with instructions otherwise
+                            tower_dtype=CLIP_TOWER_DTYPES[clip_tower_dtype], text_tower=clip_text_tower,
+                            text_tower_dtype=None if clip_text_tower_dtype is None else CLIP_TOWER_DTYPES[clip_text_tower_dtype])
+                            # (local HF cache only; raises with instructions otherwise)
     raise ValueError(f"Unknown or invalid scorer '{scorer_name}' for backend '{backend}'")
 
 
@@ -159,7 +167,9 @@ def main_sd(args):
     te = load_sd_text_encoder(model_id, dev, te_kind)
 
     scorer = get_scorer('sd', args.scorer, dev, clip_tower=getattr(args, 'clip_tower', 'transformers'),
-                        jpeg_codec=getattr(args, 'jpeg_codec', 'pil'), clip_tower_dtype=getattr(args, 'clip_tower_dtype', 'f16'))
+                        jpeg_codec=getattr(args, 'jpeg_codec', 'pil'), clip_tower_dtype=getattr(args, 'clip_tower_dtype', 'f16'),
+                        clip_text_tower=getattr(args, 'clip_text_tower', 'transformers'),
+                        clip_text_tower_dtype=getattr(args, 'clip_text_tower_dtype', None))
     pipe = SDSearchPipeline(unet, vae, device=dev, text_encoder=te, tokenizer=tok)     # encodes the prompt itself (pipeline...:976-992)
     params = {'N': args.N, 'lambda': args.lambda_, 'eps': args.eps, 'K': args.K, 'B': args.B, 'S': args.S}
     torch.manual_seed(args.seed)                                                       # same host RNG stream on every rank
@@ -215,6 +225,13 @@ def build_parser():
     parser.add_argument('--clip-tower-dtype', dest='clip_tower_dtype', type=str, default='f16', choices=['f16', 'bf16', 'f16x3'],
                         help="--clip-tower hip: the tower's activations.  f16 (default) / bf16: the 16-bit throughput modes; f16x3: the parity-grade "
                              "mode (float32 activations, split-precision matrix products: the float32 module's rewards to its own rounding error)")
+    parser.add_argument('--clip-text-tower', dest='clip_text_tower', type=str, default='transformers', choices=['transformers', 'hip'],
+                        help="SD backend, --scorer clip: 'hip' = the CLIP text tower on this build's kernels (an error if the kernels do not take the "
+                             "model's shape), 'transformers' = the stock module, float32 like the reference")
+    parser.add_argument('--clip-text-tower-dtype', dest='clip_text_tower_dtype', type=str, default=None, choices=['f16', 'bf16', 'f16x3'],
+                        help="--clip-text-tower hip: the text tower's activations.  Default: follow --clip-tower-dtype (which selects a 16-bit text "
+                             "tower only).  f16x3: the parity-grade text tower (float32 activations, split-precision matrix products, masked "
+                             "split-precision attention)")
     parser.add_argument('--jpeg-codec', dest='jpeg_codec', type=str, default='pil', choices=['pil', 'hip'],
                         help="--scorer compressibility: 'hip' = the JPEG byte length computed on the GPU (identical rewards; image sides must be "
                              "multiples of 16, an error otherwise), 'pil' = the reference's host encode of every image")
