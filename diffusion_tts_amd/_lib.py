@@ -81,6 +81,9 @@ SIGNATURES = {
     'dts_heun_xhat': [_p, _i, _i, _p, _i, _d, _p, _i, _i, _p],
     'dts_heun_euler': [_p, _p, _d, _d, _p, _p, _i64, _p],
     'dts_heun_correct': [_p, _p, _p, _d, _d, _p, _i64, _p],
+    'dts_ode_xhat': [_p, _p, _i, _d, _d, _d, _p, _p, _i64, _p],
+    'dts_ode_slope': [_p, _p, _d, _d, _p, _d, _d, _p, _p, _p, _i64, _p],
+    'dts_ode_correct': [_p, _p, _p, _p, _d, _d, _d, _d, _d, _p, _i64, _p],
     'dts_quantize_u8': [_p, _i, _p, _i64, _p],
     'dts_brightness': [_p, _p, _i, _i, _p],
     'dts_u8_to_unit_f32': [_p, _p, _i64, _p],
@@ -100,7 +103,7 @@ OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 122              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 123              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

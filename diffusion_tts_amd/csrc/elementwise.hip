@@ -219,6 +219,41 @@ __global__ void heun_correct_kernel(const double* __restrict__ x_hat, const floa
   }
 }
 
+// ---- K9b: the general ODE step, fp64 state (edm/generate.py:156-174) -----------------------------------
+// The scaled, time-reparametrised ODE dx/dt = a(t) x - b(t) D(x / s(t); sigma(t)): every scalar is evaluated once per step on the host.
+// x_in = x / s is the denoiser's input: a true division, as the reference's.  Optional outputs are null pointers.
+template <typename E>
+__global__ void ode_xhat_kernel(const double* __restrict__ x_cur, const E* __restrict__ eps, double ratio, double coef, double s_hat,
+                                double* __restrict__ x_hat, double* __restrict__ x_in, long long count) {
+  GSL(i, count) {
+    double v = ratio * x_cur[i];
+    if (eps) v = v + coef * (double)eps[i];
+    x_hat[i] = v;
+    if (x_in) x_in[i] = v / s_hat;
+  }
+}
+// x and base may be the same array (they are in both of the sampler's uses): neither is written
+__global__ void ode_slope_kernel(const double* x, const float* __restrict__ D, double a, double b, const double* base, double step,
+                                 double s_out, double* __restrict__ d_out, double* __restrict__ x_out, double* __restrict__ x_in,
+                                 long long count) {
+  GSL(i, count) {
+    const double d = a * x[i] - b * (double)D[i];
+    const double v = base[i] + step * d;
+    if (d_out) d_out[i] = d;
+    x_out[i] = v;
+    if (x_in) x_in[i] = v / s_out;
+  }
+}
+// x_next may be x_prime's array (element i is read before it is written)
+__global__ void ode_correct_kernel(const double* __restrict__ x_hat, const double* x_prime, const float* __restrict__ D2,
+                                   const double* __restrict__ d_cur, double a, double b, double h, double w0, double w1, double* x_next,
+                                   long long count) {
+  GSL(i, count) {
+    const double dp = a * x_prime[i] - b * (double)D2[i];
+    x_next[i] = x_hat[i] + h * (w0 * d_cur[i] + w1 * dp);
+  }
+}
+
 // ---- K10/K11 -----------------------------------------------------------------------------------------
 // The reference's `(x * 127.5 + 128).clip(0, 255).to(torch.uint8)` is two tensor operations: the product is rounded, then the sum.  A
 // fused multiply-add rounds once and lands on the other side of an integer for about two values in a million (one pixel level off), so
@@ -774,6 +809,49 @@ extern "C" int dts_heun_correct(const double* x_hat, const float* D2, const doub
   hipLaunchKernelGGL(heun_correct_kernel, dim3(grid1d(count)), dim3(256), 0, st, x_hat, D2, d_cur, t_hat, t_next, x_next,
                      (long long)count);
   DTS_CHECK_LAUNCH("dts_heun_correct");
+  return DTS_OK;
+}
+
+static inline bool fin(double v) { return v - v == 0.0; }            // neither infinite nor NaN
+
+extern "C" int dts_ode_xhat(const double* x_cur, const void* eps, int eps_f32, double ratio, double noise_coef, double s_hat,
+                            double* x_hat, double* x_in, int64_t count, dts_stream s) {
+  DTS_CHECK_ARG(x_cur && x_hat && count > 0, "dts_ode_xhat: bad args");
+  DTS_CHECK_ARG(fin(ratio) && fin(noise_coef) && fin(s_hat), "dts_ode_xhat: ratio=%g noise_coef=%g s_hat=%g", ratio, noise_coef, s_hat);
+  DTS_CHECK_ARG((eps != nullptr) == (noise_coef != 0.0), "dts_ode_xhat: eps is NULL exactly when noise_coef == 0 (noise_coef=%g)", noise_coef);
+  DTS_CHECK_ARG(!x_in || s_hat != 0.0, "dts_ode_xhat: x_in with s_hat == 0");
+  ST;
+  const int g = grid1d(count);
+  if (eps_f32)
+    hipLaunchKernelGGL((ode_xhat_kernel<float>), dim3(g), dim3(256), 0, st, x_cur, (const float*)eps, ratio, noise_coef, s_hat, x_hat,
+                       x_in, (long long)count);
+  else
+    hipLaunchKernelGGL((ode_xhat_kernel<double>), dim3(g), dim3(256), 0, st, x_cur, (const double*)eps, ratio, noise_coef, s_hat, x_hat,
+                       x_in, (long long)count);
+  DTS_CHECK_LAUNCH("dts_ode_xhat");
+  return DTS_OK;
+}
+extern "C" int dts_ode_slope(const double* x, const float* D, double a, double b, const double* base, double step, double s_out,
+                             double* d, double* x_out, double* x_in, int64_t count, dts_stream s) {
+  DTS_CHECK_ARG(x && D && base && x_out && count > 0, "dts_ode_slope: bad args");
+  DTS_CHECK_ARG(x_out != x && x_out != base, "dts_ode_slope: x_out must not be x or base");
+  DTS_CHECK_ARG(fin(a) && fin(b) && fin(step) && fin(s_out), "dts_ode_slope: a=%g b=%g step=%g s_out=%g", a, b, step, s_out);
+  DTS_CHECK_ARG(!x_in || s_out != 0.0, "dts_ode_slope: x_in with s_out == 0");
+  ST;
+  hipLaunchKernelGGL(ode_slope_kernel, dim3(grid1d(count)), dim3(256), 0, st, x, D, a, b, base, step, s_out, d, x_out, x_in,
+                     (long long)count);
+  DTS_CHECK_LAUNCH("dts_ode_slope");
+  return DTS_OK;
+}
+extern "C" int dts_ode_correct(const double* x_hat, const double* x_prime, const float* D2, const double* d_cur, double a, double b,
+                               double h, double w0, double w1, double* x_next, int64_t count, dts_stream s) {
+  DTS_CHECK_ARG(x_hat && x_prime && D2 && d_cur && x_next && count > 0, "dts_ode_correct: bad args");
+  DTS_CHECK_ARG(x_next != x_hat && x_next != d_cur, "dts_ode_correct: x_next must not be x_hat or d_cur");
+  DTS_CHECK_ARG(fin(a) && fin(b) && fin(h) && fin(w0) && fin(w1), "dts_ode_correct: a=%g b=%g h=%g w0=%g w1=%g", a, b, h, w0, w1);
+  ST;
+  hipLaunchKernelGGL(ode_correct_kernel, dim3(grid1d(count)), dim3(256), 0, st, x_hat, x_prime, D2, d_cur, a, b, h, w0, w1, x_next,
+                     (long long)count);
+  DTS_CHECK_LAUNCH("dts_ode_correct");
   return DTS_OK;
 }
 

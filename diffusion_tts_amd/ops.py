@@ -1063,6 +1063,48 @@ def heun_correct(x_hat, D2, d_cur, t_hat, t_next, x_next):
     return x_next
 
 
+# ---- the general ODE step (ablation sampler, edm/generate.py:156-174) ---------------------------
+def ode_xhat(x_cur, eps, ratio, noise_coef, s_hat=1.0):
+    """x_hat = ratio * x_cur + noise_coef * eps (eps float64 | float32; None exactly when noise_coef == 0: no noise is read).
+    Returns (x_hat, x_in): x_in = x_hat / s_hat, the denoiser's input -- x_hat itself when s_hat == 1."""
+    if (eps is None) != (float(noise_coef) == 0.0):
+        raise ValueError(f'ode_xhat: eps is None exactly when noise_coef == 0 (noise_coef = {float(noise_coef)!r})')
+    if eps is not None:
+        if eps.dtype not in (torch.float64, torch.float32):
+            raise ValueError('eps must be float64 or float32')
+        if eps.shape != x_cur.shape:
+            raise ValueError(f'eps has shape {tuple(eps.shape)}, x_cur {tuple(x_cur.shape)}')
+    x_hat = torch.empty_like(x_cur)
+    x_in = torch.empty_like(x_cur) if float(s_hat) != 1.0 else None
+    _call('dts_ode_xhat', _ptr(x_cur, 'x_cur', torch.float64), _ptr(eps, 'eps'), int(eps is not None and eps.dtype == torch.float32),
+          float(ratio), float(noise_coef), float(s_hat), _ptr(x_hat), _ptr(x_in), x_cur.numel())
+    return x_hat, (x_hat if x_in is None else x_in)
+
+
+def ode_slope(x, D, a, b, step, s_out=1.0, base=None, want_d=True):
+    """d = a * x - b * D; x_out = base + step * d (base = x unless given).  Returns (d or None, x_out, x_in): x_in = x_out / s_out, the
+    denoiser's next input -- x_out itself when s_out == 1."""
+    base = x if base is None else base
+    if D.shape != x.shape or base.shape != x.shape:
+        raise ValueError(f'ode_slope: x {tuple(x.shape)}, D {tuple(D.shape)}, base {tuple(base.shape)}')
+    d = torch.empty_like(x) if want_d else None
+    x_out = torch.empty_like(x)
+    x_in = torch.empty_like(x) if float(s_out) != 1.0 else None
+    _call('dts_ode_slope', _ptr(x, 'x', torch.float64), _ptr(D, 'D', torch.float32), float(a), float(b), _ptr(base, 'base', torch.float64),
+          float(step), float(s_out), _ptr(d), _ptr(x_out), _ptr(x_in), x.numel())
+    return d, x_out, (x_out if x_in is None else x_in)
+
+
+def ode_correct(x_hat, x_prime, D2, d_cur, a, b, h, w0, w1):
+    """x_next = x_hat + h * (w0 * d_cur + w1 * (a * x_prime - b * D2))"""
+    if not (x_prime.shape == D2.shape == d_cur.shape == x_hat.shape):
+        raise ValueError('ode_correct: shapes differ')
+    x_next = torch.empty_like(x_hat)
+    _call('dts_ode_correct', _ptr(x_hat, 'x_hat', torch.float64), _ptr(x_prime, 'x_prime', torch.float64), _ptr(D2, 'D2', torch.float32),
+          _ptr(d_cur, 'd_cur', torch.float64), float(a), float(b), float(h), float(w0), float(w1), _ptr(x_next), x_hat.numel())
+    return x_next
+
+
 # ---- scorer plumbing ----------------------------------------------------------------------------
 def quantize_u8(x, f32_math=False):
     """(x*127.5+128).clip(0,255) truncated to uint8; f64 arithmetic (EDM loop) unless f32_math (SD loop, f32 input)."""

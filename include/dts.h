@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 122        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 123        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -58,7 +58,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      119: dts_conv_plan (the whole launch plan of a dts_conv2d call, as a query);
                                      120: dts_conv_args.up == 2 (phase-packed weights), dts_conv_takes_phases, dts_conv_plan_info.phases;
                                      121: dts_precond_in (the VP, VE and iDDPM preconditioners);
-                                     122: dts_attention_x3_masked, dts_text_tokens_f32 (the CLIP text tower in DTS_F16X3)) */
+                                     122: dts_attention_x3_masked, dts_text_tokens_f32 (the CLIP text tower in DTS_F16X3);
+                                     123: dts_ode_xhat, dts_ode_slope, dts_ode_correct (the general ODE step of the ablation sampler)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -368,6 +369,22 @@ int dts_heun_euler(const double* x_hat, const float* D, double t_hat, double t_n
 /* x_next = x_hat + (t_next - t_hat)*(0.5*d_cur + 0.5*(x_next - D2)/t_next)   (in place on x_next) */
 int dts_heun_correct(const double* x_hat, const float* D2, const double* d_cur, double t_hat, double t_next,
                      double* x_next, int64_t count, dts_stream s);
+
+/* ---- K9b: the general ODE step of the ablation sampler, fp64 state (edm/generate.py:156-174) -------
+ * dx/dt = a(t) x - b(t) D(x / s(t); sigma(t)) with a = sigma'/sigma + s'/s and b = sigma' s / sigma.  Every scalar is evaluated once per
+ * step on the host and must be finite; D is the denoiser's f32 output; the arrays hold `count` elements, row for row (no broadcast).
+ * Optional outputs may be NULL.  x_in = (the state just written) / s is the denoiser's next input: a true division. */
+/* x_hat = ratio * x_cur + noise_coef * eps;  x_in (optional) = x_hat / s_hat.  eps is f64 (eps_f32=0) or f32; eps == NULL is legal
+ * exactly when noise_coef == 0 (no noise is read). */
+int dts_ode_xhat(const double* x_cur, const void* eps, int eps_f32, double ratio, double noise_coef, double s_hat,
+                 double* x_hat, double* x_in, int64_t count, dts_stream s);
+/* d (optional) = a * x - b * D;  x_out = base + step * d;  x_in (optional) = x_out / s_out.  x and base may be the same array; x_out is
+ * neither.  step = h: the Euler step; step = alpha * h: the Heun predictor x_prime. */
+int dts_ode_slope(const double* x, const float* D, double a, double b, const double* base, double step, double s_out,
+                  double* d, double* x_out, double* x_in, int64_t count, dts_stream s);
+/* x_next = x_hat + h * (w0 * d_cur + w1 * (a * x_prime - b * D2));  w0 = 1 - 1/(2 alpha), w1 = 1/(2 alpha).  x_next may be x_prime. */
+int dts_ode_correct(const double* x_hat, const double* x_prime, const float* D2, const double* d_cur, double a, double b,
+                    double h, double w0, double w1, double* x_next, int64_t count, dts_stream s);
 
 /* ---- K10/K11: scorer pre-processing and brightness reward (edm/main.py:126; scorers.py:38-52) ----- */
 /* u8 = trunc(clip(x*127.5+128, 0, 255)); x is f64 (is_f32=0) or f32 (1): arithmetic in f64 as the EDM loop's (.to(float64) first);
