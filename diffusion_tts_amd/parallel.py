@@ -6,7 +6,9 @@ sharding the N candidates of one search iteration is this build's addition (SURV
   - every rank replays the same host RNG stream, so noise is never communicated;
   - the only data-path collective is ONE all-gather of the per-candidate rewards (N*B floats, <= 1 KB) per
     search iteration; every rank then takes the same first-max argmax, so the survivor is known everywhere
-    from its index alone and is rebuilt locally from the replicated host noise.
+    from its index alone and is rebuilt locally from the replicated host noise;
+  - the EDM beam search (sampler._beam_search) shards the N candidates of EVERY beam and adds one exchange of the S*B survivor
+    rows per sigma step (exchange_rows): a survivor is a Heun step's output, which only its owner computed.
 """
 import os
 from typing import Tuple
@@ -102,11 +104,43 @@ class CandidateShards:
             parts.append(recv[r * cap:r * cap + (hi - lo) * rows_per_candidate])
         return torch.cat(parts)
 
+    def owner(self, candidate: int, n_candidates: int) -> int:
+        """The (group) rank whose span holds `candidate`."""
+        return next(r for r in range(self.world) if self.span(n_candidates, r)[0] <= candidate < self.span(n_candidates, r)[1])
+
+    def exchange_rows(self, local: torch.Tensor, owners) -> torch.Tensor:
+        """The EDM beam search's survivors: row i of `local` [R, ...] is valid on rank owners[i] (replicated list) and anything of the
+        right shape elsewhere.  Returns the R valid rows, identical on every rank, in ONE all-gather per call: every rank sends the rows
+        it owns (padded to the largest share) and copies each row out of its owner's slab, so a row arrives bit for bit (a sum over
+        ranks would turn -0.0 into +0.0)."""
+        if self.solo:
+            return local
+        owners = [int(o) for o in owners]
+        if len(owners) != local.shape[0] or any(not 0 <= o < self.world for o in owners):
+            raise ValueError(f'exchange_rows: {local.shape[0]} rows need as many owners in [0, {self.world}), got {owners}')
+        held = [[i for i, o in enumerate(owners) if o == r] for r in range(self.world)]
+        cap = max(len(h) for h in held)
+        if local.is_cuda:
+            dev = local.device if self.dev_direct else torch.device('cpu')
+        else:
+            dev = local.device if self.host_direct else self._device()
+        send = torch.zeros((cap,) + tuple(local.shape[1:]), dtype=local.dtype, device=dev)
+        if held[self.rank]:
+            send[:len(held[self.rank])] = local[held[self.rank]].to(dev)
+        recv = torch.empty((cap * self.world,) + tuple(local.shape[1:]), dtype=local.dtype, device=dev)
+        dist.all_gather_into_tensor(recv, send, group=self.group)
+        self.collectives += 1
+        where = [0] * len(owners)
+        for r, h in enumerate(held):
+            for slot, i in enumerate(h):
+                where[i] = r * cap + slot
+        return recv[where].to(local.device).contiguous()
+
     def broadcast_from_owner(self, tensor: torch.Tensor, candidate: int, n_candidates: int) -> torch.Tensor:
         """Rejection sampling's survivor image travels once from the rank that owns `candidate`."""
         if self.solo:
             return tensor
-        owner = next(r for r in range(self.world) if self.span(n_candidates, r)[0] <= candidate < self.span(n_candidates, r)[1])
+        owner = self.owner(candidate, n_candidates)
         src = owner if self.group is None else dist.get_global_rank(self.group, owner)
         if tensor.is_cuda and not self.dev_direct:
             host = tensor.cpu()

@@ -95,6 +95,7 @@ class _Loop:
         self.S_churn, self.S_min, self.S_max, self.S_noise = S_churn, S_min, S_max, S_noise
         self.scale_fn, self.shards = scale_fn, shards
         self.rewards, self.selected = [], []
+        self.beam_parents = []                # generate_image_grid(beam_search=True): selected // N per sigma step
         self.record_noises, self.best_noises = False, {}
         self.reuse_winner = False
         self.forced = None                    # generate_image_grid(forced_selections=...)
@@ -109,22 +110,23 @@ class _Loop:
         coef = (t_hat ** 2 - t_cur ** 2).sqrt() * self.S_noise
         return float(t_hat), float(coef)
 
-    def step(self, x_cur, t_cur, t_next, i, eps, labels, nb=None, interleave=False, live=None):
+    def step(self, x_cur, t_cur, t_next, i, eps, labels, nb=None, interleave=False, live=None, first_denoised=False):
         """edm/main.py:82-96 on the device.  x_cur [xb,...] f64 is broadcast to nb rows; eps [nb,...] f64|f32.
-        live: rows that are real candidates (the rest is batch-shape padding): only those count as candidate evaluations."""
+        live: rows that are real candidates (the rest is batch-shape padding): only those count as candidate evaluations.
+        first_denoised: return D(x_hat, t_hat) instead of the second-order output (the beam branch's own step, edm/main.py:161-212)."""
         nb = eps.shape[0] if nb is None else nb
         evals0 = getattr(self.net, 'evals', None)
         t_hat, coef = self.churn(t_cur)
         t_hat_t = torch.tensor([t_hat], dtype=torch.float64)
         x_hat = ops.heun_xhat(x_cur, eps, coef, nb, interleave)
-        D = self.net(x_hat, t_hat_t, labels)
+        D = D1 = self.net(x_hat, t_hat_t, labels)
         d_cur, x_next = ops.heun_euler(x_hat, D, t_hat, float(t_next))
         if i < self.num_steps - 1:
             D = self.net(x_next, torch.as_tensor(t_next, dtype=torch.float64).reshape(1), labels)
             ops.heun_correct(x_hat, D, d_cur, t_hat, float(t_next), x_next)
         if live is not None and live != nb and evals0 is not None:       # padding rows went through the denoiser but are not counted
             self.net.evals = evals0 + (self.net.evals - evals0) // nb * live
-        return x_next, D
+        return x_next, (D1 if first_denoised else D)
 
     def score(self, scorer, x, labels):
         img = ops.quantize_u8(x)
@@ -178,6 +180,60 @@ def _beam(L: _Loop, t_steps, x_next, labels, p, pre):
     # (edm/main.py:140), so `--method beam` raises AttributeError on entry.  Kept verbatim for drop-in behaviour.
     b, k = p.b, p.k
     raise RuntimeError('unreachable')
+
+
+def beam_select(rewards, B):
+    """Top B of each row of `rewards` [S, B*N] (host, float32), best first; exact ties go to the lower flat index j*N + n.
+    A stable host sort, as the SD beam's (sd_pipeline.py): torch.topk leaves the order of exact ties unspecified."""
+    r = rewards.to(torch.float32).cpu()
+    rows = [sorted(range(r.shape[1]), key=v.__getitem__, reverse=True)[:B] for v in r.tolist()]
+    return torch.tensor(rows, dtype=torch.int64).reshape(r.shape[0], B)
+
+
+def _beam_search(L: _Loop, t_steps, x_next, labels, p, pre):
+    """generate_image_grid(beam_search=True): the search edm/main.py:138-404 sets out to do -- B = p.B beams per image (the reference's k),
+    N = p.N candidates per beam (its b) -- with the survivor gather fixed (:375-379 reads every survivor from beam row `sample_idx`).
+    Beam rows are image-major (row s*B + j, :155); per sigma step one host draw [N, C, H, W] per beam row in row order (:257), drawn at
+    gamma = 0 steps too; every candidate takes the full step with churn and Heun and is scored on the step's returned `denoised`
+    (:319-336) -- the branch's own step_with_microbatch (:161-212) returns the FIRST denoiser output, D(x_hat, t_hat), its Heun stage
+    keeps a `denoised_2` of its own; the reference's k = 1 runs pin that (tests/golden/make_golden_beam.py); per image the top
+    B of the B*N rewards survive in rank order (beam_select); the result is beam 0 (:404).  All S*B*N rows of a step go through the
+    denoiser and the scorer in one call each (the reference's micro-batches are memory workarounds over independent rows).
+    Sharded: rank r owns candidates [lo, hi) of EVERY beam; per step one reward all-gather and one exchange of the S*B survivor rows."""
+    B, N, S = p.B, p.N, x_next.shape[0]
+    shape1 = tuple(x_next.shape[1:])
+    L.shards.require_candidates(N, 'EDM beam search')
+    lo, hi = L.shards.span(N)
+    nl = hi - lo
+    lab = None if labels is None else labels.repeat_interleave(B * nl, dim=0).contiguous()
+    x = x_next.repeat_interleave(B, dim=0).contiguous()                               # [S*B, ...] (:155)
+
+    def draw(i):
+        if pre is not None and i in pre:
+            if tuple(pre[i].shape) != (S, B, N) + shape1:
+                raise ValueError(f'precomputed_noise[{i}]: beam search takes [S, B, N, C, H, W] = {(S, B, N) + shape1}, got {tuple(pre[i].shape)}')
+            return pre[i].to(torch.float64).reshape(S * B, N, *shape1)
+        return torch.stack([torch.randn((N,) + shape1, dtype=torch.float64) for _ in range(S * B)])        # :257, one draw per beam
+
+    eps = draw(0)
+    for i in range(L.num_steps):
+        eps_l = L.up(eps[:, lo:hi].reshape(S * B * nl, *shape1))
+        x_cand, x0 = L.step(x, t_steps[i], t_steps[i + 1], i, eps_l, lab, interleave=True, first_denoised=True)
+        loc = L.score(p.scorer, x0, lab).to(L.dev, torch.float32).view(S * B, nl).t().contiguous().reshape(-1)   # candidate-major
+        # the draws never depend on search results: the next step's are made (in the reference's order) while the GPU runs this step --
+        # in line they left it idle for the 10 ms that 64 x [3, 64, 64] float64 normals take on the host (DESIGN.md section 5)
+        eps = draw(i + 1) if i + 1 < L.num_steps else None
+        allr = L.shards.gather_rewards(loc, N, S * B).view(N, S * B).t().contiguous().cpu().reshape(S, B * N)
+        sel = beam_select(allr, B)                                                     # [S, B] flat indices j*N + n
+        L.rewards.append(allr)
+        L.selected.append(sel)
+        L.beam_parents.append(sel // N)
+        # survivor (s, rank q) is candidate n = sel % N of beam row s*B + sel // N: this rank holds it iff lo <= n < hi
+        rows = (torch.arange(S).reshape(S, 1) * B + sel // N).reshape(-1)
+        cand = (sel % N).reshape(-1)
+        src = rows * nl + (cand - lo).clamp(0, nl - 1)                                 # any valid row where the survivor is another rank's
+        x = L.shards.exchange_rows(x_cand.index_select(0, L.up(src)), [L.shards.owner(n, N) for n in cand.tolist()])
+    return x.view(S, B, *shape1)[:, 0].contiguous()
 
 
 class _Lookahead:
@@ -477,7 +533,7 @@ def generate_image_grid(
     precomputed_noise: Optional[Dict[Any, torch.Tensor]] = None,
     *, scale_fn: Callable[[int, int, int], float] = builtin_scale, compute_dtype=ops.F16X3, verbose=True,
     reuse_winner: Optional[bool] = None, record_noises: bool = False, shard_candidates: bool = True,
-    forced_selections: Optional[Sequence[int]] = None, candidate_chunk: Optional[int] = None,
+    forced_selections: Optional[Sequence[int]] = None, candidate_chunk: Optional[int] = None, beam_search: bool = False,
 ):
     """Same positional/keyword surface as edm/main.py:47-55.  Keyword-only extras: `scale_fn` (the hash-derived step
     table, edm/main.py:776), `compute_dtype` (default ops.F16X3: split precision, the reference's fp32 selections at a third of the 16-bit
@@ -489,7 +545,12 @@ def generate_image_grid(
     rank must pass the same list: the override is applied after the reward all-gather, on every rank alike), `candidate_chunk` (eps-greedy /
     zero-order: evaluate the candidates of an iteration in sequential pieces of that many candidates instead of one batch -- the kernels,
     split-K factors and launch forms a rank of a sharded run uses for a share of that size, on one GPU; values are the batched run's up to
-    the f32 summation order those launch forms imply).  Writes the PNG grid like the
+    the f32 summation order those launch forms imply), `beam_search` (SamplingMethod.BEAM_SEARCH only.  False, the default: the reference's
+    branch as it stands -- it reads `method_params.b` / `.k`, which SamplingParams does not define, and raises AttributeError.  True: the search
+    that branch sets out to do, `_beam_search`: B = sampling_params['B'] beams per image (the reference's k) x N = sampling_params['N']
+    candidates per beam (its b), per sigma step the top B of an image's B*N rewards survive in rank order, exact ties to the lower flat index
+    j*N + n; `precomputed_noise[i]` of shape [S, B, N, C, H, W] replaces the draws of step i; the result dict gains `beam_parents`, and
+    `rewards` / `selected` hold one [S, B*N] / [S, B] tensor per sigma step).  Writes the PNG grid like the
     reference when `dest_path` is not None and additionally returns a dict with the final state and the search trace."""
     device = torch.device(device)
     if device.type != 'cuda':
@@ -520,10 +581,21 @@ def generate_image_grid(
         if sampling_method not in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER) or int(candidate_chunk) < 1:
             raise ValueError('candidate_chunk: a positive candidate count, eps-greedy / zero-order search only')
         L.chunk = int(candidate_chunk)
+    method_fn = _METHODS[sampling_method]
+    if beam_search:
+        if sampling_method != SamplingMethod.BEAM_SEARCH:
+            raise ValueError(f'beam_search=True: SamplingMethod.BEAM_SEARCH only, got {sampling_method.name}')
+        for name, given in (('forced_selections', forced_selections is not None), ('candidate_chunk', candidate_chunk is not None),
+                            ('record_noises', bool(record_noises))):
+            if given:
+                raise ValueError(f'beam_search=True: {name} is not supported by the beam search')
+        if int(p.B) < 1 or int(p.N) < 1:
+            raise ValueError(f'beam_search=True: need B >= 1 beams and N >= 1 candidates per beam, got B={p.B}, N={p.N}')
+        method_fn = _beam_search
     x0 = (latents.to(torch.float64).cpu() * t_steps[0]).to(device).contiguous()       # edm/main.py:99
     labels = None if class_labels is None else class_labels.to(device, torch.float32).contiguous()
     evals0 = getattr(net, 'evals', 0)
-    x_next = _METHODS[sampling_method](L, t_steps, x0, labels, p, precomputed_noise)
+    x_next = method_fn(L, t_steps, x0, labels, p, precomputed_noise)
     image = ops.quantize_u8(x_next)                                                   # edm/main.py:869
     scores = p.scorer(image.clone(), labels, torch.zeros(image.shape[0], device=device))
     avg_score = float(scores.float().mean())
@@ -540,7 +612,7 @@ def generate_image_grid(
     if verbose:
         print('Done.')
     return dict(x=x_next, image=img_cpu, final_scores=scores.cpu(), avg_score=avg_score, t_steps=t_steps,
-                rewards=L.rewards, selected=L.selected, net_rows=getattr(net, 'evals', 0) - evals0,
+                rewards=L.rewards, selected=L.selected, beam_parents=L.beam_parents, net_rows=getattr(net, 'evals', 0) - evals0,
                 collectives=shards.collectives, best_noises={i: torch.stack(v) for i, v in L.best_noises.items()})
 
 

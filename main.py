@@ -33,6 +33,10 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   (--text-encoder hip, the SD text encoder, stays float16: the reference runs SD in float16)
     --jpeg-codec: --scorer compressibility: pil (default: the reference's host encode per image) | hip (the same byte count computed on the
                   GPU, identical rewards; image sides must be multiples of 16; no fallback)
+    --beam      : EDM backend, --method beam: reference (default: the reference's branch as it stands -- it reads fields SamplingParams does not
+                  define and raises AttributeError on entry) | run (the search that branch sets out to do: --B beams per image, the reference's
+                  k, x --N candidates per beam, its b; per sigma step the top B of the B*N rewards survive, exact ties to the lower flat index;
+                  generate_image_grid(beam_search=True)).  --backend sd has a working beam search of its own and ignores the flag
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`; the N candidates of every
@@ -235,6 +239,9 @@ def build_parser():
     parser.add_argument('--jpeg-codec', dest='jpeg_codec', type=str, default='pil', choices=['pil', 'hip'],
                         help="--scorer compressibility: 'hip' = the JPEG byte length computed on the GPU (identical rewards; image sides must be "
                              "multiples of 16, an error otherwise), 'pil' = the reference's host encode of every image")
+    parser.add_argument('--beam', type=str, default='reference', choices=['reference', 'run'],
+                        help="EDM backend, --method beam: 'reference' = the reference's branch as it stands (AttributeError on entry), 'run' = the "
+                             "beam search it sets out to do: --B beams x --N candidates per beam (generate_image_grid(beam_search=True))")
     parser.add_argument('--seeds', type=str, default=None, help='bulk mode: seeds, e.g. 0-63 or 1,2,5-10 (one image per seed)')
     parser.add_argument('--outdir', type=str, default='out', help='bulk mode: output directory')
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')
@@ -250,6 +257,8 @@ def main(argv=None):
     if args.backend == 'edm' and args.scorer == 'clip':
         raise ValueError('clip scorer is only available for sd backend')
     if args.backend == 'sd':
+        if getattr(args, 'beam', 'reference') != 'reference':
+            print(f'[SD] --beam {args.beam} is an EDM option: ignored (--method beam runs on the SD backend as it is)')
         return main_sd(args)
     if not str(args.device).startswith('cuda'):
         raise RuntimeError(f"--device {args.device}: this build is the GPU path; the CPU path is the reference itself "
@@ -277,6 +286,10 @@ def main(argv=None):
     # edm/generate.py:31-32: the schedule's end points inside the network's range (EDMPrecond: 0 .. inf, the identity).  Without it an iDDPM
     # network rounds 0.002 to u[M] = 0 and the last Heun step divides by t_hat = 0, as the reference's would
     sigma_min, sigma_max = max(0.002, net.sigma_min), min(80, net.sigma_max)
+    beam_run = getattr(args, 'beam', 'reference') == 'run'
+    if beam_run and args.method != 'beam':
+        raise ValueError(f'--beam run goes with --method beam, got --method {args.method}')
+    extras = dict(beam_search=True) if beam_run else {}
     if args.seeds is not None:                                                        # bulk mode: seeds sharded over the ranks
         from diffusion_tts_amd.bulk import generate_seeds
         mm = {'naive': SamplingMethod.NAIVE, 'rejection': SamplingMethod.REJECTION_SAMPLING, 'beam': SamplingMethod.BEAM_SEARCH,
@@ -286,7 +299,7 @@ def main(argv=None):
             sp.update(N=args.N, K=args.K, lambda_param=args.lambda_, eps=args.eps, B=args.B, S=args.S)
         done = generate_seeds(net, args.seeds, args.outdir, sampling_method=mm[args.method], sampling_params=sp,
                               class_idx=args.class_idx, subdirs=args.subdirs, device=device, compute_dtype=dtype,
-                              num_steps=18, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003, sigma_min=sigma_min, sigma_max=sigma_max)
+                              num_steps=18, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003, sigma_min=sigma_min, sigma_max=sigma_max, **extras)
         print(f'[EDM] rank {os.environ.get("RANK", "0")}: {len(done)} images -> {args.outdir}')
         if world > 1:
             dist.barrier()
@@ -313,7 +326,7 @@ def main(argv=None):
     outname = args.output or f'edm_{args.method}_{args.scorer}.png'
     res = generate_image_grid(net, outname, latents, class_labels, seed=args.seed, gridw=1, gridh=1, device=device,
                               num_steps=18, sigma_min=sigma_min, sigma_max=sigma_max, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003,
-                              sampling_method=method_map[args.method], sampling_params=sampling_params, compute_dtype=dtype)
+                              sampling_method=method_map[args.method], sampling_params=sampling_params, compute_dtype=dtype, **extras)
     if int(os.environ.get('RANK', '0')) == 0:
         print(f'\n[EDM] Saved: {outname}  (denoiser rows: {res["net_rows"]}, reward collectives: {res["collectives"]})')
         print(f'[EDM] compute mode {args.dtype}; denoiser forwards: {net._graphs.path_report()}\n')
