@@ -95,6 +95,7 @@ SIGNATURES = {
     'dts_take_token': [_p, _i, _p, _i, _i, _i, _i, _p],
     'dts_softmax_gather': [_p, _p, _p, _i, _i, _p],
     'dts_candidate_noise': [_p, _p, _p, _p, _p, _i, _i, _i, _p],
+    'dts_candidate_noise_rows': [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     'dts_candidate_noise_sd': [_p, _p, _p, _p, _p, _i, _i, _i64, _p],
     'dts_cfg_combine': [_p, _p, _f, _p, _i, _i64, _p],
     'dts_ddim_candidates': [_p, _p, _p, _p, _p, _i, _f, _f, _f, _i, _i64, _p],
@@ -103,7 +104,7 @@ OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 123              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 124              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

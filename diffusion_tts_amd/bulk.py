@@ -5,7 +5,8 @@ parallel.CandidateShards instead).
 Mirrors the batch bookkeeping of the reference's bulk generator (edm/generate.py:254-309): seeds are split into
 `ceil(len(seeds) / (batch * world)) * world` batches by `tensor_split` and rank r takes batches r, r+world, ...; images are
 written as `<outdir>/<seed:06d>.png` (`--subdirs`: one directory per 1000 seeds).  Each image runs the search loop of
-`generate_image_grid` with `seed` as its RNG seed, so a seed's result does not depend on the number of ranks.  Latents and
+`generate_image_grid` with `seed` as its RNG seed -- `search_batch` seeds at a time in lock-step as one batch, every image on its own
+seed's stream (`row_seeds`) -- so a seed's result does not depend on the number of ranks or on its batch.  Latents and
 labels come from a per-seed CPU generator (the reference's StackedRandomGenerator draws on the CUDA device, a stream no
 other device reproduces; its per-seed independence is what is kept).
 
@@ -53,24 +54,69 @@ def seed_inputs(seed: int, net, class_idx: Optional[int] = None):
     return latents, labels
 
 
+def image_result(res, b, count, local_search):
+    """Image b's part of the result dict of a lock-step generate_image_grid(row_seeds=...) call over `count` images, shaped like a one-image
+    call's: the image's slice of x, image, final_scores, rewards, selected, beam_parents and best_noises; `net_rows` is the call's count
+    divided by the batch size (exact: the searches run in lock-step); `row_seeds` stays the whole batch's.  local_search: eps-greedy /
+    zero-order, whose rewards are [N, B] (every other trace tensor has the image first)."""
+    one = dict(res)
+    for key in ('x', 'image', 'final_scores'):
+        one[key] = res[key][b:b + 1]
+    one['avg_score'] = float(one['final_scores'].float().mean())
+    one['rewards'] = [r[:, b:b + 1] if local_search else r[b:b + 1] for r in res['rewards']]
+    one['selected'] = [s[b:b + 1] for s in res['selected']]
+    one['beam_parents'] = [s[b:b + 1] for s in res['beam_parents']]
+    one['best_noises'] = {i: v[:, b:b + 1] for i, v in res['best_noises'].items()}
+    assert res['net_rows'] % count == 0, (res['net_rows'], count)
+    one['net_rows'] = res['net_rows'] // count
+    return one
+
+
 @torch.no_grad()
 def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAIVE, sampling_params: Optional[Dict[str, Any]] = None,
                    class_idx: Optional[int] = None, max_batch_size: int = 64, subdirs: bool = False, device='cuda',
-                   compute_dtype=ops.F16X3, verbose=False, **sampler_kwargs):
-    """Returns {seed: result dict of generate_image_grid} for the seeds this rank generated."""
-    dist_on = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+                   compute_dtype=ops.F16X3, verbose=False, search_batch: int = 1, rank: Optional[int] = None, world: Optional[int] = None,
+                   **sampler_kwargs):
+    """Returns {seed: result dict of generate_image_grid} for the seeds this rank generated.  This rank's seeds are split into batches of up to
+    `search_batch` (rank_batches; rank / world default to torch.distributed's when it is initialised, else 0 / 1) and the searches of a batch
+    run in lock-step as ONE generate_image_grid(row_seeds=batch) call -- search_batch x the rows in every denoiser and scorer call; image b
+    draws from its own seed's stream, so a seed's search is the one it runs alone (search_batch=1: bit for bit the `seed=` call's; larger
+    batches: up to the launch forms the row count selects).  One PNG per seed; each seed's dict is its slice of the call's (image_result).
+    MCTS, and calls with forced_selections / precomputed_noise (per search by nature), run one `seed=` call per seed as before.
+    `max_batch_size` is accepted for the reference's signature; the split is by `search_batch`."""
+    if rank is None or world is None:
+        dist_on = dist.is_available() and dist.is_initialized()
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+    if int(search_batch) < 1:
+        raise ValueError(f'search_batch: a positive number of seeds per lock-step batch, got {search_batch}')
     net = load_network(network, device=device, dtype=compute_dtype)
+    lock_step = sampling_method != SamplingMethod.MCTS and not any(
+        sampler_kwargs.get(k) is not None for k in ('forced_selections', 'precomputed_noise'))
+    local_search = sampling_method in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER)
     done = {}
-    for batch in rank_batches(parse_int_list(seeds), max_batch_size, rank, world):
-        for seed in batch.tolist():
-            latents, labels = seed_inputs(seed, net, class_idx)
-            image_dir = os.path.join(outdir, f'{seed - seed % 1000:06d}') if subdirs else outdir
-            os.makedirs(image_dir, exist_ok=True)
-            done[seed] = generate_image_grid(net, os.path.join(image_dir, f'{seed:06d}.png'), latents, labels, seed=seed, gridw=1,
-                                             gridh=1, device=device, sampling_method=sampling_method,
-                                             sampling_params=sampling_params, compute_dtype=compute_dtype, verbose=verbose,
-                                             shard_candidates=False, **sampler_kwargs)
+
+    def png_path(seed):
+        image_dir = os.path.join(outdir, f'{seed - seed % 1000:06d}') if subdirs else outdir
+        os.makedirs(image_dir, exist_ok=True)
+        return os.path.join(image_dir, f'{seed:06d}.png')
+
+    for batch in rank_batches(parse_int_list(seeds), int(search_batch), rank, world):
+        batch = batch.tolist()
+        if not batch:
+            continue
+        inputs = [seed_inputs(seed, net, class_idx) for seed in batch]
+        common = dict(gridw=1, gridh=1, device=device, sampling_method=sampling_method, sampling_params=sampling_params,
+                      compute_dtype=compute_dtype, verbose=verbose, shard_candidates=False, **sampler_kwargs)
+        if not lock_step:
+            for seed, (latents, labels) in zip(batch, inputs):
+                done[seed] = generate_image_grid(net, png_path(seed), latents, labels, seed=seed, **common)
+            continue
+        latents = torch.cat([lat for lat, _ in inputs], dim=0)
+        labels = None if inputs[0][1] is None else torch.cat([lab for _, lab in inputs], dim=0)
+        res = generate_image_grid(net, None, latents, labels, row_seeds=batch, **common)
+        for b, seed in enumerate(batch):
+            done[seed] = image_result(res, b, len(batch), local_search)
+            save_image(done[seed]['image'][0].permute(1, 2, 0).contiguous().numpy(), png_path(seed))
     return done
 
 

@@ -516,15 +516,19 @@ __global__ __launch_bounds__(256) void softmax_gather_kernel(const float* __rest
 }
 
 // ---- K14 -----------------------------------------------------------------------------------------------
-// one block per candidate row; fp64 L2 norm by block reduction, then the axpy
+// one block per candidate row; fp64 L2 norm by block reduction, then the axpy.  One body, two forms: ROWS = false reads mode / scale per
+// candidate (mode[cn], shared by the b images of candidate cn), ROWS = true per output row (mode[row]: lock-step searches whose coins differ
+// from image to image).  Only the index of the two scalar reads differs, so equal mode / scale give equal bits in either form.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void candidate_noise_kernel(const double* __restrict__ pivot, const double* __restrict__ g,
                                                                const int32_t* __restrict__ mode, const float* __restrict__ scale,
                                                                double* __restrict__ cand, int b, int chw) {
   __shared__ double red[4];
   const int row = blockIdx.x, cn = row / b, sample = row - cn * b;
+  const int key = ROWS ? row : cn;
   const double* gr = g + (size_t)row * chw;
   double* out = cand + (size_t)row * chw;
-  if (mode[cn] == 0) {
+  if (mode[key] == 0) {
     for (int i = threadIdx.x; i < chw; i += blockDim.x) out[i] = gr[i];
     return;
   }
@@ -534,7 +538,7 @@ __global__ __launch_bounds__(256) void candidate_noise_kernel(const double* __re
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
   __syncthreads();
   const double nrm = sqrt(red[0] + red[1] + red[2] + red[3]);
-  const double sc = (double)scale[cn];
+  const double sc = (double)scale[key];
   const double* pv = pivot + (size_t)sample * chw;
   for (int i = threadIdx.x; i < chw; i += blockDim.x) out[i] = pv[i] + sc * (gr[i] / nrm);
 }
@@ -958,8 +962,17 @@ extern "C" int dts_candidate_noise(const double* pivot, const double* g, const i
   DTS_CHECK_ARG(pivot && g && mode && scale && cand, "dts_candidate_noise: null pointer");
   DTS_CHECK_ARG(nb > 0 && b > 0 && nb % b == 0 && chw > 0, "dts_candidate_noise: nb=%d b=%d", nb, b);
   ST;
-  hipLaunchKernelGGL(candidate_noise_kernel, dim3(nb), dim3(256), 0, st, pivot, g, mode, scale, cand, b, chw);
+  hipLaunchKernelGGL(candidate_noise_kernel<false>, dim3(nb), dim3(256), 0, st, pivot, g, mode, scale, cand, b, chw);
   DTS_CHECK_LAUNCH("dts_candidate_noise");
+  return DTS_OK;
+}
+extern "C" int dts_candidate_noise_rows(const double* pivot, const double* g, const int32_t* mode, const float* scale, double* cand, int nb,
+                                        int b, int chw, dts_stream s) {
+  DTS_CHECK_ARG(pivot && g && mode && scale && cand, "dts_candidate_noise_rows: null pointer");
+  DTS_CHECK_ARG(nb > 0 && b > 0 && nb % b == 0 && chw > 0, "dts_candidate_noise_rows: nb=%d b=%d", nb, b);
+  ST;
+  hipLaunchKernelGGL(candidate_noise_kernel<true>, dim3(nb), dim3(256), 0, st, pivot, g, mode, scale, cand, b, chw);
+  DTS_CHECK_LAUNCH("dts_candidate_noise_rows");
   return DTS_OK;
 }
 

@@ -1259,6 +1259,20 @@ def candidate_noise(pivot, g, mode, scale):
     return out
 
 
+def candidate_noise_rows(pivot, g, mode_rows, scale_rows):
+    """candidate_noise with mode / scale per output row: pivot [b,...] f64, g [N*b,...] f64 (n-major), mode_rows int32 [N*b] (or [N, b]),
+    scale_rows f32 [N*b] -> candidates [N*b,...] f64; row n*b + s is built from pivot[s].  Bit-equal to candidate_noise where mode / scale
+    are constant over the images of every candidate."""
+    b = pivot.shape[0]
+    nb = g.shape[0]
+    if mode_rows.numel() != nb or scale_rows.numel() != nb:
+        raise ValueError(f'candidate_noise_rows: mode / scale need one entry per output row ({nb}), got {mode_rows.numel()} / {scale_rows.numel()}')
+    out = torch.empty_like(g)
+    _call('dts_candidate_noise_rows', _ptr(pivot, 'pivot', torch.float64), _ptr(g, 'g', torch.float64),
+          _ptr(mode_rows, 'mode_rows', torch.int32), _ptr(scale_rows, 'scale_rows', torch.float32), _ptr(out), nb, b, pivot[0].numel())
+    return out
+
+
 def candidate_noise_sd(pivot, u, mode, scale):
     """pivot [1,C,H,W], u [N,1,C,H,W] (same dtype), mode int32 [N], scale f32 [N,3] = (rand, lambda, sqrt(numel)) per candidate ->
     candidates [N,1,C,H,W]: the SD backend's eps-greedy / zero-order builder (pipeline_stable_diffusion.py:1371-1379) in the latents' dtype,

@@ -6,7 +6,8 @@ randomness is drawn from the torch *CPU* global generator (and numpy's for MCTS)
 order -- including draws whose values the reference throws away -- and uploaded, because the parity oracle is the
 reference's `--device cpu` run and a device Philox stream could not reproduce it (hard part 2).
 What runs on the GPU: every tensor operation -- candidate construction (K14), the fp64 Heun/Euler step (K9), the
-denoiser, quantisation (K10) and the scorer.
+denoiser, quantisation (K10) and the scorer.  With `row_seeds` every image of the batch draws from a CPU generator of its own instead
+(`_Source`): the searches of several seeds run in lock-step as one batch, each the search its seed runs alone.
 
 With torch.distributed initialised (one process per GPU) the N candidates of each search iteration are sharded
 across ranks (parallel.CandidateShards): one all-gather of N*B rewards per iteration, identical argmax on every rank.
@@ -87,6 +88,45 @@ def load_network(spec, device='cuda', dtype=ops.F16X3):
                      f'state-dict bundle or "random:<preset>[:seed]" (URLs cannot be fetched here)')
 
 
+class _Source:
+    """Where the host draws of a search come from.  row_seeds=None: torch's global CPU generator, one stream for the whole batch (the
+    reference's).  row_seeds given: image b draws from its own torch.Generator().manual_seed(row_seeds[b]) in exactly the order and shapes
+    a one-image call seeded row_seeds[b] draws from the global stream -- which such a generator replays bit for bit -- so an image's
+    numbers do not depend on its companions in the batch.  torch's CPU generator keeps the low 32 bits of a seed and nothing else (seed
+    s + 2^32 replays seed s): a seed outside [0, 2^32) is refused by name, not reduced in silence."""
+
+    def __init__(self, row_seeds=None):
+        for s in row_seeds or ():
+            if not 0 <= int(s) < 2 ** 32:
+                raise ValueError(f'row_seeds: seed {int(s)} is outside [0, 2^32): torch\'s CPU generator would keep its low 32 bits '
+                                 f'(the stream of seed {int(s) % 2 ** 32})')
+        self.gens = None if row_seeds is None else [torch.Generator().manual_seed(int(s)) for s in row_seeds]
+
+    def _gen(self, image):
+        return None if self.gens is None else self.gens[image]
+
+    def randn(self, image, shape, dtype=torch.float64):
+        """one draw of `shape` from image `image`'s stream (the global stream without row_seeds)"""
+        return torch.randn(shape, dtype=dtype, generator=self._gen(image))
+
+    def rand1(self, image):
+        return torch.rand(1, generator=self._gen(image))
+
+    def images(self, B, rows, shape1):
+        """[B * rows, *shape1] float64 normals, image-major: one draw for the batch, or image b's `rows` rows from its own stream"""
+        if self.gens is None:
+            return torch.randn((B * rows,) + tuple(shape1), dtype=torch.float64)
+        return torch.cat([self.randn(b, (rows,) + tuple(shape1)) for b in range(B)], dim=0)
+
+    def beams(self, S, B, N, shape1):
+        """[S * B, N, *shape1] float64 normals: one draw of N candidates per beam row in row order (image-major: image s draws its B blocks in order)"""
+        return torch.stack([self.randn(r // B, (N,) + tuple(shape1)) for r in range(S * B)])
+
+    def lanes(self, shape):
+        """the independent streams behind a batch of `shape` [B, ...] as (image, shape of one draw): the whole batch at once, or one image each"""
+        return [(None, tuple(shape))] if self.gens is None else [(b, (1,) + tuple(shape[1:])) for b in range(shape[0])]
+
+
 class _Loop:
     """State shared by the search methods: schedule, device step, bookkeeping."""
 
@@ -100,6 +140,7 @@ class _Loop:
         self.reuse_winner = False
         self.forced = None                    # generate_image_grid(forced_selections=...)
         self.chunk = None                     # generate_image_grid(candidate_chunk=...)
+        self.src = _Source()                  # generate_image_grid(row_seeds=...): one stream per image
 
     def up(self, t, dtype=None):
         return t.to(self.dev, dtype).contiguous() if dtype is not None else t.to(self.dev).contiguous()
@@ -137,7 +178,7 @@ class _Loop:
 # ---------------------------------------------------------------------------------------------------------
 def _naive(L: _Loop, t_steps, x_next, labels, p, pre):
     for i in range(L.num_steps):
-        eps = torch.randn(x_next.shape, dtype=torch.float64)                         # edm/main.py:865
+        eps = L.src.images(x_next.shape[0], 1, x_next.shape[1:])                     # edm/main.py:865
         x_next, _ = L.step(x_next, t_steps[i], t_steps[i + 1], i, L.up(eps), labels)
     return x_next
 
@@ -156,7 +197,7 @@ def _rejection(L: _Loop, t_steps, x_next, labels, p, pre):
         if pre is not None and i in pre:
             eps = pre[i][:, :N].reshape(B * N, *shape1).to(torch.float64)
         else:
-            eps = torch.randn((B * N,) + shape1, dtype=torch.float64)                # edm/main.py:120
+            eps = L.src.images(B, N, shape1)                                         # edm/main.py:120
         eps_l = L.up(eps.view(B, N, *shape1)[:, lo:hi].reshape(B * nl, *shape1))
         if x is None:
             x, _ = L.step(x_next, t_steps[i], t_steps[i + 1], i, eps_l, lab, interleave=True)
@@ -213,7 +254,7 @@ def _beam_search(L: _Loop, t_steps, x_next, labels, p, pre):
             if tuple(pre[i].shape) != (S, B, N) + shape1:
                 raise ValueError(f'precomputed_noise[{i}]: beam search takes [S, B, N, C, H, W] = {(S, B, N) + shape1}, got {tuple(pre[i].shape)}')
             return pre[i].to(torch.float64).reshape(S * B, N, *shape1)
-        return torch.stack([torch.randn((N,) + shape1, dtype=torch.float64) for _ in range(S * B)])        # :257, one draw per beam
+        return L.src.beams(S, B, N, shape1)                                            # :257, one draw per beam
 
     eps = draw(0)
     for i in range(L.num_steps):
@@ -260,29 +301,36 @@ class _Lookahead:
 
 def _eps_greedy_draws(L, p, pre, shape, lam):
     """The host-RNG stream of edm/main.py:724-797 in call order: per timestep one pivot, then per local-search
-    iteration the N coins / Gaussians / hash-derived scales."""
-    N, K, eps_p = p.N, p.K, p.eps
+    iteration the N coins / Gaussians / hash-derived scales.  A lane is one stream (_Source.lanes): the whole batch shares the coin of a
+    candidate (mode / scale [N]), or every image flips its own (mode / scale [N, B])."""
+    N, K, eps_p, src = p.N, p.K, p.eps, L.src
+    lanes = src.lanes(shape)
     if not (pre is not None and 'pivot' in pre):
-        torch.randn(shape, dtype=torch.float64)                                       # :727, overwritten at :737
+        src.images(shape[0], 1, shape[1:])                                            # :727, overwritten at :737
     for i in range(L.num_steps):
-        yield pre[f'pivot_{i}'] if (pre is not None and f'pivot_{i}' in pre) else torch.randn(shape, dtype=torch.float64)
+        yield pre[f'pivot_{i}'] if (pre is not None and f'pivot_{i}' in pre) else src.images(shape[0], 1, shape[1:])
         for k in range(K):
             g_h, mode, scale = [], [], []
             for n in range(N):
-                if torch.rand(1) < (1 - eps_p):                                       # :751
-                    if pre is not None and i in pre and k < pre[i].shape[1] and n < pre[i].shape[2]:
-                        g = pre[i][:, k, n].reshape(shape).to(torch.float64)
+                g_n, m_n, s_n = [], [], []
+                for image, lshape in lanes:
+                    if src.rand1(image) < (1 - eps_p):                                # :751
+                        if pre is not None and i in pre and k < pre[i].shape[1] and n < pre[i].shape[2]:
+                            g = pre[i][:, k, n].reshape(lshape).to(torch.float64)
+                        else:
+                            g = src.randn(image, lshape)                              # :767
+                        s = torch.ones([lshape[0], 1, 1, 1]) * L.scale_fn(i, k, n) * lam   # float32, :779
+                        m_n.append(1)
+                        s_n.append(float(s.flatten()[0]))
                     else:
-                        g = torch.randn(shape, dtype=torch.float64)                   # :767
-                    s = torch.ones([shape[0], 1, 1, 1]) * L.scale_fn(i, k, n) * lam   # float32, :779
-                    mode.append(1)
-                    scale.append(float(s.flatten()[0]))
-                else:
-                    key = f'fresh_{i}_{k}_{n}'
-                    g = pre[key].to(torch.float64) if (pre is not None and key in pre) else torch.randn(shape, dtype=torch.float64)
-                    mode.append(0)
-                    scale.append(0.0)
-                g_h.append(g)
+                        key = f'fresh_{i}_{k}_{n}'
+                        g = pre[key].to(torch.float64) if (pre is not None and key in pre) else src.randn(image, lshape)
+                        m_n.append(0)
+                        s_n.append(0.0)
+                    g_n.append(g)
+                g_h.append(g_n[0] if src.gens is None else torch.cat(g_n, dim=0))
+                mode.append(m_n[0] if src.gens is None else m_n)
+                scale.append(s_n[0] if src.gens is None else s_n)
             yield g_h, torch.tensor(mode, dtype=torch.int32), torch.tensor(scale, dtype=torch.float32)
 
 
@@ -299,6 +347,7 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
     lo, hi = L.shards.span(N)
     nl = hi - lo
     lab_l = None if labels is None else labels.repeat(nl, 1).contiguous()
+    per_image = L.src.gens is not None
     copy_stream = torch.cuda.Stream(device=L.dev)
 
     def stage(item):
@@ -329,7 +378,10 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
             g_h, mode_t, scale_t, g_l, ready, _pinned = draws.get()                    # n-major rows (:800)
             torch.cuda.current_stream(L.dev).wait_event(ready)
             g_l.record_stream(torch.cuda.current_stream(L.dev))
-            cand = ops.candidate_noise(pivot, g_l, L.up(mode_t[lo:hi]), L.up(scale_t[lo:hi]))
+            if per_image:                                                              # mode / scale [N, B]: a row each (n-major, as the rows)
+                cand = ops.candidate_noise_rows(pivot, g_l, L.up(mode_t[lo:hi].reshape(-1)), L.up(scale_t[lo:hi].reshape(-1)))
+            else:
+                cand = ops.candidate_noise(pivot, g_l, L.up(mode_t[lo:hi]), L.up(scale_t[lo:hi]))
             if L.chunk is None or L.chunk * B >= nl * B:
                 x_cand, x0 = L.step(x_cur, t_cur, t_next, i, cand, lab_l, nb=nl * B)
                 loc = L.score(p.scorer, x0, lab_l).to(L.dev, torch.float32)
@@ -355,7 +407,10 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
             # survivor rebuilt from the replicated host noise: no second collective
             bl = best.tolist()
             g_w = torch.stack([g_h[j][b] for b, j in enumerate(bl)])
-            if len(set(bl)) == 1:
+            if per_image:                                                              # every image's own winner, mode and scale: one launch
+                own = torch.arange(B)
+                pivot = ops.candidate_noise_rows(pivot, L.up(g_w), L.up(mode_t[best, own]), L.up(scale_t[best, own]))
+            elif len(set(bl)) == 1:
                 pivot = ops.candidate_noise(pivot, L.up(g_w), L.up(mode_t[bl[0]:bl[0] + 1]), L.up(scale_t[bl[0]:bl[0] + 1]))
             else:
                 rows = [ops.candidate_noise(pivot[b:b + 1].contiguous(), L.up(g_w[b:b + 1]), L.up(mode_t[j:j + 1]),
@@ -534,6 +589,7 @@ def generate_image_grid(
     *, scale_fn: Callable[[int, int, int], float] = builtin_scale, compute_dtype=ops.F16X3, verbose=True,
     reuse_winner: Optional[bool] = None, record_noises: bool = False, shard_candidates: bool = True,
     forced_selections: Optional[Sequence[int]] = None, candidate_chunk: Optional[int] = None, beam_search: bool = False,
+    row_seeds: Optional[Sequence[int]] = None,
 ):
     """Same positional/keyword surface as edm/main.py:47-55.  Keyword-only extras: `scale_fn` (the hash-derived step
     table, edm/main.py:776), `compute_dtype` (default ops.F16X3: split precision, the reference's fp32 selections at a third of the 16-bit
@@ -550,7 +606,12 @@ def generate_image_grid(
     that branch sets out to do, `_beam_search`: B = sampling_params['B'] beams per image (the reference's k) x N = sampling_params['N']
     candidates per beam (its b), per sigma step the top B of an image's B*N rewards survive in rank order, exact ties to the lower flat index
     j*N + n; `precomputed_noise[i]` of shape [S, B, N, C, H, W] replaces the draws of step i; the result dict gains `beam_parents`, and
-    `rewards` / `selected` hold one [S, B*N] / [S, B] tensor per sigma step).  Writes the PNG grid like the
+    `rewards` / `selected` hold one [S, B*N] / [S, B] tensor per sigma step), `row_seeds` (one seed per image: image b takes every host draw
+    of the search from its own generator seeded row_seeds[b], in the order and shapes of a one-image call with seed=row_seeds[b], so its
+    search is that call's whatever else is in the batch -- up to the launch forms the row count selects -- and the searches of many seeds
+    run in lock-step as one batch (bulk.generate_seeds(search_batch=...)); eps-greedy / zero-order coins then differ from image to image:
+    mode / scale are [N, B] and the candidates and the rebuilt pivots come from ops.candidate_noise_rows; the result dict gains `row_seeds`;
+    not with MCTS, forced_selections, precomputed_noise or candidates sharded over ranks).  Writes the PNG grid like the
     reference when `dest_path` is not None and additionally returns a dict with the final state and the search trace."""
     device = torch.device(device)
     if device.type != 'cuda':
@@ -570,6 +631,19 @@ def generate_image_grid(
     # `net_rows` equals the reference's count (config 3: 8 995); the 16-bit throughput modes reuse the row (8 960 rows, same values).
     L.reuse_winner = (compute_dtype not in (torch.float32, ops.F16X3)) if reuse_winner is None else bool(reuse_winner)
     L.record_noises = bool(record_noises)
+    if row_seeds is not None:
+        row_seeds = [int(s) for s in row_seeds]
+        if len(row_seeds) != latents.shape[0]:
+            raise ValueError(f'row_seeds: need one seed per image, got {len(row_seeds)} seeds for {latents.shape[0]} images')
+        if sampling_method == SamplingMethod.MCTS:
+            raise ValueError('row_seeds: SamplingMethod.MCTS is not supported (its numpy child draw and its ragged trees are per search)')
+        for name, given in (('forced_selections', forced_selections is not None), ('precomputed_noise', precomputed_noise is not None)):
+            if given:
+                raise ValueError(f'row_seeds: {name} is not supported with per-image random streams')
+        if not shards.solo:
+            raise ValueError('row_seeds: candidate sharding over more than one rank is not supported (shard_candidates=False: lock-step '
+                             'batches go with seed sharding)')
+        L.src = _Source(row_seeds)
     if forced_selections is not None:
         if sampling_method not in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER) or latents.shape[0] != 1:
             raise ValueError('forced_selections: eps-greedy / zero-order search of one image only')
@@ -611,9 +685,12 @@ def generate_image_grid(
         PIL.Image.fromarray(grid.numpy(), 'RGB').save(dest_path)
     if verbose:
         print('Done.')
-    return dict(x=x_next, image=img_cpu, final_scores=scores.cpu(), avg_score=avg_score, t_steps=t_steps,
-                rewards=L.rewards, selected=L.selected, beam_parents=L.beam_parents, net_rows=getattr(net, 'evals', 0) - evals0,
-                collectives=shards.collectives, best_noises={i: torch.stack(v) for i, v in L.best_noises.items()})
+    res = dict(x=x_next, image=img_cpu, final_scores=scores.cpu(), avg_score=avg_score, t_steps=t_steps,
+               rewards=L.rewards, selected=L.selected, beam_parents=L.beam_parents, net_rows=getattr(net, 'evals', 0) - evals0,
+               collectives=shards.collectives, best_noises={i: torch.stack(v) for i, v in L.best_noises.items()})
+    if row_seeds is not None:
+        res['row_seeds'] = row_seeds
+    return res
 
 
 def dump_noise_trajectory(result, directory='.'):

@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 123        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 124        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -59,7 +59,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      120: dts_conv_args.up == 2 (phase-packed weights), dts_conv_takes_phases, dts_conv_plan_info.phases;
                                      121: dts_precond_in (the VP, VE and iDDPM preconditioners);
                                      122: dts_attention_x3_masked, dts_text_tokens_f32 (the CLIP text tower in DTS_F16X3);
-                                     123: dts_ode_xhat, dts_ode_slope, dts_ode_correct (the general ODE step of the ablation sampler)) */
+                                     123: dts_ode_xhat, dts_ode_slope, dts_ode_correct (the general ODE step of the ablation sampler);
+                                     124: dts_candidate_noise_rows (mode / scale per output row: searches of several seeds in lock-step)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -436,6 +437,11 @@ int dts_softmax_gather(const float* logits, const int32_t* target, float* reward
  *   mode[n] == 1 : cand[i] = pivot[i % b] + (double)scale[n] * (g[i] / ||g[i]||_2)   (edm/main.py:767-788) */
 int dts_candidate_noise(const double* pivot, const double* g, const int32_t* mode, const float* scale,
                         double* cand, int nb, int b, int chw, dts_stream s);
+/* The same body with mode / scale per OUTPUT ROW (nb entries each): row r = n * b + sample reads mode[r], scale[r] and pivot[sample].  With
+ * mode / scale constant over the b images of every candidate the output is dts_candidate_noise's bit for bit (same reduction order).
+ * nb = b rebuilds b pivots, each from its own winner, in one launch. */
+int dts_candidate_noise_rows(const double* pivot, const double* g, const int32_t* mode, const float* scale,
+                             double* cand, int nb, int b, int chw, dts_stream s);
 /* The SD backend's builder (sd/diffusers/.../pipeline_stable_diffusion.py:1371-1379), in the latents' storage type `dtype` with the
  * reference's roundings: u host-drawn normals [n][count]; mode[c] == 0: cand[c] = u[c] (fresh noise, :1375);
  * mode[c] == 1: cand[c] = pivot + ((((u[c] / ||u[c]||) * scale[3c]) * scale[3c+1]) * scale[3c+2]), scale[3c..] = (rand, lambda, sqrt(count)) as f32:

@@ -39,6 +39,8 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   generate_image_grid(beam_search=True)).  --backend sd has a working beam search of its own and ignores the flag
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
+    --search-batch S: bulk mode: the searches of S seeds run in lock-step as ONE batch (S x the rows per denoiser call; every image draws
+                  from its own seed's stream, so a seed's search does not depend on its companions; default 1; --method mcts runs per seed)
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`; the N candidates of every
 search iteration are sharded across the ranks (diffusion_tts_amd/parallel.py).
 """
@@ -245,6 +247,8 @@ def build_parser():
     parser.add_argument('--seeds', type=str, default=None, help='bulk mode: seeds, e.g. 0-63 or 1,2,5-10 (one image per seed)')
     parser.add_argument('--outdir', type=str, default='out', help='bulk mode: output directory')
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')
+    parser.add_argument('--search-batch', type=int, default=1,
+                        help='bulk mode: run the searches of this many seeds in lock-step as one batch (default 1; mcts: one search per seed)')
     parser.add_argument('--class', dest='class_idx', type=int, default=None, help='bulk mode: class label (default: per-seed random)')
     return parser
 
@@ -298,7 +302,7 @@ def main(argv=None):
         if args.method != 'naive':
             sp.update(N=args.N, K=args.K, lambda_param=args.lambda_, eps=args.eps, B=args.B, S=args.S)
         done = generate_seeds(net, args.seeds, args.outdir, sampling_method=mm[args.method], sampling_params=sp,
-                              class_idx=args.class_idx, subdirs=args.subdirs, device=device, compute_dtype=dtype,
+                              class_idx=args.class_idx, subdirs=args.subdirs, device=device, compute_dtype=dtype, search_batch=args.search_batch,
                               num_steps=18, S_churn=40, S_min=0.05, S_max=50, S_noise=1.003, sigma_min=sigma_min, sigma_max=sigma_max, **extras)
         print(f'[EDM] rank {os.environ.get("RANK", "0")}: {len(done)} images -> {args.outdir}')
         if world > 1:
