@@ -97,14 +97,16 @@ SIGNATURES = {
     'dts_candidate_noise': [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     'dts_candidate_noise_rows': [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     'dts_candidate_noise_sd': [_p, _p, _p, _p, _p, _i, _i, _i64, _p],
+    'dts_candidate_noise_sd_rows': [_p, _p, _p, _p, _p, _i, _i, _i, _i64, _p],
     'dts_cfg_combine': [_p, _p, _f, _p, _i, _i64, _p],
     'dts_ddim_candidates': [_p, _p, _p, _p, _p, _i, _f, _f, _f, _i, _i64, _p],
+    'dts_ddim_candidates_groups': [_p, _p, _p, _p, _p, _i, _f, _f, _f, _i, _i, _i64, _p],
 }
 OTHER = {'dts_version': ([], _i), 'dts_conv_fuses_gn': ([C.POINTER(ConvArgs)], _i), 'dts_conv_kernel': ([C.POINTER(ConvArgs)], _i), 'dts_conv_folds_skip': ([C.POINTER(ConvArgs)], _i), 'dts_conv_takes_phases': ([C.POINTER(ConvArgs)], _i), 'dts_conv_plan': ([C.POINTER(ConvArgs), C.POINTER(ConvPlanInfo)], _i), 'dts_set_tuning': ([_i, _i], _i), 'dts_get_tuning': ([_i], _i), 'dts_last_error': ([], C.c_char_p), 'dts_gn_ws_floats': ([_i, _i], _i64),
          'dts_jpeg_workspace_bytes': ([_i, _i, _i], _i64)}
 
 _lib = None
-ABI_VERSION = 124              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
+ABI_VERSION = 125              # include/dts.h DTS_ABI_VERSION this binding was written against (ConvArgs = 208 bytes)
 
 
 def load():

@@ -120,6 +120,62 @@ def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAI
     return done
 
 
+def seed_png_path(outdir, seed, subdirs=False):
+    """<outdir>/<seed:06d>.png (`subdirs`: one directory per 1000 seeds), its directory created"""
+    image_dir = os.path.join(outdir, f'{seed - seed % 1000:06d}') if subdirs else outdir
+    os.makedirs(image_dir, exist_ok=True)
+    return os.path.join(image_dir, f'{seed:06d}.png')
+
+
+@torch.no_grad()
+def generate_sd_seeds(pipe, prompt, seeds, outdir, *, method='naive', params=None, search_batch: int = 1, num_inference_steps=50,
+                      score_function=None, subdirs: bool = False, decode_rows: Optional[int] = None, rank: Optional[int] = None,
+                      world: Optional[int] = None, save=True, **pipe_kwargs):
+    """The SD backend's bulk mode: one search per seed with `pipe` (sd_pipeline.SDSearchPipeline), `<outdir>/<seed:06d>.png` per seed.  This
+    rank's seeds (rank_batches; rank / world default to torch.distributed's when it is initialised, else 0 / 1; no collective is used) run
+    `search_batch` at a time in lock-step as ONE `pipe(..., row_seeds=batch)` call; seed s draws what `main.py --backend sd --seed s` draws,
+    so its search does not depend on its batch or on the number of ranks.  `method='rejection'` is the reference's N-trajectory loop as N
+    rows per seed; `method='mcts'` (ragged trees) runs one single-search call per seed after `torch.manual_seed(seed)`.  decode_rows caps the
+    rows per VAE decode.  pipe_kwargs (prompt_embeds=, negative_prompt_embeds=, guidance_scale=, eta=, ...) go to the call.
+    Returns {seed: maximum score} for the seeds this rank generated."""
+    if rank is None or world is None:
+        dist_on = dist.is_available() and dist.is_initialized()
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+    if int(search_batch) < 1:
+        raise ValueError(f'search_batch: a positive number of seeds per lock-step batch, got {search_batch}')
+    params = {} if params is None else params
+    done = {}
+
+    def write(image, seed):
+        if save:
+            arr = (image.clamp(0, 1).permute(1, 2, 0).float().cpu().numpy() * 255).round().astype('uint8')
+            save_image(arr, seed_png_path(outdir, seed, subdirs))
+
+    def number(v):
+        return float(v.item() if torch.is_tensor(v) else v)
+
+    for batch in rank_batches(parse_int_list(seeds), int(search_batch), rank, world):
+        batch = batch.tolist()
+        if not batch:
+            continue
+        if method == 'mcts':
+            cfg = pipe.unet.config
+            for seed in batch:
+                torch.manual_seed(seed)
+                lat = torch.randn(1, cfg.in_channels, cfg.sample_size, cfg.sample_size)
+                out, score = pipe(prompt=prompt, latents=lat, num_inference_steps=num_inference_steps, score_function=score_function,
+                                  method=method, params=params, output_type='pt', **pipe_kwargs)
+                done[seed] = number(score)
+                write(out.images[0], seed)
+            continue
+        out, scores = pipe(prompt=prompt, num_inference_steps=num_inference_steps, score_function=score_function, method=method,
+                           params=params, output_type='pt', row_seeds=batch, decode_rows=decode_rows, **pipe_kwargs)
+        for k, seed in enumerate(batch):
+            done[seed] = number(scores[k])
+            write(out.images[k], seed)
+    return done
+
+
 def batch_inputs(batch_seeds, net, class_idx: Optional[int] = None):
     """(rnd, latents, labels) of one batch as edm/generate.py:281-288 picks them: a StackedRandomGenerator over the batch's seeds, latents drawn
     first, then the label indices; `class_idx` overrides the drawn classes (the draw is still made)."""

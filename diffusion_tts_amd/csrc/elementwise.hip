@@ -545,13 +545,17 @@ __global__ __launch_bounds__(256) void candidate_noise_kernel(const double* __re
 
 // K14 of the SD backend (pipeline_stable_diffusion.py:1371-1379): the same construction in the LATENTS' storage type T, rounding where
 // the reference's tensor ops round -- norm (f32 accumulation, result in T), u / norm (in T), * python scalar (f32 math, result in T),
-// pivot + ... (in T).  One block per candidate.
-template <typename T>
+// pivot + ... (in T).  One block per candidate.  One body, two forms: ROWS = false is one search (every candidate reads the one pivot),
+// ROWS = true is S searches of `per` candidates each in lock-step (candidate row r = s * per + n reads pivot[s]; mode / scale are per row in
+// both forms).  Only the pivot's base differs, so S = 1 gives the single-search form's bits, and the single-search form's instruction
+// stream is what it was before there were two (`per` sits in the padding of its argument block and is never read).
+template <typename T, bool ROWS>
 __global__ __launch_bounds__(256) void candidate_noise_sd_kernel(const T* __restrict__ pivot, const T* __restrict__ u,
                                                                   const int32_t* __restrict__ mode, const float* __restrict__ scale,
-                                                                  T* __restrict__ cand, int count) {
+                                                                  T* __restrict__ cand, int count, int per) {
   __shared__ float red[4];
   const int cn = blockIdx.x;
+  const T* pv = ROWS ? pivot + (size_t)(cn / per) * count : pivot;
   const T* ur = u + (size_t)cn * count;
   T* out = cand + (size_t)cn * count;
   if (mode[cn] == 0) {                                        // fresh Gaussian (:1375)
@@ -586,25 +590,36 @@ __global__ __launch_bounds__(256) void candidate_noise_sd_kernel(const T* __rest
     t_ = ld1<T>(&a) * s2;                                     // * np.sqrt(numel)
     asm volatile("" : "+v"(t_));
     st1<T>(&b, t_);
-    st1<T>(&c, ld1<T>(pivot + i) + ld1<T>(&b));               // pivot + ...
+    st1<T>(&c, ld1<T>(pv + i) + ld1<T>(&b));                  // pivot + ...
     out[i] = c;
   }
 }
 
 // ---- K13 -----------------------------------------------------------------------------------------------
-template <typename T>
+// One body, two forms.  The single-pair form (no G) is one (x, e) pair with its ncand candidates; the groups form (G = long long) is
+// `groups` independent pairs in one launch, x / e / x0_out [groups][count] and z / prev [groups][ncand][count] (group-major: the host draws
+// arrive per beam or per search as [ncand, ...] stacks).  The scalars are shared (lock-step searches sit at one timestep).  Only the
+// candidate base differs, so groups = 1 gives equal bits.  `groups` is a parameter PACK so that the single-pair form has the argument block
+// it always had: its instruction stream (the offsets of the implicit arguments behind the block included) is unchanged.
+template <typename T, typename... G>
 __global__ void ddim_candidates_kernel(const T* __restrict__ x, const T* __restrict__ e, const T* __restrict__ z, T* __restrict__ prev,
-                                       T* __restrict__ x0_out, float a_t, float a_prev, float sigma_t, int ncand, long long count) {
+                                       T* __restrict__ x0_out, float a_t, float a_prev, float sigma_t, int ncand, long long count,
+                                       G... groups) {
+  constexpr bool GROUPS = sizeof...(G) == 1;
+  static_assert(sizeof...(G) <= 1, "at most one group count");
+  const long long total = (count * ... * (long long)groups);
   const float sa = sqrtf(a_t), sb = sqrtf(1.f - a_t);
   const float sp = sqrtf(a_prev), dirc = sqrtf(1.f - a_prev - sigma_t * sigma_t);
-  GSL(i, count) {
+  GSL(i, total) {
     const float xv = ld1<T>(x + i), ev = ld1<T>(e + i);
     const float x0 = (xv - sb * ev) / sa;
     if (x0_out) st1<T>(x0_out + i, x0);
     const float base = sp * x0 + dirc * ev;
+    // element j of group g: candidate c sits at (g * ncand + c) * count + j = i + (g * (ncand - 1) + c) * count
+    const size_t at = GROUPS ? (size_t)i + (size_t)(i / count) * (size_t)(ncand - 1) * (size_t)count : (size_t)i;
     for (int c = 0; c < ncand; ++c) {
-      const float zv = z ? ld1<T>(z + (size_t)c * count + i) : 0.f;
-      st1<T>(prev + (size_t)c * count + i, base + sigma_t * zv);
+      const float zv = z ? ld1<T>(z + (size_t)c * count + at) : 0.f;
+      st1<T>(prev + (size_t)c * count + at, base + sigma_t * zv);
     }
   }
 }
@@ -982,8 +997,22 @@ extern "C" int dts_candidate_noise_sd(const void* pivot, const void* u, const in
   DTS_CHECK_ARG(n > 0 && count > 0 && count < (1ll << 31), "dts_candidate_noise_sd: n=%d count=%lld", n, (long long)count);
   ST;
   DTS_DISPATCH_DTYPE(dtype, {
-    hipLaunchKernelGGL((candidate_noise_sd_kernel<T>), dim3(n), dim3(256), 0, st, (const T*)pivot, (const T*)u, mode, scale, (T*)cand, (int)count);
+    hipLaunchKernelGGL((candidate_noise_sd_kernel<T, false>), dim3(n), dim3(256), 0, st, (const T*)pivot, (const T*)u, mode, scale, (T*)cand,
+                       (int)count, n);
     DTS_CHECK_LAUNCH("dts_candidate_noise_sd");
+  });
+  return DTS_OK;
+}
+extern "C" int dts_candidate_noise_sd_rows(const void* pivot, const void* u, const int32_t* mode, const float* scale, void* cand, int dtype,
+                                           int searches, int per, int64_t count, dts_stream s) {
+  DTS_CHECK_ARG(pivot && u && mode && scale && cand, "dts_candidate_noise_sd_rows: null pointer");
+  DTS_CHECK_ARG(searches > 0 && per > 0 && (long long)searches * per < (1ll << 31) && count > 0 && count < (1ll << 31),
+                "dts_candidate_noise_sd_rows: searches=%d per=%d count=%lld", searches, per, (long long)count);
+  ST;
+  DTS_DISPATCH_DTYPE(dtype, {
+    hipLaunchKernelGGL((candidate_noise_sd_kernel<T, true>), dim3(searches * per), dim3(256), 0, st, (const T*)pivot, (const T*)u, mode, scale,
+                       (T*)cand, (int)count, per);
+    DTS_CHECK_LAUNCH("dts_candidate_noise_sd_rows");
   });
   return DTS_OK;
 }
@@ -1009,6 +1038,20 @@ extern "C" int dts_ddim_candidates(const void* x, const void* e, const void* z, 
     hipLaunchKernelGGL((ddim_candidates_kernel<T>), dim3(grid1d(count)), dim3(256), 0, st, (const T*)x, (const T*)e, (const T*)z, (T*)prev,
                        (T*)x0_out, alpha_t, alpha_prev, sigma_t, ncand, (long long)count);
     DTS_CHECK_LAUNCH("dts_ddim_candidates");
+  });
+  return DTS_OK;
+}
+extern "C" int dts_ddim_candidates_groups(const void* x, const void* e, const void* z, void* prev, void* x0_out, int dtype, float alpha_t,
+                                          float alpha_prev, float sigma_t, int groups, int ncand, int64_t count, dts_stream s) {
+  DTS_CHECK_ARG(x && e && prev && ncand > 0 && count > 0, "dts_ddim_candidates_groups: bad args");
+  DTS_CHECK_ARG(groups > 0, "dts_ddim_candidates_groups: groups=%d", groups);
+  DTS_CHECK_ARG(alpha_t > 0.f && alpha_t <= 1.f && alpha_prev > 0.f && alpha_prev <= 1.f, "dts_ddim_candidates_groups: alphas out of range");
+  DTS_CHECK_ARG(1.f - alpha_prev - sigma_t * sigma_t >= 0.f, "dts_ddim_candidates_groups: sigma_t too large");
+  ST;
+  DTS_DISPATCH_DTYPE(dtype, {
+    hipLaunchKernelGGL((ddim_candidates_kernel<T, long long>), dim3(grid1d((long long)groups * count)), dim3(256), 0, st, (const T*)x, (const T*)e,
+                       (const T*)z, (T*)prev, (T*)x0_out, alpha_t, alpha_prev, sigma_t, ncand, (long long)count, (long long)groups);
+    DTS_CHECK_LAUNCH("dts_ddim_candidates_groups");
   });
   return DTS_OK;
 }

@@ -1286,6 +1286,41 @@ def candidate_noise_sd(pivot, u, mode, scale):
     return out
 
 
+def candidate_noise_sd_rows(pivot, u, mode, scale, out=None):
+    """candidate_noise_sd for S searches in lock-step: pivot [S,C,H,W], u [S*N,C,H,W] (same dtype, search-major), mode int32 [S*N],
+    scale f32 [S*N,3] -> candidates [S*N,C,H,W] (written into `out` where given); row s*N + n is built from pivot[s] with its own mode and
+    scale.  S = 1 is candidate_noise_sd bit for bit."""
+    s_, rows = pivot.shape[0], u.shape[0]
+    if s_ < 1 or rows % s_ != 0 or tuple(u.shape[1:]) != tuple(pivot.shape[1:]):
+        raise ValueError(f'candidate_noise_sd_rows: u {tuple(u.shape)} is not a whole number of rows per pivot of {tuple(pivot.shape)}')
+    if mode.numel() != rows or tuple(scale.shape) != (rows, 3):
+        raise ValueError(f'candidate_noise_sd_rows: mode must be [{rows}] and scale [{rows}, 3] (rand, lambda, sqrt(numel)), got '
+                         f'{tuple(mode.shape)} / {tuple(scale.shape)}')
+    out = _out('candidate_noise_sd_rows', out, tuple(u.shape), u.dtype, u.device)
+    _call('dts_candidate_noise_sd_rows', _ptr(pivot, 'pivot'), _ptr(u, 'u', pivot.dtype), _ptr(mode, 'mode', torch.int32),
+          _ptr(scale, 'scale', torch.float32), _ptr(out, 'out', pivot.dtype), dt_code(pivot.dtype), s_, rows // s_, pivot[0].numel())
+    return out
+
+
+def ddim_candidates_groups(x, e, z, alpha_t, alpha_prev, sigma_t, ncand=None, want_x0=True, out=None, x0_out=None):
+    """ddim_candidates for G independent (x, e) pairs in one launch: x, e [G, ...]; z [G, ncand, ...] or None (then ncand = 1 unless given)
+    -> (prev [G, ncand, ...], x0 [G, ...] or None), written into `out` / `x0_out` where given.  The scalars are shared by the groups.
+    G = 1 is ddim_candidates bit for bit."""
+    g = x.shape[0]
+    if z is not None:
+        if z.dim() != x.dim() + 1 or z.shape[0] != g or tuple(z.shape[2:]) != tuple(x.shape[1:]) or (ncand is not None and z.shape[1] != ncand):
+            raise ValueError(f'ddim_candidates_groups: z {tuple(z.shape)} is not [G, ncand, ...] over x {tuple(x.shape)}')
+        ncand = z.shape[1]
+    ncand = 1 if ncand is None else int(ncand)
+    if tuple(e.shape) != tuple(x.shape):
+        raise ValueError(f'ddim_candidates_groups: e {tuple(e.shape)} != x {tuple(x.shape)}')
+    prev = _out('ddim_candidates_groups', out, (g, ncand) + tuple(x.shape[1:]), x.dtype, x.device)
+    x0 = _out('ddim_candidates_groups', x0_out, tuple(x.shape), x.dtype, x.device) if want_x0 else None
+    _call('dts_ddim_candidates_groups', _ptr(x), _ptr(e, 'e', x.dtype), _ptr(z, 'z', x.dtype), _ptr(prev, 'out', x.dtype), _ptr(x0, 'x0_out'),
+          dt_code(x.dtype), float(alpha_t), float(alpha_prev), float(sigma_t), g, ncand, x[0].numel() if g else 0)
+    return prev, x0
+
+
 def ddim_candidates(x, e, z, alpha_t, alpha_prev, sigma_t, want_x0=True):
     """x, e: [count] tensors (any shape, same dtype); z: [ncand, *x.shape] or None -> (prev [ncand,*], x0)."""
     ncand = 1 if z is None else z.shape[0]

@@ -30,6 +30,12 @@ tensor, and a beam survivor's latent is one fused DDIM step of replicated inputs
 which every rank computes for all B*N candidates anyway (32 KB each) -- so no broadcast is needed and the collective count is exactly one
 per search decision.  SD MCTS (reference-faithful default) never scores, so there is nothing to shard; `mcts_backprop` runs replicated.
 
+Lock-step (`pipe(..., row_seeds=[s0, s1, ...])`, `_call_rows`): the searches of S seeds as ONE batch, rows search-major, every search on
+its own seed's host stream (sd_streams.SeedStream: what `main.py --backend sd --seed s` draws), selection on the host per search.  The
+candidates of all searches come from one `dts_candidate_noise_sd_rows` launch, every DDIM candidate step from one
+`dts_ddim_candidates_groups` launch (S*B beams x N candidates in the beam search, where the single-search path launches per beam).  MCTS and
+candidate sharding are refused there; bulk.generate_sd_seeds shards seeds.  Without `row_seeds` nothing changes.
+
 Prompt handling (pipeline...:812-814, 976-992, `encode_prompt` :330-460): with a `text_encoder` / `tokenizer` pair the
 pipeline encodes `prompt` and `negative_prompt` itself exactly as `encode_prompt` does; `prompt_embeds` /
 `negative_prompt_embeds` may be passed instead.  Missing `latents` are drawn like `prepare_latents` (:671-690).
@@ -257,13 +263,256 @@ class SDSearchPipeline:
         self._mcts_latents = latents
         return best_reward
 
+    # ---- lock-step searches (row_seeds) ---------------------------------------------------------
+    def _eps_rows(self, x, t, eu, ec, ctx_of, per, g):
+        """CFG noise prediction for the rows of S searches, search-major: row r belongs to search r // per, whose context pair is
+        ctx_of[r // per] of the D pairs in eu / ec.  One 2R-row U-Net call.  A U-Net that announces `takes_context_rows` gets the 2D
+        distinct contexts (negative, then positive) and an int32 row map built once per (rows, prompts); every other U-Net the expanded
+        tensor."""
+        rows, d = x.shape[0], eu.shape[0]
+        own = [ctx_of[r // per] for r in range(rows)]
+        if getattr(self.unet, 'takes_context_rows', False):
+            key = (rows, per, tuple(ctx_of))
+            cmap = self._context_rows.get(key)
+            if cmap is None:
+                cmap = self._context_rows[key] = torch.tensor(own + [d + c for c in own], dtype=torch.int32).to(self.device)
+            out = self.unet(torch.cat([x, x]), t, encoder_hidden_states=torch.cat([eu, ec]), context_rows=cmap, return_dict=False)[0].contiguous()
+        else:
+            idx = torch.tensor(own, dtype=torch.int64, device=eu.device)
+            out = self.unet(torch.cat([x, x]), t, encoder_hidden_states=torch.cat([eu[idx], ec[idx]]), return_dict=False)[0].contiguous()
+        self.unet_rows += 2 * rows
+        return ops.cfg_combine(out[:rows].contiguous(), out[rows:].contiguous(), g)
+
+    def _score_images(self, score_function, u8, prompts):
+        """rewards of quantised images [n,3,H,W], `prompts` one per image: a `batched` scorer gets ONE call -- `prompts=` the one shared
+        prompt, or one entry per image when they differ -- every other scorer the reference's per-image calls (pipeline...:1114)."""
+        n = u8.shape[0]
+        shared = all(p == prompts[0] for p in prompts)
+        if n > 1 and getattr(score_function, 'batched', False):
+            s = score_function(images=[u8[j:j + 1] for j in range(n)], prompts=[prompts[0]] if shared else list(prompts), timesteps=None)
+            self.scorer_calls += 1
+            return [float(v) for v in (s.float().cpu().tolist() if torch.is_tensor(s) else s)]
+        vals = []
+        for j in range(n):
+            s = score_function(images=[u8[j:j + 1]], prompts=[prompts[j]], timesteps=None)
+            self.scorer_calls += 1
+            vals.append(s.item() if torch.is_tensor(s) else float(s))
+        return vals
+
+    def _decode_rows(self, x, decode_rows):
+        """the VAE decode of latents [R,...] in chunks of `decode_rows` rows (None: all at once)"""
+        step = x.shape[0] if decode_rows is None else int(decode_rows)
+        parts = [self.vae.decode(x[lo:lo + step].contiguous() / self.vae.config.scaling_factor, return_dict=False)[0] for lo in range(0, x.shape[0], step)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def _score_rows(self, score_function, x0, row_prompts, decode_rows):
+        """decode + quantise + score the rows, `decode_rows` rows per decode and scorer call (None: all at once) -> the rows' rewards.
+        Chunks change the launch forms, never the values' order or the draws."""
+        rows = x0.shape[0]
+        step = rows if decode_rows is None else int(decode_rows)
+        vals = []
+        for lo in range(0, rows, step):
+            image = self._decode_rows(x0[lo:lo + step], None).float().contiguous()
+            self.decoded += image.shape[0]
+            vals += self._score_images(score_function, ops.quantize_u8(image, f32_math=True), row_prompts[lo:lo + step])
+        return vals
+
+    def _call_rows(self, row_seeds, *, prompt, num_inference_steps, guidance_scale, negative_prompt, eta, latents, prompt_embeds,
+                   negative_prompt_embeds, score_function, method, params, output_type, height, width, decode_rows):
+        """The searches of S seeds in lock-step as ONE batch: `pipe(..., row_seeds=[s0, s1, ...]) -> (output, [max_score] * S)`.
+
+        Search k draws from its own `torch.Generator().manual_seed(row_seeds[k])` (sd_streams.SeedStream) what `main.py --backend sd --seed`
+        draws from the global generator: the float32 latents [1,C,h,w] first (only when `latents` is None), then the loop's draws in the
+        reference's order and in the latents' dtype -- so a seed's search is the one it runs alone, whatever its companions.  Rows are
+        search-major everywhere (naive 1 row per search, eps-greedy / zero-order N, beam B*N, rejection N); selection stays on the host per
+        search (first maximum, stable sort).  The candidates of all searches come from ONE `dts_candidate_noise_sd_rows` launch and every
+        DDIM candidate step from ONE `dts_ddim_candidates_groups` launch; the U-Net sees all rows in one call, the decoder and the scorer
+        `decode_rows` rows at a time (None: all).  `method='rejection'` (the reference's main.py:134 loop: N naive trajectories on one
+        stream) pre-draws a seed's N trajectories in that order and runs them as rows; best of N, ties to the first.
+
+        latents [S,C,H,W] or None; prompt a string or a list of 1 or S strings; prompt_embeds / negative_prompt_embeds 1 or S rows.
+        output: images / latents [S,...], scores / max_scores / searches per search, unet_rows / decoded / scorer_calls as totals."""
+        from .sd_streams import SeedStream
+        seeds = [int(s) for s in row_seeds]
+        S = len(seeds)
+        if S < 1:
+            raise ValueError('row_seeds: need at least one seed')
+        if method == 'mcts':
+            raise ValueError("row_seeds: method 'mcts' is not supported (with or without mcts_backprop: its trees are ragged per search)")
+        if method not in ('naive', 'eps_greedy', 'zero_order', 'beam', 'rejection'):
+            raise ValueError(f'row_seeds: unknown method {method!r}')
+        if not self.shards.solo:
+            raise ValueError('row_seeds: candidate sharding over more than one rank is not supported (shards=CandidateShards(enabled=False): '
+                             'lock-step batches go with seed sharding)')
+        if decode_rows is not None and int(decode_rows) < 1:
+            raise ValueError(f'decode_rows: a positive number of rows per VAE decode, got {decode_rows}')
+        if prompt is not None and prompt_embeds is not None:
+            raise ValueError(f'Cannot forward both `prompt`: {prompt} and `prompt_embeds`. Please make sure to only forward one of the two.')
+        prompts = None
+        if prompt is not None:
+            prompts = [prompt] if isinstance(prompt, str) else list(prompt)
+            if len(prompts) not in (1, S):
+                raise ValueError(f'row_seeds: prompt: need 1 or {S} prompts (one per seed), got {len(prompts)}')
+        if prompt_embeds is None or negative_prompt_embeds is None:
+            if prompts is None:
+                raise ValueError('pass `prompt` (with a text_encoder/tokenizer in the pipeline) or prompt_embeds + negative_prompt_embeds')
+            shared_negative = negative_prompt is None or isinstance(negative_prompt, str)
+            distinct = list(dict.fromkeys(prompts)) if shared_negative else prompts      # each distinct prompt is encoded once
+            pe, ne = self.encode_prompt(distinct, negative_prompt)
+            ctx_of = [distinct.index(p) if shared_negative else k for k, p in enumerate(prompts)] * (S // len(prompts))
+            prompt_embeds = pe if prompt_embeds is None else prompt_embeds
+            negative_prompt_embeds = ne if negative_prompt_embeds is None else negative_prompt_embeds
+        else:
+            ctx_of = None
+        d = prompt_embeds.shape[0]
+        if negative_prompt_embeds.shape[0] != d:
+            raise ValueError(f'row_seeds: prompt_embeds has {d} rows, negative_prompt_embeds {negative_prompt_embeds.shape[0]}')
+        if ctx_of is None or max(ctx_of) >= d:                                # embeddings given: one pair for all, or one per seed
+            if d not in (1, S):
+                raise ValueError(f'row_seeds: prompt_embeds: need 1 or {S} rows (one per seed), got {d}')
+            ctx_of = [0] * S if d == 1 else list(range(S))
+        search_prompts = [None] * S if prompts is None else prompts * (S // len(prompts))
+
+        sch, dev = self.scheduler, self.device
+        dtype = getattr(self.unet, 'dtype', torch.float32)
+        eu, ec = self._up(negative_prompt_embeds, dtype), self._up(prompt_embeds, dtype)
+        timesteps = sch.set_timesteps(num_inference_steps)
+        nT = len(timesteps)
+        g = float(guidance_scale)
+        rejection = method == 'rejection'
+        if latents is not None:
+            if rejection:
+                raise ValueError("row_seeds: method 'rejection' draws the latents of its N trajectories itself: pass latents=None")
+            if latents.dim() != 4 or latents.shape[0] != S:
+                raise ValueError(f'row_seeds: latents: need [{S}, C, H, W] (one row per seed), got {tuple(latents.shape)}')
+            shape = (1,) + tuple(latents.shape[1:])
+        else:
+            cfgu = self.unet.config
+            vsf = 2 ** (len(getattr(self.vae.config, 'block_out_channels', [0] * 4)) - 1)
+            shape = (1, cfgu.in_channels, (height // vsf) if height else cfgu.sample_size, (width // vsf) if width else cfgu.sample_size)
+        streams = [SeedStream(s, shape, dtype) for s in seeds]
+        self.unet_rows = self.decoded = self.scorer_calls = 0
+        scores = [[] for _ in range(S)]
+        stack = lambda parts: self._up(torch.cat(parts), dtype)               # host [1,...] / [n,...] pieces, search-major -> device rows
+
+        def per_search(vals, per):
+            return [vals[k * per:(k + 1) * per] for k in range(S)]
+
+        def step_rows(x, e, z_rows, t):
+            """the DDIM step of every row with its own noise: one launch, G = rows groups of one candidate"""
+            a_t, a_p, sig = sch.coefficients(t, eta)
+            prev, _ = ops.ddim_candidates_groups(x, e, z_rows.reshape(x.shape[0], 1, *x.shape[1:]), a_t, a_p, sig, want_x0=False)
+            return prev.reshape(x.shape)
+
+        def evaluate(x, e, cands, per, t):
+            """cands [R*per,...] search-major over the R rows of (x, e) -> (candidate latents [R*per,...], rewards): steps 1083-1114"""
+            a_t, a_p, sig = sch.coefficients(t, eta)
+            prev, _ = ops.ddim_candidates_groups(x, e, cands.reshape(x.shape[0], per, *x.shape[1:]), a_t, a_p, sig, want_x0=False)
+            lat_c = prev.reshape(x.shape[0] * per, *x.shape[1:])
+            rows_per_search = lat_c.shape[0] // S
+            np2 = self._eps_rows(lat_c, t, eu, ec, ctx_of, rows_per_search, g)           # same t, not t-1 (:1090)
+            _, x0 = ops.ddim_candidates_groups(lat_c, np2, None, a_t, a_p, sig, want_x0=True)
+            vals = self._score_rows(score_function, x0, [search_prompts[r // rows_per_search] for r in range(lat_c.shape[0])], decode_rows)
+            return lat_c, vals
+
+        max_scores = [None] * S
+        per_final = 1
+        if rejection:
+            N = params['N']
+            trajs = [st.rejection_trajectories(N, nT) for st in streams]       # [S][N] of (latents, [nT] noises), pre-drawn in stream order
+            x = stack([lat * sch.init_noise_sigma for tr in trajs for lat, _ in tr])
+            for i, t in enumerate(timesteps):
+                e = self._eps_rows(x, t, eu, ec, ctx_of, N, g)
+                x = step_rows(x, e, stack([zs[i] for tr in trajs for _, zs in tr]), t)
+            per_final = N
+        else:
+            if latents is None:
+                latents = torch.cat([st.latents() for st in streams])
+            x = self._up(latents * sch.init_noise_sigma, dtype)
+            if method == 'beam':
+                B, N = params['B'], params['N']
+                x = x.repeat_interleave(B, dim=0)                              # [S*B,...]: every search starts with B copies (:1047)
+                for i, t in enumerate(timesteps):
+                    e = self._eps_rows(x, t, eu, ec, ctx_of, B, g)
+                    cands = stack([st.beam_round(N) for st in streams for _ in range(B)])     # per search, per beam: the reference's order
+                    lat_all, vals = evaluate(x, e, cands, N, t)                # [S*B*N,...], (search, beam, candidate)-major
+                    keep = []
+                    for k, v in enumerate(per_search(vals, B * N)):
+                        scores[k] += v
+                        order = sorted(range(B * N), key=lambda j: v[j], reverse=True)        # stable: first wins ties (:1132)
+                        keep += [k * B * N + j for j in order[:B]]
+                    x = lat_all[torch.tensor(keep, dtype=torch.int64, device=dev)].contiguous()
+                per_final = B
+            else:
+                for i, t in enumerate(timesteps):
+                    e = self._eps_rows(x, t, eu, ec, ctx_of, 1, g)
+                    pivot = stack([st.randn() for st in streams])              # :1366
+                    if method in ('eps_greedy', 'zero_order'):
+                        N = params['N']
+                        thr = params['eps'] if method == 'eps_greedy' else 0.0
+                        for _ in range(params['K']):
+                            rounds = [st.local_round(N, thr, params['lambda']) for st in streams]
+                            mode = torch.tensor([m for _, ms, _ in rounds for m in ms], dtype=torch.int32, device=dev)
+                            scale = torch.tensor([s_ for _, _, sc in rounds for s_ in sc], dtype=torch.float32, device=dev)
+                            cands = ops.candidate_noise_sd_rows(pivot, stack([u.reshape(N, *shape[1:]) for u, _, _ in rounds]), mode, scale)
+                            _, vals = evaluate(x, e, cands, N, t)
+                            best = []
+                            for k, v in enumerate(per_search(vals, N)):
+                                scores[k] += v
+                                max_scores[k] = max(v)
+                                best.append(k * N + v.index(max_scores[k]))     # first max (:1432-1433)
+                            pivot = cands[torch.tensor(best, dtype=torch.int64, device=dev)].contiguous()
+                    x = step_rows(x, e, pivot, t)
+        # beam: the beams' own latents are decoded and scored (:1157-1170), the winner is decoded for the output; naive / rejection: the
+        # final image is what is scored (:1457-1485, main.py:134-140).  Best per search, ties to the first
+        final_prompts = [search_prompts[r // per_final] for r in range(x.shape[0])]
+        image = None
+        if method == 'beam':
+            finals = self._score_rows(score_function, x, final_prompts, decode_rows)
+        elif method in ('naive', 'rejection'):
+            image = self._decode_rows(x, decode_rows)
+            finals = self._score_images(score_function, ops.quantize_u8(image.float().contiguous(), f32_math=True), final_prompts)
+        if method in ('beam', 'naive', 'rejection'):
+            win = []
+            for k, v in enumerate(per_search(finals, per_final)):
+                scores[k] += v
+                max_scores[k] = max(v)
+                win.append(k * per_final + v.index(max_scores[k]))
+            win = torch.tensor(win, dtype=torch.int64, device=dev)
+            x = x[win].contiguous()
+            image = None if image is None else image[win].contiguous()
+        if image is None:
+            image = self._decode_rows(x, decode_rows)
+        if output_type == 'latent':
+            images = x
+        elif output_type == 'pt':
+            images = (image / 2 + 0.5).clamp(0, 1)
+        else:
+            import PIL.Image
+            arr = ((image / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).float().cpu().numpy() * 255).round().astype('uint8')
+            images = [PIL.Image.fromarray(a) for a in arr]
+        searches = [types.SimpleNamespace(seed=seeds[k], images=images[k:k + 1], latents=x[k:k + 1], scores=scores[k], max_score=max_scores[k],
+                                          prompt=search_prompts[k]) for k in range(S)]
+        out = types.SimpleNamespace(images=images, nsfw_content_detected=None, latents=x, scores=scores, max_scores=max_scores,
+                                    searches=searches, row_seeds=seeds, unet_rows=self.unet_rows, decoded=self.decoded,
+                                    scorer_calls=self.scorer_calls, collectives=0)
+        return out, max_scores
+
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt=None, num_inference_steps=100, guidance_scale=7.5, negative_prompt=None, eta=1.0, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, score_function: Optional[Callable] = None, method='eps_greedy',
-                 params=None, output_type='pt', height=None, width=None):
+                 params=None, output_type='pt', height=None, width=None, row_seeds=None, decode_rows=None):
         """Keyword surface of the reference call (pipeline...:785-817) for the arguments the search path uses:
-        `pipe(prompt=..., num_inference_steps=..., score_function=..., method=..., params=...) -> (output, max_score)`."""
+        `pipe(prompt=..., num_inference_steps=..., score_function=..., method=..., params=...) -> (output, max_score)`.
+        row_seeds=[s0, s1, ...] (this build's keyword) runs the searches of those seeds in lock-step as one batch: see `_call_rows`."""
+        if row_seeds is not None:
+            return self._call_rows(row_seeds, prompt=prompt, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                   negative_prompt=negative_prompt, eta=eta, latents=latents, prompt_embeds=prompt_embeds,
+                                   negative_prompt_embeds=negative_prompt_embeds, score_function=score_function, method=method,
+                                   params=params, output_type=output_type, height=height, width=width, decode_rows=decode_rows)
+        if decode_rows is not None:
+            raise ValueError('decode_rows goes with row_seeds (the lock-step search loop)')
         if prompt is not None and prompt_embeds is not None:                  # check_inputs (:657-661)
             raise ValueError(f'Cannot forward both `prompt`: {prompt} and `prompt_embeds`. Please make sure to only forward one of the two.')
         if prompt_embeds is None or negative_prompt_embeds is None:

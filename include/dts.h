@@ -42,7 +42,7 @@ enum dts_dtype { DTS_F32 = 0, DTS_BF16 = 1, DTS_F16 = 2,
                  DTS_F16X3 = 3 };
 enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNSUPPORTED = -3 };
 
-#define DTS_ABI_VERSION 124        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
+#define DTS_ABI_VERSION 125        /* bumped with every change of a signature or of dts_conv_args (101: ev_start/ev_stop; 102: tuning knobs; 103: dts_cosine_rows; 104: dts_nchw_to_nhwc_pad,
                                      105: dts_conv_args.gn_coef / gn_silu, dts_conv_fuses_gn;
                                      head dim 512 in dts_attention; 106: dts_conv_kernel, 128-cout ping-pong blocks; 107: dts_resample_u8, dts_lut_u8_f32; 108: DTS_F16X3, dts_conv_args.acc_scale, dts_split3_f16, dts_gn_apply_x3, dts_split2_f16, dts_attention_x3;
                                      109: dts_candidate_noise_sd; the DTS_F16X3 operand images are 2*C wide, interleaved per 32 channels; dts_gn_apply_x3 raw_out;
@@ -60,7 +60,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      121: dts_precond_in (the VP, VE and iDDPM preconditioners);
                                      122: dts_attention_x3_masked, dts_text_tokens_f32 (the CLIP text tower in DTS_F16X3);
                                      123: dts_ode_xhat, dts_ode_slope, dts_ode_correct (the general ODE step of the ablation sampler);
-                                     124: dts_candidate_noise_rows (mode / scale per output row: searches of several seeds in lock-step)) */
+                                     124: dts_candidate_noise_rows (mode / scale per output row: searches of several seeds in lock-step);
+                                     125: dts_candidate_noise_sd_rows, dts_ddim_candidates_groups (the SD backend's searches of several seeds in lock-step)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -448,6 +449,12 @@ int dts_candidate_noise_rows(const double* pivot, const double* g, const int32_t
  * the reference's three tensor-by-scalar products, each rounded to `dtype` (:1377-1379).  pivot [count], scale [n][3]. */
 int dts_candidate_noise_sd(const void* pivot, const void* u, const int32_t* mode, const float* scale, void* cand, int dtype, int n,
                            int64_t count, dts_stream s);
+/* The same body for `searches` searches of `per` candidates each in lock-step (pipeline_stable_diffusion.py:1371-1379, once per search):
+ * pivot [searches][count], u / cand [searches * per][count], mode [searches * per], scale [searches * per][3]; candidate row
+ * r = s * per + n reads pivot[s], mode[r] and scale[3r..].  One block per row, the norm over that row's count values in the same reduction
+ * order and with the same roundings, so searches == 1 is dts_candidate_noise_sd bit for bit. */
+int dts_candidate_noise_sd_rows(const void* pivot, const void* u, const int32_t* mode, const float* scale, void* cand, int dtype,
+                                int searches, int per, int64_t count, dts_stream s);
 
 /* ---- K13: DDIM candidate step, SD backend (scheduling_ddim.py:402-463), eta*std = sigma_t ---------- */
 /* For i in [0,count): x0 = (x - sqrt(1-a_t) e)/sqrt(a_t); [e' = (x - sqrt(a_t) x0)/sqrt(1-a_t) == e];
@@ -457,6 +464,12 @@ int dts_candidate_noise_sd(const void* pivot, const void* u, const int32_t* mode
 int dts_cfg_combine(const void* uncond, const void* cond, float guidance, void* out, int dtype, int64_t count, dts_stream s);
 int dts_ddim_candidates(const void* x, const void* e, const void* z, void* prev, void* x0_out, int dtype,
                         float alpha_t, float alpha_prev, float sigma_t, int ncand, int64_t count, dts_stream s);
+/* The same step (scheduling_ddim.py:402-463) for `groups` independent (x, e) pairs with ncand candidates each, in one launch: the beams of
+ * the SD beam search (pipeline_stable_diffusion.py:1077-1088) and the searches of several seeds in lock-step.  x / e / x0_out
+ * [groups][count], z / prev [groups][ncand][count] (group-major, as the host draws arrive); z NULL as above, x0_out NULL to skip it.  The
+ * three scalars are shared: lock-step searches sit at one timestep.  groups == 1 is dts_ddim_candidates bit for bit. */
+int dts_ddim_candidates_groups(const void* x, const void* e, const void* z, void* prev, void* x0_out, int dtype,
+                               float alpha_t, float alpha_prev, float sigma_t, int groups, int ncand, int64_t count, dts_stream s);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,10 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
     --search-batch S: bulk mode: the searches of S seeds run in lock-step as ONE batch (S x the rows per denoiser call; every image draws
                   from its own seed's stream, so a seed's search does not depend on its companions; default 1; --method mcts runs per seed)
+                  --backend sd: the same flags (--seeds --outdir [--subdirs] [--search-batch S]); seed s draws what `--seed s` draws, --method
+                  rejection runs its N naive trajectories as N rows per seed, and `--decode-rows R` caps the rows per VAE decode and scorer
+                  call (at [n,3,512,512] the decoder needs it for large S x N)
+    python main.py --backend sd --scorer clip --method eps_greedy --N 4 --K 2 --unet hip --seeds 0-63 --search-batch 8 --decode-rows 16 --outdir out
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`; the N candidates of every
 search iteration are sharded across the ranks (diffusion_tts_amd/parallel.py).
 """
@@ -176,8 +180,19 @@ def main_sd(args):
                         jpeg_codec=getattr(args, 'jpeg_codec', 'pil'), clip_tower_dtype=getattr(args, 'clip_tower_dtype', 'f16'),
                         clip_text_tower=getattr(args, 'clip_text_tower', 'transformers'),
                         clip_text_tower_dtype=getattr(args, 'clip_text_tower_dtype', None))
-    pipe = SDSearchPipeline(unet, vae, device=dev, text_encoder=te, tokenizer=tok)     # encodes the prompt itself (pipeline...:976-992)
     params = {'N': args.N, 'lambda': args.lambda_, 'eps': args.eps, 'K': args.K, 'B': args.B, 'S': args.S}
+    if getattr(args, 'seeds', None) is not None:                               # bulk mode: the SEEDS are split over the ranks, whole searches per rank
+        from diffusion_tts_amd.bulk import generate_sd_seeds
+        from diffusion_tts_amd.parallel import CandidateShards
+        pipe = SDSearchPipeline(unet, vae, device=dev, text_encoder=te, tokenizer=tok, shards=CandidateShards(enabled=False))
+        done = generate_sd_seeds(pipe, args.prompt, args.seeds, args.outdir, method=args.method, params=params, search_batch=args.search_batch,
+                                 num_inference_steps=50, score_function=scorer, subdirs=args.subdirs, decode_rows=args.decode_rows)
+        print(f'[SD] rank {os.environ.get("RANK", "0")}: {len(done)} images -> {args.outdir}')
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return done
+    pipe = SDSearchPipeline(unet, vae, device=dev, text_encoder=te, tokenizer=tok)     # encodes the prompt itself (pipeline...:976-992)
     torch.manual_seed(args.seed)                                                       # same host RNG stream on every rank
     best, best_score = None, float('-inf')
     for _ in range(params['N'] if args.method == 'rejection' else 1):          # reference main.py:134
@@ -249,8 +264,25 @@ def build_parser():
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')
     parser.add_argument('--search-batch', type=int, default=1,
                         help='bulk mode: run the searches of this many seeds in lock-step as one batch (default 1; mcts: one search per seed)')
+    parser.add_argument('--decode-rows', dest='decode_rows', type=int, default=None,
+                        help='SD backend, bulk mode: at most this many rows per VAE decode and scorer call (default: all rows of a batch at once)')
     parser.add_argument('--class', dest='class_idx', type=int, default=None, help='bulk mode: class label (default: per-seed random)')
     return parser
+
+
+def check_bulk_args(args):
+    """the bulk-mode flags that only go together: raised before anything is loaded"""
+    if args.seeds is not None and args.search_batch < 1:
+        raise ValueError(f'--search-batch: a positive number of seeds per lock-step batch, got {args.search_batch}')
+    if args.decode_rows is not None:
+        if args.backend != 'sd':
+            raise ValueError('--decode-rows is an SD option (the rows per VAE decode of a lock-step batch)')
+        if args.seeds is None:
+            raise ValueError('--decode-rows goes with --seeds (the SD bulk mode)')
+        if args.decode_rows < 1:
+            raise ValueError(f'--decode-rows: a positive number of rows per VAE decode, got {args.decode_rows}')
+    if args.backend == 'sd' and args.seeds is not None and args.output is not None:
+        raise ValueError('--output names the one image of a single search; bulk mode (--seeds) writes <outdir>/<seed:06d>.png')
 
 
 def main(argv=None):
@@ -260,6 +292,7 @@ def main(argv=None):
         raise ValueError('imagenet scorer is only available for edm backend')
     if args.backend == 'edm' and args.scorer == 'clip':
         raise ValueError('clip scorer is only available for sd backend')
+    check_bulk_args(args)
     if args.backend == 'sd':
         if getattr(args, 'beam', 'reference') != 'reference':
             print(f'[SD] --beam {args.beam} is an EDM option: ignored (--method beam runs on the SD backend as it is)')
