@@ -43,6 +43,21 @@ def rank_batches(seeds: Iterable[int], max_batch_size: int, rank: int, world: in
     return torch.as_tensor(seeds, dtype=torch.int64).tensor_split(num_batches)[rank::world]
 
 
+def rank_world(rank=None, world=None):
+    """(rank, world) as given; where either is missing, torch.distributed's when it is initialised, else (0, 1)"""
+    if rank is None or world is None:
+        dist_on = dist.is_available() and dist.is_initialized()
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+    return rank, world
+
+
+def seed_png_path(outdir, seed, subdirs=False):
+    """<outdir>/<seed:06d>.png (`subdirs`: one directory per 1000 seeds), its directory created"""
+    image_dir = os.path.join(outdir, f'{seed - seed % 1000:06d}') if subdirs else outdir
+    os.makedirs(image_dir, exist_ok=True)
+    return os.path.join(image_dir, f'{seed:06d}.png')
+
+
 def seed_inputs(seed: int, net, class_idx: Optional[int] = None):
     g = torch.Generator().manual_seed(int(seed))
     latents = torch.randn([1, net.img_channels, net.img_resolution, net.img_resolution], generator=g)
@@ -84,9 +99,7 @@ def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAI
     batches: up to the launch forms the row count selects).  One PNG per seed; each seed's dict is its slice of the call's (image_result).
     MCTS, and calls with forced_selections / precomputed_noise (per search by nature), run one `seed=` call per seed as before.
     `max_batch_size` is accepted for the reference's signature; the split is by `search_batch`."""
-    if rank is None or world is None:
-        dist_on = dist.is_available() and dist.is_initialized()
-        rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+    rank, world = rank_world(rank, world)
     if int(search_batch) < 1:
         raise ValueError(f'search_batch: a positive number of seeds per lock-step batch, got {search_batch}')
     net = load_network(network, device=device, dtype=compute_dtype)
@@ -94,11 +107,6 @@ def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAI
         sampler_kwargs.get(k) is not None for k in ('forced_selections', 'precomputed_noise'))
     local_search = sampling_method in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER)
     done = {}
-
-    def png_path(seed):
-        image_dir = os.path.join(outdir, f'{seed - seed % 1000:06d}') if subdirs else outdir
-        os.makedirs(image_dir, exist_ok=True)
-        return os.path.join(image_dir, f'{seed:06d}.png')
 
     for batch in rank_batches(parse_int_list(seeds), int(search_batch), rank, world):
         batch = batch.tolist()
@@ -109,22 +117,15 @@ def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAI
                       compute_dtype=compute_dtype, verbose=verbose, shard_candidates=False, **sampler_kwargs)
         if not lock_step:
             for seed, (latents, labels) in zip(batch, inputs):
-                done[seed] = generate_image_grid(net, png_path(seed), latents, labels, seed=seed, **common)
+                done[seed] = generate_image_grid(net, seed_png_path(outdir, seed, subdirs), latents, labels, seed=seed, **common)
             continue
         latents = torch.cat([lat for lat, _ in inputs], dim=0)
         labels = None if inputs[0][1] is None else torch.cat([lab for _, lab in inputs], dim=0)
         res = generate_image_grid(net, None, latents, labels, row_seeds=batch, **common)
         for b, seed in enumerate(batch):
             done[seed] = image_result(res, b, len(batch), local_search)
-            save_image(done[seed]['image'][0].permute(1, 2, 0).contiguous().numpy(), png_path(seed))
+            save_image(done[seed]['image'][0].permute(1, 2, 0).contiguous().numpy(), seed_png_path(outdir, seed, subdirs))
     return done
-
-
-def seed_png_path(outdir, seed, subdirs=False):
-    """<outdir>/<seed:06d>.png (`subdirs`: one directory per 1000 seeds), its directory created"""
-    image_dir = os.path.join(outdir, f'{seed - seed % 1000:06d}') if subdirs else outdir
-    os.makedirs(image_dir, exist_ok=True)
-    return os.path.join(image_dir, f'{seed:06d}.png')
 
 
 @torch.no_grad()
@@ -138,9 +139,7 @@ def generate_sd_seeds(pipe, prompt, seeds, outdir, *, method='naive', params=Non
     rows per seed; `method='mcts'` (ragged trees) runs one single-search call per seed after `torch.manual_seed(seed)`.  decode_rows caps the
     rows per VAE decode.  pipe_kwargs (prompt_embeds=, negative_prompt_embeds=, guidance_scale=, eta=, ...) go to the call.
     Returns {seed: maximum score} for the seeds this rank generated."""
-    if rank is None or world is None:
-        dist_on = dist.is_available() and dist.is_initialized()
-        rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+    rank, world = rank_world(rank, world)
     if int(search_batch) < 1:
         raise ValueError(f'search_batch: a positive number of seeds per lock-step batch, got {search_batch}')
     params = {} if params is None else params
@@ -222,9 +221,7 @@ def generate_images(network, seeds, outdir, *, class_idx: Optional[int] = None, 
     generator, quantised by ops.quantize_u8 and written as `<outdir>/<seed:06d>.png`.  rank / world default to torch.distributed's when it is
     initialised, else 0 / 1; no collective is used.  `sampler_fn(net, latents, labels, randn_like=..., **kwargs)` replaces the choice of
     sampler.  Returns {seed: uint8 image [c, h, w] (CPU)} for the seeds this rank generated."""
-    if rank is None or world is None:
-        dist_on = dist.is_available() and dist.is_initialized()
-        rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+    rank, world = rank_world(rank, world)
     net = load_network(network, device=device, dtype=compute_dtype)
     picked, kw = pick_sampler(sampler_kwargs)
     sampler_fn = picked if sampler_fn is None else sampler_fn
@@ -237,8 +234,6 @@ def generate_images(network, seeds, outdir, *, class_idx: Optional[int] = None, 
         x = sampler_fn(net, latents, labels, randn_like=rnd.randn_like, **kw)
         images = ops.quantize_u8(x).cpu()
         for seed, image in zip(batch_seeds, images):
-            image_dir = os.path.join(outdir, f'{seed - seed % 1000:06d}') if subdirs else outdir
-            os.makedirs(image_dir, exist_ok=True)
-            save_image(image.permute(1, 2, 0).contiguous().numpy(), os.path.join(image_dir, f'{seed:06d}.png'))
+            save_image(image.permute(1, 2, 0).contiguous().numpy(), seed_png_path(outdir, seed, subdirs))
             done[seed] = image
     return done

@@ -1,9 +1,10 @@
-"""Per-seed host random streams of the SD backend's lock-step searches (sd_pipeline.SDSearchPipeline(row_seeds=...)).
+"""Host random streams of the SD backend's search loop (sd_pipeline.SDSearchPipeline): one per search.
 
-One `torch.Generator().manual_seed(s)` per search: its stream is the global CPU generator's after `torch.manual_seed(s)`, so the draws of seed
-s in any batch are the draws of `main.py --backend sd --seed s` -- first the float32 latents [1,C,h,w] (main.py's own draw, made here only
-when the caller passes none), then everything the reference's loop draws, in the reference's order and in the latents' dtype
-(pipeline_stable_diffusion.py:1080, 1109, 1366-1379, 1410; scheduling_ddim.py:457-460).  Host tensors only: nothing here needs a GPU."""
+A seed `s` gives a `torch.Generator().manual_seed(s)`: its stream is the global CPU generator's after `torch.manual_seed(s)`, so the draws of
+seed s in any batch are the draws of `main.py --backend sd --seed s` -- first the float32 latents [1,C,h,w] (main.py's own draw, made here
+only when the caller passes none), then everything the reference's loop draws, in the reference's order and in the latents' dtype
+(pipeline_stable_diffusion.py:1080, 1109, 1366-1379, 1410; scheduling_ddim.py:457-460).  `seed=None` is the global CPU generator itself, as
+it stands: the single search of a call without `row_seeds`.  Host tensors only: nothing here needs a GPU."""
 import numpy as np
 import torch
 
@@ -13,8 +14,8 @@ class SeedStream:
     another stream than a float32 draw rounded to float16, so every loop draw is made in `dtype`, as the reference's `randn_like` does)."""
 
     def __init__(self, seed, shape, dtype):
-        self.seed = int(seed)
-        self.gen = torch.Generator().manual_seed(self.seed)
+        self.seed = None if seed is None else int(seed)
+        self.gen = None if seed is None else torch.Generator().manual_seed(self.seed)      # None: torch's global generator, not reseeded
         self.shape, self.dtype = tuple(shape), dtype
 
     def latents(self):

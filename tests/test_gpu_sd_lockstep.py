@@ -15,8 +15,9 @@ seed it uses is checkable, so nothing passes by being left out.  Seeds (scanned 
   zero-order (N=3, K=2): every candidate is a short step from the pivot, so the gaps scale with lambda; at lambda=0.15 NO seed of 0..599 has
     all 8 decisions above the margin (best: 3.0e-5).  The test therefore runs zero-order at lambda=1.0: seeds 61, 85, 98, 112 (>= 5.7e-5).
   rejection (N=3): 1, 4, 5 (gaps > 2e-2); naive makes no decision: 1, 2, 3.
-Against this build's own solo runs (`row_seeds=[s]`, and the unchanged `pipe(latents=[1,...])` after torch.manual_seed(s)) the selections are
-identical and the values within 4e-5 (both are within 2e-5 of the oracle)."""
+Against this build's own solo run (`row_seeds=[s]`) the selections are identical and the values within 4e-5 (both are within 2e-5 of the
+oracle).  The single call (`pipe(latents=[1,...])` after torch.manual_seed(s)) IS the one-seed lock-step call on the global generator: equal
+bit for bit, and it leaves the global generator where the oracle leaves it."""
 import types
 
 import numpy as np
@@ -62,7 +63,7 @@ def oracle(method, seed, pe=PE, ne=NE, tag=0):
         finals = [float(r['max_score']) for r in runs]
         best = runs[finals.index(max(finals))]
         _ORACLE[key] = dict(scores=[v for r in runs for v in r['scores']], unet_rows=sum(r['unet_rows'] for r in runs), max_score=max(finals),
-                            image=(best['image'] / 2 + 0.5).clamp(0, 1))
+                            image=(best['image'] / 2 + 0.5).clamp(0, 1), rng_state=torch.get_rng_state())
     return _ORACLE[key]
 
 
@@ -155,7 +156,7 @@ def test_lockstep_batch_matches_the_oracle_seed_by_seed(pipe, method):
 
 @pytest.mark.parametrize('method', METHODS)
 def test_a_seed_in_a_batch_equals_its_solo_runs(pipe, method):
-    """row_seeds=[s] alone, and the unchanged single-search call after torch.manual_seed(s): identical selections, values within 4e-5"""
+    """row_seeds=[s] alone: identical selections, values within 4e-5; the single call after torch.manual_seed(s): equal to row_seeds=[s]"""
     out, _ = batch(pipe, method)
     for k, seed in enumerate(SEEDS[method][:2]):
         solo, solo_max = run(pipe, method, [seed])
@@ -169,11 +170,48 @@ def test_a_seed_in_a_batch_equals_its_solo_runs(pipe, method):
         lat = torch.randn(1, 4, 8, 8)
         one, one_max = pipe(prompt_embeds=PE, negative_prompt_embeds=NE, latents=lat, num_inference_steps=STEPS, score_function=ListBrightness(),
                             method=method, params=PARAMS[method], output_type='pt')
-        assert decisions(method, one.scores)[0] == decisions(method, out.scores[k])[0]
-        assert float(np.abs(np.array(one.scores) - np.array(out.scores[k])).max()) < MARGIN
-        assert float((one.images - out.images[k:k + 1]).abs().max()) < MARGIN
-        assert abs(float(one_max) - float(out.max_scores[k])) < MARGIN
+        assert one.scores == solo.scores[0]
+        assert torch.equal(one.images, solo.images)
+        assert float(one_max) == float(solo_max[0])
         assert one.unet_rows == solo.unet_rows and one.decoded == solo.decoded
+
+
+def assert_same_search(one, one_max, solo, solo_max):
+    """the single call's result against the one-seed lock-step call's: the same search, bit for bit, counted alike"""
+    assert one.scores == solo.scores[0]
+    assert torch.equal(one.latents, solo.latents) and torch.equal(one.images, solo.images)
+    assert isinstance(one_max, float) and float(one_max) == float(solo_max[0])
+    assert (one.unet_rows, one.decoded, one.scorer_calls) == (solo.unet_rows, solo.decoded, solo.scorer_calls)
+    assert sorted(vars(one)) == ['collectives', 'decoded', 'images', 'latents', 'nsfw_content_detected', 'scorer_calls', 'scores', 'unet_rows']
+
+
+@pytest.mark.parametrize('method', ['naive', 'eps_greedy', 'zero_order', 'beam'])
+def test_the_single_call_is_the_one_seed_lockstep_call(pipe, method):
+    """`torch.manual_seed(s); pipe(...)` without row_seeds is `pipe(row_seeds=[s], ...)` on the global generator, bit for bit, in each form
+    of passing the latents.  A seed's stream starts with main.py's latent draw unless the lock-step call is GIVEN latents (then it starts
+    at the loop's first draw, test_latents_given_per_seed), so each single call is paired with the lock-step call whose stream it is:
+      main.py's call -- seed, draw `lat`, pipe(latents=lat) -- with row_seeds=[s] drawing the same latents itself;
+      seed, pipe(latents=lat) with row_seeds=[s], latents=lat (no latent draw on either stream);
+      seed, pipe(latents=None) with row_seeds=[s] (the stand-in U-Net is float32, so prepare_latents' draw is main.py's float32 draw).
+    The single call leaves the global generator where the oracle's run from the same seed and latents leaves it: the count of draws, the
+    dropped variance noises after the last decision included, which no score can see."""
+    kw = dict(prompt_embeds=PE, negative_prompt_embeds=NE, num_inference_steps=STEPS, score_function=ListBrightness(), method=method,
+              params=PARAMS[method], output_type='pt')
+    for seed in SEEDS[method][:2]:
+        want = oracle(method, seed)
+        drawing = run(pipe, method, [seed])
+        torch.manual_seed(seed)
+        lat = torch.randn(1, 4, 8, 8)
+        one, one_max = pipe(latents=lat.clone(), **kw)
+        assert torch.equal(torch.get_rng_state(), want['rng_state']), (method, seed)
+        assert_same_search(one, one_max, *drawing)
+        torch.manual_seed(seed)
+        given, given_max = pipe(latents=lat.clone(), **kw)
+        assert_same_search(given, given_max, *run(pipe, method, [seed], latents=lat.clone()))
+        torch.manual_seed(seed)
+        drawn, drawn_max = pipe(latents=None, **kw)
+        assert torch.equal(torch.get_rng_state(), want['rng_state']), (method, seed)
+        assert_same_search(drawn, drawn_max, *drawing)
 
 
 @pytest.mark.parametrize('method', METHODS)

@@ -138,13 +138,13 @@ def test_the_pipeline_passes_the_row_map(gold, monkeypatch):
     real = ops.group_rows
     monkeypatch.setattr(ops, 'group_rows', lambda v: (calls.append(tuple(v.shape)), real(v))[1])
     pipe = SDSearchPipeline(unet, None, device=DEV)
-    got = pipe._eps(x, t, eu, ec, 7.5)
+    got = pipe._eps_rows(x, t, eu, ec, [0], 3, 7.5)
     assert calls == [] and pipe.unet_rows == 6 and unet.rows == 6
     assert list(pipe._context_rows) == [3] and pipe._context_rows[3].tolist() == [0, 0, 0, 1, 1, 1]
     out = unet(torch.cat([x, x]), t, encoder_hidden_states=torch.cat([eu.expand(3, -1, -1), ec.expand(3, -1, -1)]), return_dict=False)[0]
     assert calls == [(6, c['context_len'], c['cross_attention_dim'])]        # the stock surface does group (and the counter does count)
     assert torch.equal(got, ops.cfg_combine(out[:3].contiguous(), out[3:].contiguous(), 7.5))
-    assert pipe._eps(x, t, eu, ec, 7.5) is not None and len(pipe._context_rows) == 1      # the map is built once per n
+    assert pipe._eps_rows(x, t, eu, ec, [0], 3, 7.5) is not None and len(pipe._context_rows) == 1      # the map is built once per n
 
     class Plain:                                                 # a U-Net without the keyword: the expanded tensor, as before
         dtype, seen = torch.float16, []
@@ -154,7 +154,7 @@ def test_the_pipeline_passes_the_row_map(gold, monkeypatch):
             self.ehs = encoder_hidden_states
             return (sample,)
     plain = Plain()
-    SDSearchPipeline(plain, None, device=DEV)._eps(x, t, eu, ec, 7.5)
+    SDSearchPipeline(plain, None, device=DEV)._eps_rows(x, t, eu, ec, [0], 3, 7.5)
     assert plain.seen == [((6, 4, 16, 16), (6, c['context_len'], c['cross_attention_dim']), [])]
     assert torch.equal(plain.ehs[:3], eu.expand(3, -1, -1)) and torch.equal(plain.ehs[3:], ec.expand(3, -1, -1))
 

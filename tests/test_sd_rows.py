@@ -111,6 +111,35 @@ def test_rejection_predraw_equals_sequential_naive_runs_on_one_stream(dtype):
     assert SeedStream(seed, SHAPE, dtype).naive_trajectory(steps, draw_latents=False)[0] is None
 
 
+@pytest.mark.parametrize('dtype', DTYPES, ids=IDS)
+@pytest.mark.parametrize('seed', [0, 33])
+def test_the_global_generator_is_the_stream_of_seed_none(seed, dtype):
+    """SeedStream(None, ...) draws from torch's global generator as it stands: after torch.manual_seed(s) it yields what SeedStream(s, ...)
+    yields in every round form the loop uses, two rounds each, and leaves the global generator where the seeded one stands"""
+    def draws(st):
+        got = []
+        for thr in (0.4, 0.0):                                      # eps-greedy, zero-order
+            for _ in range(2):
+                u, mode, scale = st.local_round(4, thr, 0.15)
+                got += [u, torch.tensor(mode), torch.tensor(scale, dtype=torch.float64)]
+        got += [st.beam_round(3) for _ in range(2)]
+        for _ in range(2):
+            lat, noises = st.naive_trajectory(3, draw_latents=False)
+            assert lat is None
+            got += noises
+        return got
+    seeded = SeedStream(seed, SHAPE, dtype)
+    want = draws(seeded)
+    torch.manual_seed(seed)
+    glob = SeedStream(None, SHAPE, dtype)
+    assert glob.seed is None and glob.gen is None
+    got = draws(glob)
+    assert len(got) == len(want) == 12 + 2 + 6
+    assert all(a.dtype == b.dtype and torch.equal(a, b) for a, b in zip(got, want))
+    assert all(t.dtype == dtype for t in got[0:12:3] + got[12:])
+    assert torch.equal(torch.get_rng_state(), seeded.gen.get_state())
+
+
 # ---- bulk driver --------------------------------------------------------------------------------------------------------------------------------
 class StubPipe:
     """records the calls generate_sd_seeds makes; images carry the seed so the files can be told apart"""
@@ -223,6 +252,11 @@ def test_pipeline_refuses_by_name_without_touching_a_gpu():
         pipe(method='mcts', row_seeds=[1, 2], **kw)
     with pytest.raises(ValueError, match='row_seeds: prompt: need 1 or 3 prompts'):
         pipe(prompt=['a', 'b'], method='naive', row_seeds=[1, 2, 3], score_function=None, params={})
+    # the single call: an unknown method is named (it used to run as 'naive'), and 'rejection' is main.py's loop over N calls or row_seeds' rows
+    with pytest.raises(ValueError, match="unknown method 'greedy'"):
+        pipe(method='greedy', latents=torch.zeros(1, 4, 8, 8), **kw)
+    with pytest.raises(ValueError, match="method 'rejection': the single call runs one trajectory .*row_seeds"):
+        pipe(method='rejection', latents=torch.zeros(1, 4, 8, 8), **dict(kw, params={'N': 2}))
     pipe.shards = types.SimpleNamespace(solo=False, collectives=0)
     with pytest.raises(ValueError, match='row_seeds: candidate sharding over more than one rank is not supported'):
         pipe(method='naive', row_seeds=[1, 2], **kw)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Measurement of the SD backend's lock-step searches (SDSearchPipeline(row_seeds=...)): searches per second for the same seeds run as
-sequential single-search `pipe()` calls (the path of every commit before lock-step existed), as `row_seeds` batches of one, and as batches
+sequential single-search `pipe()` calls (the loop's one-search case on the global generator), as `row_seeds` batches of one, and as batches
 of --search-batches seeds.  Random-init SDUNet and VAEDecoder at SD-1.5's shapes (as tools/sd_unet_bench.py / tools/sd_bench.py build
 them), float16, [1,4,64,64] latents, brightness scorer, eps-greedy with --N candidates, --K iterations, --steps DDIM steps.  GPU only.
 
