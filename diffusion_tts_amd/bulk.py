@@ -98,7 +98,9 @@ def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAI
     draws from its own seed's stream, so a seed's search is the one it runs alone (search_batch=1: bit for bit the `seed=` call's; larger
     batches: up to the launch forms the row count selects).  One PNG per seed; each seed's dict is its slice of the call's (image_result).
     MCTS, and calls with forced_selections / precomputed_noise (per search by nature), run one `seed=` call per seed as before.
-    `max_batch_size` is accepted for the reference's signature; the split is by `search_batch`."""
+    `max_batch_size` is accepted for the reference's signature; the split is by `search_batch`.  sampler_kwargs go to every call:
+    `share_identical=True` (eps-greedy / zero-order / beam_search=True) evaluates the identical candidates of a sigma step without churn
+    noise once per image -- the same PNGs from fewer denoiser rows."""
     rank, world = rank_world(rank, world)
     if int(search_batch) < 1:
         raise ValueError(f'search_batch: a positive number of seeds per lock-step batch, got {search_batch}')

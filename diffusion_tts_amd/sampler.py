@@ -127,6 +127,30 @@ class _Source:
         return [(None, tuple(shape))] if self.gens is None else [(b, (1,) + tuple(shape[1:])) for b in range(shape[0])]
 
 
+def churn_of(t_cur, num_steps, S_churn, S_min, S_max, S_noise, round_sigma):
+    """(t_hat, noise coefficient) of the sigma step that starts at `t_cur` (edm/main.py:84-86); host arithmetic only"""
+    gamma = min(S_churn / num_steps, np.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
+    t_hat = round_sigma(t_cur + gamma * t_cur)
+    coef = (t_hat ** 2 - t_cur ** 2).sqrt() * S_noise
+    return float(t_hat), float(coef)
+
+
+def identical_steps(t_steps, num_steps, S_churn, S_min, S_max, S_noise, round_sigma):
+    """The sigma steps at which every candidate of a search is the same row: those whose noise coefficient (`churn_of`, the number the
+    step hands to ops.heun_xhat) is exactly 0.0, so x_hat = x_cur + 0 * eps whatever eps is.  The test is on the coefficient, not on
+    gamma: a `round_sigma` that moves t_hat off t_cur (VP, VE, iDDPM) adds noise without churn, and such a step is not listed.
+    t_steps: the schedule, a float64 tensor of at least num_steps levels.  Pure host arithmetic."""
+    t = torch.as_tensor(t_steps, dtype=torch.float64)
+    return [i for i in range(num_steps) if churn_of(t[i], num_steps, S_churn, S_min, S_max, S_noise, round_sigma)[1] == 0.0]
+
+
+def shared_rows_saved(shared, num_steps, N, K, B=1):
+    """Denoiser rows an eps-greedy / zero-order search over B images does not launch with share_identical=True: at each sigma step of
+    `shared` its K candidate batches of N * B rows, two Heun stages each, one at the last step.  (The batch-B pivot step of every sigma
+    step is made either way.)  Sharded over ranks: N is the rank's own share of the candidates."""
+    return sum(K * N * B * (1 if i == num_steps - 1 else 2) for i in shared)
+
+
 class _Loop:
     """State shared by the search methods: schedule, device step, bookkeeping."""
 
@@ -141,15 +165,13 @@ class _Loop:
         self.forced = None                    # generate_image_grid(forced_selections=...)
         self.chunk = None                     # generate_image_grid(candidate_chunk=...)
         self.src = _Source()                  # generate_image_grid(row_seeds=...): one stream per image
+        self.shared = frozenset()             # generate_image_grid(share_identical=True): identical_steps(...) of this schedule
 
     def up(self, t, dtype=None):
         return t.to(self.dev, dtype).contiguous() if dtype is not None else t.to(self.dev).contiguous()
 
     def churn(self, t_cur):
-        gamma = min(self.S_churn / self.num_steps, np.sqrt(2) - 1) if self.S_min <= t_cur <= self.S_max else 0
-        t_hat = self.net.round_sigma(t_cur + gamma * t_cur)
-        coef = (t_hat ** 2 - t_cur ** 2).sqrt() * self.S_noise
-        return float(t_hat), float(coef)
+        return churn_of(t_cur, self.num_steps, self.S_churn, self.S_min, self.S_max, self.S_noise, self.net.round_sigma)
 
     def step(self, x_cur, t_cur, t_next, i, eps, labels, nb=None, interleave=False, live=None, first_denoised=False):
         """edm/main.py:82-96 on the device.  x_cur [xb,...] f64 is broadcast to nb rows; eps [nb,...] f64|f32.
@@ -256,8 +278,37 @@ def _beam_search(L: _Loop, t_steps, x_next, labels, p, pre):
             return pre[i].to(torch.float64).reshape(S * B, N, *shape1)
         return L.src.beams(S, B, N, shape1)                                            # :257, one draw per beam
 
+    # share_identical: cls[r] is the lowest beam row known to hold the state of beam row r (same image).  The B beams of an image start as
+    # copies of one state: one class.  A step without noise keeps equal rows equal, so its survivors inherit their parents' classes; any
+    # other step gives every survivor a noise of its own
+    cls = [r - r % B for r in range(S * B)]
     eps = draw(0)
     for i in range(L.num_steps):
+        if i in L.shared:
+            # all N candidates of a beam row are that row, and rows of one class are one row: one row per class goes through the step and
+            # the scorer, on every rank alike (no reward all-gather, no survivor exchange); rewards and survivors are expanded from it
+            reps = sorted(set(cls))
+            at = {r: q for q, r in enumerate(reps)}
+            x_rep = x.index_select(0, L.up(torch.tensor(reps))) if len(reps) < S * B else x
+            lab_rep = None if labels is None else labels.index_select(0, L.up(torch.tensor([r // B for r in reps]))).contiguous()
+            x_cand, x0 = L.step(x_rep, t_steps[i], t_steps[i + 1], i, torch.zeros_like(x_rep), lab_rep, first_denoised=True)
+            loc = L.score(p.scorer, x0, lab_rep).to(L.dev, torch.float32)
+            eps = draw(i + 1) if i + 1 < L.num_steps else None
+            of_row = torch.tensor([at[c] for c in cls])
+            allr = loc.cpu()[of_row].reshape(S, B, 1).expand(S, B, N).reshape(S, B * N).contiguous()
+            sel = beam_select(allr, B)
+            L.rewards.append(allr)
+            L.selected.append(sel)
+            L.beam_parents.append(sel // N)
+            rows = (torch.arange(S).reshape(S, 1) * B + sel // N).reshape(-1)           # the survivors' parent beam rows
+            x = x_cand.index_select(0, L.up(of_row[rows]))
+            old = [cls[r] for r in rows.tolist()]
+            first = {}
+            for r, c in enumerate(old):                                                # a class is named by its lowest member among the NEW rows
+                first.setdefault(c, r)
+            cls = [first[c] for c in old]
+            continue
+        cls = list(range(S * B))
         eps_l = L.up(eps[:, lo:hi].reshape(S * B * nl, *shape1))
         x_cand, x0 = L.step(x, t_steps[i], t_steps[i + 1], i, eps_l, lab, interleave=True, first_denoised=True)
         loc = L.score(p.scorer, x0, lab).to(L.dev, torch.float32).view(S * B, nl).t().contiguous().reshape(-1)   # candidate-major
@@ -353,9 +404,12 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
     def stage(item):
         # candidate directions of this rank (6.3 MB of fp64 at N=64): pinned and sent on a side stream while the GPU runs the
         # previous iteration -- an in-line pageable upload left the GPU idle for ~3 ms of every 41 ms iteration
+        sigma_step, stage.items = stage.items // (K + 1), stage.items + 1              # the stream is one pivot, then K iterations, per sigma step
         if not isinstance(item, tuple):
             return item                                                                # a pivot draw
         g_h, mode_t, scale_t = item
+        if sigma_step in L.shared:
+            return g_h, mode_t, scale_t, None, None, None                              # drawn as ever, not uploaded: no candidate batch is built
         host = pinned[stage.n % len(pinned)]                                           # ring: depth + 2 buffers, reused
         stage.n += 1
         if hi > lo:
@@ -366,7 +420,20 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
             ready.record(copy_stream)
         return g_h, mode_t, scale_t, g_dev, ready, host                                # `host` stays alive until the copy has run
 
-    stage.n = 0
+    def rebuild(pivot, g_h, mode_t, scale_t, best):
+        """the pivot moved to the winners `best` [B], rebuilt from the replicated host noise: no second collective"""
+        bl = best.tolist()
+        g_w = torch.stack([g_h[j][b] for b, j in enumerate(bl)])
+        if per_image:                                                                  # every image's own winner, mode and scale: one launch
+            own = torch.arange(B)
+            return ops.candidate_noise_rows(pivot, L.up(g_w), L.up(mode_t[best, own]), L.up(scale_t[best, own]))
+        if len(set(bl)) == 1:
+            return ops.candidate_noise(pivot, L.up(g_w), L.up(mode_t[bl[0]:bl[0] + 1]), L.up(scale_t[bl[0]:bl[0] + 1]))
+        rows = [ops.candidate_noise(pivot[b:b + 1].contiguous(), L.up(g_w[b:b + 1]), L.up(mode_t[j:j + 1]),
+                                    L.up(scale_t[j:j + 1])) for b, j in enumerate(bl)]
+        return torch.cat(rows, dim=0)
+
+    stage.n = stage.items = 0
     pinned = [torch.empty((nl * B,) + shape[1:], dtype=torch.float64).pin_memory() for _ in range(4)]
     draws = _Lookahead(_eps_greedy_draws(L, p, pre, shape, lam), stage=stage)
     for i in range(L.num_steps):
@@ -374,6 +441,26 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
         x_cur = x_next
         pivot = L.up(draws.get(), torch.float64)
         x_win = None
+        if i in L.shared:
+            # share_identical: the noise coefficient of this step is 0, so all K * N candidates of an image are x_cur itself, every decision
+            # is an exact tie (index 0) and the step taken is the pivot step below.  The draws are consumed and the pivot is rebuilt as ever
+            # (the stream of the later steps and best_noises do not move); no candidate batch exists, the reward of the one row every
+            # candidate equals -- the pivot step's second output, which is what a candidate row scores -- is computed once, by every rank
+            # for itself: no collective
+            for k in range(K):
+                g_h, mode_t, scale_t = draws.get()[:3]
+                best = torch.zeros(B, dtype=torch.int64) if L.forced is None else torch.tensor([L.forced[i * K + k]])
+                pivot = rebuild(pivot, g_h, mode_t, scale_t, best)
+                if L.record_noises:
+                    L.best_noises.setdefault(i, []).append(pivot.cpu())
+            x_next, x0 = L.step(x_cur, t_cur, t_next, i, pivot, labels)                # :860
+            loc = L.score(p.scorer, x0, labels).to(L.dev, torch.float32)
+            draws.prefetch()
+            scores = loc.reshape(1, B).cpu().expand(N, B).contiguous()
+            for k in range(K):
+                L.rewards.append(scores.clone())
+                L.selected.append(torch.zeros(B, dtype=torch.int64))
+            continue
         for k in range(K):
             g_h, mode_t, scale_t, g_l, ready, _pinned = draws.get()                    # n-major rows (:800)
             torch.cuda.current_stream(L.dev).wait_event(ready)
@@ -404,18 +491,8 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
             L.selected.append(best)
             if L.forced is not None:                                                   # follow another run's trajectory (B == 1)
                 best = torch.tensor([L.forced[len(L.selected) - 1]])
-            # survivor rebuilt from the replicated host noise: no second collective
             bl = best.tolist()
-            g_w = torch.stack([g_h[j][b] for b, j in enumerate(bl)])
-            if per_image:                                                              # every image's own winner, mode and scale: one launch
-                own = torch.arange(B)
-                pivot = ops.candidate_noise_rows(pivot, L.up(g_w), L.up(mode_t[best, own]), L.up(scale_t[best, own]))
-            elif len(set(bl)) == 1:
-                pivot = ops.candidate_noise(pivot, L.up(g_w), L.up(mode_t[bl[0]:bl[0] + 1]), L.up(scale_t[bl[0]:bl[0] + 1]))
-            else:
-                rows = [ops.candidate_noise(pivot[b:b + 1].contiguous(), L.up(g_w[b:b + 1]), L.up(mode_t[j:j + 1]),
-                                            L.up(scale_t[j:j + 1])) for b, j in enumerate(bl)]
-                pivot = torch.cat(rows, dim=0)
+            pivot = rebuild(pivot, g_h, mode_t, scale_t, best)
             if L.record_noises:                                                        # best_noises_this_timestep (:741, :854)
                 L.best_noises.setdefault(i, []).append(pivot.cpu())
             if L.reuse_winner and k == K - 1:
@@ -589,7 +666,7 @@ def generate_image_grid(
     *, scale_fn: Callable[[int, int, int], float] = builtin_scale, compute_dtype=ops.F16X3, verbose=True,
     reuse_winner: Optional[bool] = None, record_noises: bool = False, shard_candidates: bool = True,
     forced_selections: Optional[Sequence[int]] = None, candidate_chunk: Optional[int] = None, beam_search: bool = False,
-    row_seeds: Optional[Sequence[int]] = None,
+    row_seeds: Optional[Sequence[int]] = None, share_identical: bool = False,
 ):
     """Same positional/keyword surface as edm/main.py:47-55.  Keyword-only extras: `scale_fn` (the hash-derived step
     table, edm/main.py:776), `compute_dtype` (default ops.F16X3: split precision, the reference's fp32 selections at a third of the 16-bit
@@ -611,7 +688,13 @@ def generate_image_grid(
     search is that call's whatever else is in the batch -- up to the launch forms the row count selects -- and the searches of many seeds
     run in lock-step as one batch (bulk.generate_seeds(search_batch=...)); eps-greedy / zero-order coins then differ from image to image:
     mode / scale are [N, B] and the candidates and the rebuilt pivots come from ops.candidate_noise_rows; the result dict gains `row_seeds`;
-    not with MCTS, forced_selections, precomputed_noise or candidates sharded over ranks).  Writes the PNG grid like the
+    not with MCTS, forced_selections, precomputed_noise or candidates sharded over ranks), `share_identical` (eps-greedy / zero-order and
+    beam_search=True; not the reference's.  True: at the sigma steps `identical_steps` lists -- noise coefficient exactly 0, so every
+    candidate is the unchanged state -- the identical rows go through the denoiser and the scorer once instead of K * N times per image (beam:
+    one row per class of beam rows known to be equal).  Draws, selections (exact ties, index 0), the pivot steps and so `x`, `image` and
+    `best_noises` are those of the full run; the rewards of such a step are one value per image up to the launch form of the smaller batch;
+    `net_rows` is the actual, lower count (eps-greedy: by `shared_rows_saved`), and a sharded run makes no collective at such a step.  The
+    result dict's `shared_steps` lists the steps, [] when the keyword is off).  Writes the PNG grid like the
     reference when `dest_path` is not None and additionally returns a dict with the final state and the search trace."""
     device = torch.device(device)
     if device.type != 'cuda':
@@ -656,6 +739,10 @@ def generate_image_grid(
             raise ValueError('candidate_chunk: a positive candidate count, eps-greedy / zero-order search only')
         L.chunk = int(candidate_chunk)
     method_fn = _METHODS[sampling_method]
+    if share_identical:
+        if sampling_method not in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER) and not beam_search:
+            raise ValueError(f'share_identical=True: eps-greedy / zero-order search or beam_search=True only, got {sampling_method.name}')
+        L.shared = frozenset(identical_steps(t_steps, num_steps, S_churn, S_min, S_max, S_noise, net.round_sigma))
     if beam_search:
         if sampling_method != SamplingMethod.BEAM_SEARCH:
             raise ValueError(f'beam_search=True: SamplingMethod.BEAM_SEARCH only, got {sampling_method.name}')
@@ -687,7 +774,7 @@ def generate_image_grid(
         print('Done.')
     res = dict(x=x_next, image=img_cpu, final_scores=scores.cpu(), avg_score=avg_score, t_steps=t_steps,
                rewards=L.rewards, selected=L.selected, beam_parents=L.beam_parents, net_rows=getattr(net, 'evals', 0) - evals0,
-               collectives=shards.collectives, best_noises={i: torch.stack(v) for i, v in L.best_noises.items()})
+               collectives=shards.collectives, shared_steps=sorted(L.shared), best_noises={i: torch.stack(v) for i, v in L.best_noises.items()})
     if row_seeds is not None:
         res['row_seeds'] = row_seeds
     return res

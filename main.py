@@ -37,6 +37,9 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   define and raises AttributeError on entry) | run (the search that branch sets out to do: --B beams per image, the reference's
                   k, x --N candidates per beam, its b; per sigma step the top B of the B*N rewards survive, exact ties to the lower flat index;
                   generate_image_grid(beam_search=True)).  --backend sd has a working beam search of its own and ignores the flag
+    --share-identical: EDM backend, --method eps_greedy | zero_order | beam (--beam run): at the sigma steps without churn noise (sigma
+                  outside [S_min, S_max]: steps 0, 1, 15, 16 and 17 of the 18) all candidates of an image are the same row; evaluate it once
+                  (generate_image_grid(share_identical=True)): same image and selections, fewer denoiser rows than the reference's count
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
     --search-batch S: bulk mode: the searches of S seeds run in lock-step as ONE batch (S x the rows per denoiser call; every image draws
@@ -259,6 +262,9 @@ def build_parser():
     parser.add_argument('--beam', type=str, default='reference', choices=['reference', 'run'],
                         help="EDM backend, --method beam: 'reference' = the reference's branch as it stands (AttributeError on entry), 'run' = the "
                              "beam search it sets out to do: --B beams x --N candidates per beam (generate_image_grid(beam_search=True))")
+    parser.add_argument('--share-identical', dest='share_identical', action='store_true',
+                        help='EDM backend, eps_greedy / zero_order / beam (--beam run): evaluate the identical candidates of a sigma step without '
+                             'churn noise once (generate_image_grid(share_identical=True)); same image, fewer denoiser rows')
     parser.add_argument('--seeds', type=str, default=None, help='bulk mode: seeds, e.g. 0-63 or 1,2,5-10 (one image per seed)')
     parser.add_argument('--outdir', type=str, default='out', help='bulk mode: output directory')
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')
@@ -294,6 +300,8 @@ def main(argv=None):
         raise ValueError('clip scorer is only available for sd backend')
     check_bulk_args(args)
     if args.backend == 'sd':
+        if getattr(args, 'share_identical', False):
+            raise ValueError('--share-identical is an EDM option (DDIM with eta = 1 adds noise at every step)')
         if getattr(args, 'beam', 'reference') != 'reference':
             print(f'[SD] --beam {args.beam} is an EDM option: ignored (--method beam runs on the SD backend as it is)')
         return main_sd(args)
@@ -327,6 +335,8 @@ def main(argv=None):
     if beam_run and args.method != 'beam':
         raise ValueError(f'--beam run goes with --method beam, got --method {args.method}')
     extras = dict(beam_search=True) if beam_run else {}
+    if getattr(args, 'share_identical', False):
+        extras['share_identical'] = True
     if args.seeds is not None:                                                        # bulk mode: seeds sharded over the ranks
         from diffusion_tts_amd.bulk import generate_seeds
         mm = {'naive': SamplingMethod.NAIVE, 'rejection': SamplingMethod.REJECTION_SAMPLING, 'beam': SamplingMethod.BEAM_SEARCH,
