@@ -7,7 +7,8 @@ schedule sigma(t) and scaling s(t), on the K9b kernels (ops.ode_*).  Both are ro
 What stays on the host, as in sampler.py: the schedule and every per-step scalar (float64 torch operations in the reference's order of
 operations, `ode_schedule`), and the random numbers.  `StackedRandomGenerator` keeps one CPU generator per row, so a seed's image does not
 depend on the batch it is generated in; the reference draws on the CUDA device, a stream no other device reproduces.  The noise of a step is
-drawn every step (the stream stays the reference's) and uploaded once, only when its coefficient is not zero.
+drawn every step (the stream stays the reference's) and uploaded once (ablation_sampler: only when its coefficient is not zero).
+sampler.py builds on this file: the EDM schedule (`edm_sigmas`), the churn rule (`churn_of`) and the Heun step (`heun_step`, `heun_loop`) exist here, once.
 """
 import math
 
@@ -111,7 +112,7 @@ def ode_schedule(net, num_steps=18, sigma_min=None, sigma_max=None, rho=7, discr
         kept = u[torch.logical_and(u >= sigma_min, u <= sigma_max)]
         sigma_steps = kept[((len(kept) - 1) / (num_steps - 1) * idx).round().to(torch.int64)]
     else:
-        sigma_steps = (sigma_max ** (1 / rho) + idx / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
+        sigma_steps = edm_sigmas(num_steps, sigma_min, sigma_max, rho)
 
     if schedule == 'vp':
         sigma, sigma_inv = vp.sigma, vp.inverse
@@ -182,12 +183,55 @@ def _start(net, latents, class_labels, scale):
     return dev, x, labels
 
 
-def _noise(randn_like, x_cur, coef, dev, always=False):
-    """the step's draw (made whether or not it is used), on the device when it is"""
+def _noise(randn_like, x_cur, coef, dev):
+    """the ablation step's draw (made whether or not it is used), on the device when it is"""
     eps = randn_like(x_cur)
-    if coef == 0.0 and not always:
-        return None
-    return eps.to(dev).contiguous()
+    return None if coef == 0.0 else eps.to(dev).contiguous()
+
+
+def edm_sigmas(num_steps, sigma_min, sigma_max, rho):
+    """The EDM time discretisation (edm/main.py:78-79, edm/generate.py:38-39): num_steps noise levels from sigma_max down to sigma_min, float64
+    on the host.  Clamping to the network's range, rounding with net.round_sigma and the final 0 are each caller's own."""
+    idx = torch.arange(num_steps, dtype=torch.float64)
+    return (sigma_max ** (1 / rho) + idx / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
+
+
+def edm_schedule(net, num_steps, sigma_min, sigma_max, rho):
+    """t_steps of edm_sampler (edm/generate.py:33-40): the range clamped to the network's own, `edm_sigmas`, rounded, then 0"""
+    t_steps = edm_sigmas(num_steps, max(sigma_min, net.sigma_min), min(sigma_max, net.sigma_max), rho)
+    return torch.cat([net.round_sigma(t_steps), torch.zeros_like(t_steps[:1])])
+
+
+def churn_of(t_cur, num_steps, S_churn, S_min, S_max, S_noise, round_sigma):
+    """(t_hat, noise coefficient) of the sigma step that starts at `t_cur` (edm/main.py:84-86, edm/generate.py:47-49); host arithmetic only"""
+    gamma = min(S_churn / num_steps, np.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
+    t_hat = round_sigma(t_cur + gamma * t_cur)
+    coef = (t_hat ** 2 - t_cur ** 2).sqrt() * S_noise
+    return float(t_hat), float(coef)
+
+
+def heun_step(net, x_cur, eps, churn, t_next, last, labels, nb=None, interleave=False):
+    """One EDM step (edm/main.py:82-96, edm/generate.py:44-58) on the K9 kernels.  x_cur [xb, ...] f64 is broadcast to nb rows (default: the
+    rows of eps); eps [nb, ...] f64 | f32 on the device; churn = (t_hat, coef) of `churn_of`; last: the Euler step alone, no second-order
+    correction.  Returns x_next, the first denoiser output D(x_hat, t_hat) and the last one (the same tensor at the last step)."""
+    t_hat, coef = churn
+    x_hat = ops.heun_xhat(x_cur, eps, coef, eps.shape[0] if nb is None else nb, interleave)
+    D = D1 = net(x_hat, torch.tensor([t_hat], dtype=torch.float64), labels)
+    d_cur, x_next = ops.heun_euler(x_hat, D, t_hat, float(t_next))
+    if not last:
+        D = net(x_next, torch.as_tensor(t_next, dtype=torch.float64).reshape(1), labels)
+        ops.heun_correct(x_hat, D, d_cur, t_hat, float(t_next), x_next)
+    return x_next, D1, D
+
+
+def heun_loop(net, x_next, labels, t_steps, churn, draw):
+    """The search-free trajectory over t_steps (the last one 0): per step one host draw `draw(x)` for the whole batch (made at zero-noise
+    steps too: the stream is the reference's), uploaded, and one `heun_step`.  churn(t_cur) -> (t_hat, coef)."""
+    last = len(t_steps) - 2
+    for i in range(last + 1):
+        eps = draw(x_next).to(x_next.device).contiguous()
+        x_next = heun_step(net, x_next, eps, churn(t_steps[i]), t_steps[i + 1], i == last, labels)[0]
+    return x_next
 
 
 @torch.no_grad()
@@ -195,25 +239,9 @@ def edm_sampler(net, latents, class_labels=None, randn_like=host_randn_like, num
                 S_churn=0, S_min=0, S_max=float('inf'), S_noise=1):
     """edm/generate.py:25-60 on the K9 kernels: returns x_next, float64 on the device.  latents [n, c, r, r]; class_labels [n, label_dim] or None;
     `randn_like(x)` supplies a step's noise (x float64 [n, c, r, r]; a host tensor is uploaded).  The denoiser counts the rows in net.evals."""
-    sigma_min = max(sigma_min, net.sigma_min)
-    sigma_max = min(sigma_max, net.sigma_max)
-    idx = torch.arange(num_steps, dtype=torch.float64)
-    t_steps = (sigma_max ** (1 / rho) + idx / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
-    t_steps = torch.cat([net.round_sigma(t_steps), torch.zeros_like(t_steps[:1])])
-    dev, x_next, labels = _start(net, latents, class_labels, t_steps[0])
-    n = x_next.shape[0]
-    for i in range(num_steps):
-        t_cur, t_next = t_steps[i], t_steps[i + 1]
-        gamma = min(S_churn / num_steps, np.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
-        t_hat = net.round_sigma(t_cur + gamma * t_cur)
-        coef = float((t_hat ** 2 - t_cur ** 2).sqrt() * S_noise)
-        x_hat = ops.heun_xhat(x_next, _noise(randn_like, x_next, coef, dev, always=True), coef, n)
-        D = net(x_hat, t_hat.reshape(1), labels)
-        d_cur, x_next = ops.heun_euler(x_hat, D, float(t_hat), float(t_next))
-        if i < num_steps - 1:
-            D = net(x_next, t_next.reshape(1), labels)
-            ops.heun_correct(x_hat, D, d_cur, float(t_hat), float(t_next), x_next)
-    return x_next
+    t_steps = edm_schedule(net, num_steps, sigma_min, sigma_max, rho)
+    _, x_next, labels = _start(net, latents, class_labels, t_steps[0])
+    return heun_loop(net, x_next, labels, t_steps, lambda t_cur: churn_of(t_cur, num_steps, S_churn, S_min, S_max, S_noise, net.round_sigma), randn_like)
 
 
 @torch.no_grad()

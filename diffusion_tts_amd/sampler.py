@@ -6,13 +6,13 @@ randomness is drawn from the torch *CPU* global generator (and numpy's for MCTS)
 order -- including draws whose values the reference throws away -- and uploaded, because the parity oracle is the
 reference's `--device cpu` run and a device Philox stream could not reproduce it (hard part 2).
 What runs on the GPU: every tensor operation -- candidate construction (K14), the fp64 Heun/Euler step (K9), the
-denoiser, quantisation (K10) and the scorer.  With `row_seeds` every image of the batch draws from a CPU generator of its own instead
-(`_Source`): the searches of several seeds run in lock-step as one batch, each the search its seed runs alone.
+denoiser, quantisation (K10) and the scorer.  A batch draws from L lanes (`_Source`): L = 1, the global stream for all its images, or with
+`row_seeds` L = B, a CPU generator per image: the searches of several seeds run in lock-step as one batch, each the search its seed runs alone.
+The sigma schedule, the churn rule and the Heun step are plain.py's (`edm_sigmas`, `churn_of`, `heun_step`): the plain sampler is this loop without a search.
 
 With torch.distributed initialised (one process per GPU) the N candidates of each search iteration are sharded
 across ranks (parallel.CandidateShards): one all-gather of N*B rewards per iteration, identical argmax on every rank.
 """
-import math
 import os
 from dataclasses import dataclass, field
 from enum import Enum, auto
@@ -24,6 +24,7 @@ import torch
 from . import ops
 from .hashing import builtin_scale
 from .parallel import CandidateShards
+from .plain import churn_of, edm_sigmas, heun_loop, heun_step
 from .scorers import Scorer, CompressibilityScorer
 
 
@@ -88,51 +89,56 @@ def load_network(spec, device='cuda', dtype=ops.F16X3):
                      f'state-dict bundle or "random:<preset>[:seed]" (URLs cannot be fetched here)')
 
 
+def _side_by_side(parts):
+    """the draws of the lanes as one batch [B, ...]: the one lane's draw is the batch itself, not a copy of it"""
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
 class _Source:
     """Where the host draws of a search come from.  row_seeds=None: torch's global CPU generator, one stream for the whole batch (the
     reference's).  row_seeds given: image b draws from its own torch.Generator().manual_seed(row_seeds[b]) in exactly the order and shapes
     a one-image call seeded row_seeds[b] draws from the global stream -- which such a generator replays bit for bit -- so an image's
     numbers do not depend on its companions in the batch.  torch's CPU generator keeps the low 32 bits of a seed and nothing else (seed
-    s + 2^32 replays seed s): a seed outside [0, 2^32) is refused by name, not reduced in silence."""
+    s + 2^32 replays seed s): a seed outside [0, 2^32) is refused by name, not reduced in silence.
+    Either way it is L lanes, a lane being one stream and the images it covers: the lane None (generator=None, the global one) covers the whole
+    batch, lane b of row_seeds covers image b; every draw is a lane's `randn` / `rand1`."""
 
     def __init__(self, row_seeds=None):
         for s in row_seeds or ():
             if not 0 <= int(s) < 2 ** 32:
                 raise ValueError(f'row_seeds: seed {int(s)} is outside [0, 2^32): torch\'s CPU generator would keep its low 32 bits '
                                  f'(the stream of seed {int(s) % 2 ** 32})')
-        self.gens = None if row_seeds is None else [torch.Generator().manual_seed(int(s)) for s in row_seeds]
+        self.gens = {None: None} if row_seeds is None else {b: torch.Generator().manual_seed(int(s)) for b, s in enumerate(row_seeds)}
+        self.L = len(self.gens)                                          # lanes: 1 for the whole batch, or one per image
 
     def _gen(self, image):
-        return None if self.gens is None else self.gens[image]
+        return self.gens[image if image in self.gens else None]          # the image's own lane, or the one lane of all
 
     def randn(self, image, shape, dtype=torch.float64):
-        """one draw of `shape` from image `image`'s stream (the global stream without row_seeds)"""
+        """one draw of `shape` from the stream of lane (or image) `image`"""
         return torch.randn(shape, dtype=dtype, generator=self._gen(image))
 
     def rand1(self, image):
         return torch.rand(1, generator=self._gen(image))
 
+    def lanes(self, shape):
+        """the L lanes behind a batch of `shape` [B, ...] as (lane, shape of one draw): [B, ...] for the one lane of all, [1, ...] for an image's own"""
+        assert self.L in (1, shape[0]), f'{self.L} lanes for a batch of {shape[0]} images: one lane in all, or one per image'
+        return [(lane, (shape[0] // self.L,) + tuple(shape[1:])) for lane in self.gens]
+
     def images(self, B, rows, shape1):
-        """[B * rows, *shape1] float64 normals, image-major: one draw for the batch, or image b's `rows` rows from its own stream"""
-        if self.gens is None:
-            return torch.randn((B * rows,) + tuple(shape1), dtype=torch.float64)
-        return torch.cat([self.randn(b, (rows,) + tuple(shape1)) for b in range(B)], dim=0)
+        """[B * rows, *shape1] float64 normals, image-major: per lane one draw of `rows` rows for each image it covers"""
+        return _side_by_side([self.randn(lane, (n * rows,) + tuple(shape1)) for lane, (n, *_) in self.lanes((B,))])
 
     def beams(self, S, B, N, shape1):
         """[S * B, N, *shape1] float64 normals: one draw of N candidates per beam row in row order (image-major: image s draws its B blocks in order)"""
         return torch.stack([self.randn(r // B, (N,) + tuple(shape1)) for r in range(S * B)])
 
-    def lanes(self, shape):
-        """the independent streams behind a batch of `shape` [B, ...] as (image, shape of one draw): the whole batch at once, or one image each"""
-        return [(None, tuple(shape))] if self.gens is None else [(b, (1,) + tuple(shape[1:])) for b in range(shape[0])]
 
-
-def churn_of(t_cur, num_steps, S_churn, S_min, S_max, S_noise, round_sigma):
-    """(t_hat, noise coefficient) of the sigma step that starts at `t_cur` (edm/main.py:84-86); host arithmetic only"""
-    gamma = min(S_churn / num_steps, np.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
-    t_hat = round_sigma(t_cur + gamma * t_cur)
-    coef = (t_hat ** 2 - t_cur ** 2).sqrt() * S_noise
-    return float(t_hat), float(coef)
+def grid_schedule(net, num_steps, sigma_min, sigma_max, rho):
+    """t_steps of generate_image_grid (edm/main.py:78-80): `edm_sigmas` of the range as given -- not clamped to the network's -- rounded, then 0"""
+    t_steps = edm_sigmas(num_steps, sigma_min, sigma_max, rho)
+    return torch.cat([net.round_sigma(t_steps), torch.zeros_like(t_steps[:1])])
 
 
 def identical_steps(t_steps, num_steps, S_churn, S_min, S_max, S_noise, round_sigma):
@@ -179,14 +185,7 @@ class _Loop:
         first_denoised: return D(x_hat, t_hat) instead of the second-order output (the beam branch's own step, edm/main.py:161-212)."""
         nb = eps.shape[0] if nb is None else nb
         evals0 = getattr(self.net, 'evals', None)
-        t_hat, coef = self.churn(t_cur)
-        t_hat_t = torch.tensor([t_hat], dtype=torch.float64)
-        x_hat = ops.heun_xhat(x_cur, eps, coef, nb, interleave)
-        D = D1 = self.net(x_hat, t_hat_t, labels)
-        d_cur, x_next = ops.heun_euler(x_hat, D, t_hat, float(t_next))
-        if i < self.num_steps - 1:
-            D = self.net(x_next, torch.as_tensor(t_next, dtype=torch.float64).reshape(1), labels)
-            ops.heun_correct(x_hat, D, d_cur, t_hat, float(t_next), x_next)
+        x_next, D1, D = heun_step(self.net, x_cur, eps, self.churn(t_cur), t_next, i >= self.num_steps - 1, labels, nb, interleave)
         if live is not None and live != nb and evals0 is not None:       # padding rows went through the denoiser but are not counted
             self.net.evals = evals0 + (self.net.evals - evals0) // nb * live
         return x_next, (D1 if first_denoised else D)
@@ -196,13 +195,17 @@ class _Loop:
         ts = torch.zeros(img.shape[0], device=self.dev)
         return scorer(img, labels, ts)
 
+    def winner_rows(self, x, best, N, row):
+        """[B, ...]: for image b the row of its winner best[b] among N candidates, sent by the rank that owns that candidate.  x: the rows of
+        this rank's share [lo, hi); row(b, j) is where it keeps its j-th candidate of image b."""
+        lo, hi = self.shards.span(N)
+        mine = lambda b, j: x[row(b, j - lo)].clone() if lo <= j < hi else torch.empty(x.shape[1:], dtype=torch.float64, device=self.dev)
+        return torch.stack([self.shards.broadcast_from_owner(mine(b, j), j, N) for b, j in enumerate(best.tolist())])
+
 
 # ---------------------------------------------------------------------------------------------------------
 def _naive(L: _Loop, t_steps, x_next, labels, p, pre):
-    for i in range(L.num_steps):
-        eps = L.src.images(x_next.shape[0], 1, x_next.shape[1:])                     # edm/main.py:865
-        x_next, _ = L.step(x_next, t_steps[i], t_steps[i + 1], i, L.up(eps), labels)
-    return x_next
+    return heun_loop(L.net, x_next, labels, t_steps, L.churn, lambda x: L.src.images(x.shape[0], 1, x.shape[1:]))   # edm/main.py:865
 
 
 def _rejection(L: _Loop, t_steps, x_next, labels, p, pre):
@@ -214,28 +217,20 @@ def _rejection(L: _Loop, t_steps, x_next, labels, p, pre):
     nl = hi - lo
     shape1 = tuple(x_next.shape[1:])
     lab = None if labels is None else labels.repeat_interleave(nl, dim=0).contiguous()
-    x = None
+    x = x_next
     for i in range(L.num_steps):
         if pre is not None and i in pre:
             eps = pre[i][:, :N].reshape(B * N, *shape1).to(torch.float64)
         else:
             eps = L.src.images(B, N, shape1)                                         # edm/main.py:120
         eps_l = L.up(eps.view(B, N, *shape1)[:, lo:hi].reshape(B * nl, *shape1))
-        if x is None:
-            x, _ = L.step(x_next, t_steps[i], t_steps[i + 1], i, eps_l, lab, interleave=True)
-        else:
-            x, _ = L.step(x, t_steps[i], t_steps[i + 1], i, eps_l, lab)
+        x, _ = L.step(x, t_steps[i], t_steps[i + 1], i, eps_l, lab, interleave=(i == 0))      # the first step fans every image out to its nl rows
     loc = L.score(p.scorer, x, lab).to(L.dev, torch.float32).view(B, nl).t().contiguous().reshape(-1)   # candidate-major
     allr = L.shards.gather_rewards(loc, N, B).view(N, B).t().contiguous().cpu()                # [B, N]
     best = allr.argmax(dim=1)                                                                  # edm/main.py:136
     L.rewards.append(allr)
     L.selected.append(best)
-    out = []
-    xr = x.view(B, nl, *shape1)
-    for b, j in enumerate(best.tolist()):
-        row = xr[b, j - lo].clone() if lo <= j < hi else torch.empty(shape1, dtype=torch.float64, device=L.dev)
-        out.append(L.shards.broadcast_from_owner(row, j, N))
-    return torch.stack(out)
+    return L.winner_rows(x, best, N, lambda b, j: b * nl + j)
 
 
 def _beam(L: _Loop, t_steps, x_next, labels, p, pre):
@@ -278,6 +273,14 @@ def _beam_search(L: _Loop, t_steps, x_next, labels, p, pre):
             return pre[i].to(torch.float64).reshape(S * B, N, *shape1)
         return L.src.beams(S, B, N, shape1)                                            # :257, one draw per beam
 
+    def decide(allr):
+        """a sigma step's decision on its rewards allr [S, B*N], recorded: the survivors sel [S, B] (flat j*N + n) and their parent beam rows [S*B]"""
+        sel = beam_select(allr, B)
+        L.rewards.append(allr)
+        L.selected.append(sel)
+        L.beam_parents.append(sel // N)
+        return sel, (torch.arange(S).reshape(S, 1) * B + sel // N).reshape(-1)
+
     # share_identical: cls[r] is the lowest beam row known to hold the state of beam row r (same image).  The B beams of an image start as
     # copies of one state: one class.  A step without noise keeps equal rows equal, so its survivors inherit their parents' classes; any
     # other step gives every survivor a noise of its own
@@ -296,11 +299,7 @@ def _beam_search(L: _Loop, t_steps, x_next, labels, p, pre):
             eps = draw(i + 1) if i + 1 < L.num_steps else None
             of_row = torch.tensor([at[c] for c in cls])
             allr = loc.cpu()[of_row].reshape(S, B, 1).expand(S, B, N).reshape(S, B * N).contiguous()
-            sel = beam_select(allr, B)
-            L.rewards.append(allr)
-            L.selected.append(sel)
-            L.beam_parents.append(sel // N)
-            rows = (torch.arange(S).reshape(S, 1) * B + sel // N).reshape(-1)           # the survivors' parent beam rows
+            sel, rows = decide(allr)
             x = x_cand.index_select(0, L.up(of_row[rows]))
             old = [cls[r] for r in rows.tolist()]
             first = {}
@@ -316,12 +315,8 @@ def _beam_search(L: _Loop, t_steps, x_next, labels, p, pre):
         # in line they left it idle for the 10 ms that 64 x [3, 64, 64] float64 normals take on the host
         eps = draw(i + 1) if i + 1 < L.num_steps else None
         allr = L.shards.gather_rewards(loc, N, S * B).view(N, S * B).t().contiguous().cpu().reshape(S, B * N)
-        sel = beam_select(allr, B)                                                     # [S, B] flat indices j*N + n
-        L.rewards.append(allr)
-        L.selected.append(sel)
-        L.beam_parents.append(sel // N)
+        sel, rows = decide(allr)
         # survivor (s, rank q) is candidate n = sel % N of beam row s*B + sel // N: this rank holds it iff lo <= n < hi
-        rows = (torch.arange(S).reshape(S, 1) * B + sel // N).reshape(-1)
         cand = (sel % N).reshape(-1)
         src = rows * nl + (cand - lo).clamp(0, nl - 1)                                 # any valid row where the survivor is another rank's
         x = L.shards.exchange_rows(x_cand.index_select(0, L.up(src)), [L.shards.owner(n, N) for n in cand.tolist()])
@@ -352,37 +347,33 @@ class _Lookahead:
 
 def _eps_greedy_draws(L, p, pre, shape, lam):
     """The host-RNG stream of edm/main.py:724-797 in call order: per timestep one pivot, then per local-search
-    iteration the N coins / Gaussians / hash-derived scales.  A lane is one stream (_Source.lanes): the whole batch shares the coin of a
-    candidate (mode / scale [N]), or every image flips its own (mode / scale [N, B])."""
+    iteration the N coins / Gaussians / hash-derived scales, each candidate's taken lane by lane (_Source.lanes).  An iteration yields the
+    Gaussians as [N] tensors of [B, ...], mode int32 and scale float32 [N, L]: L = 1, the whole batch shares the coin of a candidate, or
+    L = B, every image flips its own."""
     N, K, eps_p, src = p.N, p.K, p.eps, L.src
     lanes = src.lanes(shape)
+
+    def candidate(i, k, n, lane, lshape):
+        """(Gaussian [lshape], mode, scale) of candidate n as one lane draws it"""
+        if src.rand1(lane) < (1 - eps_p):                                             # :751
+            if pre is not None and i in pre and k < pre[i].shape[1] and n < pre[i].shape[2]:
+                g = pre[i][:, k, n].reshape(lshape).to(torch.float64)
+            else:
+                g = src.randn(lane, lshape)                                           # :767
+            s = torch.ones([lshape[0], 1, 1, 1]) * L.scale_fn(i, k, n) * lam          # float32, :779
+            return g, 1, float(s.flatten()[0])
+        key = f'fresh_{i}_{k}_{n}'
+        return (pre[key].to(torch.float64) if (pre is not None and key in pre) else src.randn(lane, lshape)), 0, 0.0
+
     if not (pre is not None and 'pivot' in pre):
         src.images(shape[0], 1, shape[1:])                                            # :727, overwritten at :737
     for i in range(L.num_steps):
         yield pre[f'pivot_{i}'] if (pre is not None and f'pivot_{i}' in pre) else src.images(shape[0], 1, shape[1:])
         for k in range(K):
-            g_h, mode, scale = [], [], []
-            for n in range(N):
-                g_n, m_n, s_n = [], [], []
-                for image, lshape in lanes:
-                    if src.rand1(image) < (1 - eps_p):                                # :751
-                        if pre is not None and i in pre and k < pre[i].shape[1] and n < pre[i].shape[2]:
-                            g = pre[i][:, k, n].reshape(lshape).to(torch.float64)
-                        else:
-                            g = src.randn(image, lshape)                              # :767
-                        s = torch.ones([lshape[0], 1, 1, 1]) * L.scale_fn(i, k, n) * lam   # float32, :779
-                        m_n.append(1)
-                        s_n.append(float(s.flatten()[0]))
-                    else:
-                        key = f'fresh_{i}_{k}_{n}'
-                        g = pre[key].to(torch.float64) if (pre is not None and key in pre) else src.randn(image, lshape)
-                        m_n.append(0)
-                        s_n.append(0.0)
-                    g_n.append(g)
-                g_h.append(g_n[0] if src.gens is None else torch.cat(g_n, dim=0))
-                mode.append(m_n[0] if src.gens is None else m_n)
-                scale.append(s_n[0] if src.gens is None else s_n)
-            yield g_h, torch.tensor(mode, dtype=torch.int32), torch.tensor(scale, dtype=torch.float32)
+            rows = [[candidate(i, k, n, lane, lshape) for lane, lshape in lanes] for n in range(N)]      # candidate by candidate, lane by lane
+            g_h = [_side_by_side([g for g, _, _ in r]) for r in rows]
+            mode = torch.tensor([[m for _, m, _ in r] for r in rows], dtype=torch.int32)
+            yield g_h, mode, torch.tensor([[s for _, _, s in r] for r in rows], dtype=torch.float32)
 
 
 def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
@@ -398,7 +389,7 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
     lo, hi = L.shards.span(N)
     nl = hi - lo
     lab_l = None if labels is None else labels.repeat(nl, 1).contiguous()
-    per_image = L.src.gens is not None
+    own = torch.arange(B)
     copy_stream = torch.cuda.Stream(device=L.dev)
 
     def stage(item):
@@ -420,18 +411,21 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
             ready.record(copy_stream)
         return g_h, mode_t, scale_t, g_dev, ready, host                                # `host` stays alive until the copy has run
 
-    def rebuild(pivot, g_h, mode_t, scale_t, best):
-        """the pivot moved to the winners `best` [B], rebuilt from the replicated host noise: no second collective"""
-        bl = best.tolist()
-        g_w = torch.stack([g_h[j][b] for b, j in enumerate(bl)])
-        if per_image:                                                                  # every image's own winner, mode and scale: one launch
-            own = torch.arange(B)
-            return ops.candidate_noise_rows(pivot, L.up(g_w), L.up(mode_t[best, own]), L.up(scale_t[best, own]))
-        if len(set(bl)) == 1:
-            return ops.candidate_noise(pivot, L.up(g_w), L.up(mode_t[bl[0]:bl[0] + 1]), L.up(scale_t[bl[0]:bl[0] + 1]))
-        rows = [ops.candidate_noise(pivot[b:b + 1].contiguous(), L.up(g_w[b:b + 1]), L.up(mode_t[j:j + 1]),
-                                    L.up(scale_t[j:j + 1])) for b, j in enumerate(bl)]
-        return torch.cat(rows, dim=0)
+    def decide(i, pivot, scores, g_h, mode_t, scale_t):
+        """the end of a local-search iteration on its rewards `scores` [N, B]: the winners, recorded, and the pivot moved to them"""
+        best = scores.argmax(dim=0)                                                    # first max (:842)
+        L.rewards.append(scores)
+        L.selected.append(best)
+        if L.forced is not None:                                                       # follow another run's trajectory (B == 1)
+            best = torch.tensor([L.forced[len(L.selected) - 1]])
+        # rebuilt from the replicated host noise (no second collective) in one launch of B rows: row b carries its winner's mode and scale,
+        # [N, L] read as [N, B] -- its own lane's, or the one lane's for every image
+        g_w = torch.stack([g_h[j][b] for b, j in enumerate(best.tolist())])
+        m_w, s_w = mode_t.expand(N, B)[best, own], scale_t.expand(N, B)[best, own]
+        pivot = ops.candidate_noise_rows(pivot, L.up(g_w), L.up(m_w), L.up(s_w))
+        if L.record_noises:                                                            # best_noises_this_timestep (:741, :854)
+            L.best_noises.setdefault(i, []).append(pivot.cpu())
+        return best, pivot
 
     stage.n = stage.items = 0
     pinned = [torch.empty((nl * B,) + shape[1:], dtype=torch.float64).pin_memory() for _ in range(4)]
@@ -440,35 +434,26 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
         t_cur, t_next = t_steps[i], t_steps[i + 1]
         x_cur = x_next
         pivot = L.up(draws.get(), torch.float64)
-        x_win = None
         if i in L.shared:
             # share_identical: the noise coefficient of this step is 0, so all K * N candidates of an image are x_cur itself, every decision
-            # is an exact tie (index 0) and the step taken is the pivot step below.  The draws are consumed and the pivot is rebuilt as ever
-            # (the stream of the later steps and best_noises do not move); no candidate batch exists, the reward of the one row every
-            # candidate equals -- the pivot step's second output, which is what a candidate row scores -- is computed once, by every rank
-            # for itself: no collective
-            for k in range(K):
-                g_h, mode_t, scale_t = draws.get()[:3]
-                best = torch.zeros(B, dtype=torch.int64) if L.forced is None else torch.tensor([L.forced[i * K + k]])
-                pivot = rebuild(pivot, g_h, mode_t, scale_t, best)
-                if L.record_noises:
-                    L.best_noises.setdefault(i, []).append(pivot.cpu())
+            # is an exact tie (index 0) and the step taken is the pivot step, whatever the pivot: it is made first, on the drawn pivot, and
+            # its second output -- what a candidate row scores -- is the reward of every candidate, computed once, by every rank for itself
+            # (no candidate batch, no collective).  The draws are consumed and the pivot is rebuilt as ever (the stream of the later steps
+            # and best_noises do not move)
             x_next, x0 = L.step(x_cur, t_cur, t_next, i, pivot, labels)                # :860
             loc = L.score(p.scorer, x0, labels).to(L.dev, torch.float32)
             draws.prefetch()
-            scores = loc.reshape(1, B).cpu().expand(N, B).contiguous()
+            scores = loc.reshape(1, B).cpu().expand(N, B)
             for k in range(K):
-                L.rewards.append(scores.clone())
-                L.selected.append(torch.zeros(B, dtype=torch.int64))
+                _, pivot = decide(i, pivot, scores.clone(), *draws.get()[:3])
             continue
         for k in range(K):
             g_h, mode_t, scale_t, g_l, ready, _pinned = draws.get()                    # n-major rows (:800)
             torch.cuda.current_stream(L.dev).wait_event(ready)
             g_l.record_stream(torch.cuda.current_stream(L.dev))
-            if per_image:                                                              # mode / scale [N, B]: a row each (n-major, as the rows)
-                cand = ops.candidate_noise_rows(pivot, g_l, L.up(mode_t[lo:hi].reshape(-1)), L.up(scale_t[lo:hi].reshape(-1)))
-            else:
-                cand = ops.candidate_noise(pivot, g_l, L.up(mode_t[lo:hi]), L.up(scale_t[lo:hi]))
+            # one lane (B = 1 with its own seed included): a coin per candidate, the per-candidate launch; a lane per image: the per-row one
+            build = ops.candidate_noise if L.src.L == 1 else ops.candidate_noise_rows
+            cand = build(pivot, g_l, L.up(mode_t[lo:hi].reshape(-1)), L.up(scale_t[lo:hi].reshape(-1)))
             if L.chunk is None or L.chunk * B >= nl * B:
                 x_cand, x0 = L.step(x_cur, t_cur, t_next, i, cand, lab_l, nb=nl * B)
                 loc = L.score(p.scorer, x0, lab_l).to(L.dev, torch.float32)
@@ -485,26 +470,9 @@ def _eps_greedy(L: _Loop, t_steps, x_next, labels, p, pre):
                     locs.append(L.score(p.scorer, x0_, lab_c).to(L.dev, torch.float32).clone())
                 x_cand, loc = torch.cat(xs, dim=0), torch.cat(locs, dim=0)
             draws.prefetch()                                                           # host draws overlap the queued GPU work
-            scores = L.shards.gather_rewards(loc, N, B).reshape(N, B).cpu()
-            best = scores.argmax(dim=0)                                                # first max (:842)
-            L.rewards.append(scores)
-            L.selected.append(best)
-            if L.forced is not None:                                                   # follow another run's trajectory (B == 1)
-                best = torch.tensor([L.forced[len(L.selected) - 1]])
-            bl = best.tolist()
-            pivot = rebuild(pivot, g_h, mode_t, scale_t, best)
-            if L.record_noises:                                                        # best_noises_this_timestep (:741, :854)
-                L.best_noises.setdefault(i, []).append(pivot.cpu())
-            if L.reuse_winner and k == K - 1:
-                # the step the reference recomputes at :860 for the final pivot IS the winner's row of this iteration
-                rows = []
-                for b, j in enumerate(bl):
-                    own = lo <= j < hi
-                    r = x_cand[(j - lo) * B + b].clone() if own else torch.empty(shape[1:], dtype=torch.float64, device=L.dev)
-                    rows.append(L.shards.broadcast_from_owner(r, j, N))
-                x_win = torch.stack(rows)
-        if x_win is not None:
-            x_next = x_win
+            best, pivot = decide(i, pivot, L.shards.gather_rewards(loc, N, B).reshape(N, B).cpu(), g_h, mode_t, scale_t)
+        if L.reuse_winner and K > 0:       # the step the reference recomputes at :860 for the final pivot IS the winner's row of the last iteration
+            x_next = L.winner_rows(x_cand, best, N, lambda b, j: j * B + b)
         else:
             x_next, _ = L.step(x_cur, t_cur, t_next, i, pivot, labels)                 # :860
     return x_next
@@ -687,7 +655,8 @@ def generate_image_grid(
     of the search from its own generator seeded row_seeds[b], in the order and shapes of a one-image call with seed=row_seeds[b], so its
     search is that call's whatever else is in the batch -- up to the launch forms the row count selects -- and the searches of many seeds
     run in lock-step as one batch (bulk.generate_seeds(search_batch=...)); eps-greedy / zero-order coins then differ from image to image:
-    mode / scale are [N, B] and the candidates and the rebuilt pivots come from ops.candidate_noise_rows; the result dict gains `row_seeds`;
+    mode / scale are [N, B] instead of [N, 1] and the candidates come from ops.candidate_noise_rows (the rebuilt pivots always do, one launch
+    of B rows); the result dict gains `row_seeds`;
     not with MCTS, forced_selections, precomputed_noise or candidates sharded over ranks), `share_identical` (eps-greedy / zero-order and
     beam_search=True; not the reference's.  True: at the sigma steps `identical_steps` lists -- noise coefficient exactly 0, so every
     candidate is the unchanged state -- the identical rows go through the denoiser and the scorer once instead of K * N times per image (beam:
@@ -705,9 +674,7 @@ def generate_image_grid(
         print(f'Using sampling method: {sampling_method.name}')
     net = load_network(network_pkl, device=device, dtype=compute_dtype)
     shards = CandidateShards(enabled=shard_candidates)     # False: this rank runs the whole search (bulk.py shards seeds instead)
-    step_indices = torch.arange(num_steps, dtype=torch.float64)                       # edm/main.py:78-80 (host)
-    t_steps = (sigma_max ** (1 / rho) + step_indices / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
-    t_steps = torch.cat([net.round_sigma(t_steps), torch.zeros_like(t_steps[:1])])
+    t_steps = grid_schedule(net, num_steps, sigma_min, sigma_max, rho)              # edm/main.py:78-80 (host)
     L = _Loop(net, device, num_steps, S_churn, S_min, S_max, S_noise, scale_fn, shards)
     # eps-greedy: the reference re-runs step() at batch 1 for the final pivot of each timestep (edm/main.py:860) although
     # that row was just computed in the last candidate batch.  The default mode (f16x3) and float32 recompute it like the reference, so
@@ -785,7 +752,6 @@ def dump_noise_trajectory(result, directory='.'):
     (edm/dmap.py:16-24): `all_timestep_noises.pkl` = {timestep index: Tensor[K, B, C, H, W]} and `t_steps.pkl`.  The
     reference's loop collects exactly this list (edm/main.py:739-741, 853-854) but never writes it; `result` is the
     dict returned by `generate_image_grid(..., record_noises=True)`."""
-    import os
     import pickle
     if not result.get('best_noises'):
         raise ValueError('no noise trajectory recorded: call generate_image_grid(..., record_noises=True) with a local-search method')

@@ -57,6 +57,34 @@ def schedule_kwargs(case):
     return kw
 
 
+def written_out(num_steps, sigma_min, sigma_max, rho):
+    """the EDM discretisation as the reference writes it (edm/main.py:78-79, edm/generate.py:38-39)"""
+    step_indices = torch.arange(num_steps, dtype=torch.float64)
+    return (sigma_max ** (1 / rho) + step_indices / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
+
+
+@pytest.mark.parametrize('num_steps', [2, 4, 18])
+def test_edm_sigmas_is_the_written_out_expression_and_each_caller_keeps_its_own_range(num_steps):
+    """plain.edm_sigmas bit for bit in float64, for the default range and a clamped one; then the two callers' schedules: equal for a network
+    that neither clamps nor rounds, and for the range of the iDDPM ImageNet-64 configuration different in the expected way -- edm_sampler
+    (plain.edm_schedule) clamps the range to the network's, generate_image_grid (sampler.grid_schedule) takes it as given"""
+    from diffusion_tts_amd import plain, sampler
+    from diffusion_tts_amd.config import iddpm_imagenet64
+    for lo, hi, rho in ((0.002, 80, 7), (0.0064, 60.5, 7), (0.002, 80, 5)):
+        got = plain.edm_sigmas(num_steps, lo, hi, rho)
+        assert got.dtype == torch.float64 and torch.equal(got, written_out(num_steps, lo, hi, rho)), (lo, hi, rho)
+    free = StubNet()
+    grid, plain_ = sampler.grid_schedule(free, num_steps, 0.002, 80, 7), plain.edm_schedule(free, num_steps, 0.002, 80, 7)
+    assert torch.equal(grid, plain_) and torch.equal(grid, torch.cat([written_out(num_steps, 0.002, 80, 7), torch.zeros(1, dtype=torch.float64)]))
+    cfg = iddpm_imagenet64()
+    assert cfg.sigma_min > 0.002 and cfg.sigma_max > 80                               # the low end is cut, the high end is not
+    net = StubNet(cfg.sigma_min, cfg.sigma_max)
+    grid, plain_ = sampler.grid_schedule(net, num_steps, 0.002, 80, 7), plain.edm_schedule(net, num_steps, 0.002, 80, 7)
+    assert torch.equal(grid[:-1], written_out(num_steps, 0.002, 80, 7)) and torch.equal(plain_[:-1], written_out(num_steps, cfg.sigma_min, 80, 7))
+    assert float(grid[0]) == float(plain_[0]) and float(grid[num_steps - 1]) < 0.0021 < 0.0064 < float(plain_[num_steps - 1])
+    assert float(grid[-1]) == float(plain_[-1]) == 0.0 and not torch.equal(grid, plain_)
+
+
 SCHED_ARGS = ('sigma_min', 'sigma_max', 'rho', 'discretization', 'schedule', 'scaling', 'epsilon_s', 'C_1', 'C_2', 'M')
 STEP_ARGS = ('alpha', 'S_churn', 'S_min', 'S_max', 'S_noise')
 

@@ -168,6 +168,23 @@ def test_naive_sampler_in_lock_step(manifest, dtype):
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
+def test_the_naive_search_is_the_plain_sampler(manifest, dtype):
+    """generate_image_grid(NAIVE, seed=s) and plain.edm_sampler under torch.manual_seed(s) with host_randn_like are one loop (plain.heun_loop)
+    on one stream -- per step one float64 draw [2, ...] from the global generator -- over the same schedule (this network neither clamps nor
+    rounds it): the same latents and labels give the same final x bit for bit"""
+    from diffusion_tts_amd import plain, sampler as sm, scorers as S
+    net = hip_net(manifest, 'adm_tiny', dtype)
+    lat, lab = inputs(net, [5, 7])
+    res = sm.generate_image_grid(net, None, lat, lab, seed=3, gridw=2, gridh=1, device=torch.device(DEV), num_steps=STEPS,
+                                 sampling_method=sm.SamplingMethod.NAIVE, sampling_params=dict(scorer=S.BrightnessScorer()), compute_dtype=dtype,
+                                 verbose=False, **CHURN)
+    torch.manual_seed(3)
+    x = plain.edm_sampler(net, lat, lab, randn_like=plain.host_randn_like, num_steps=STEPS, **CHURN)
+    assert res['net_rows'] == 2 * (2 * STEPS - 1) and x.dtype == torch.float64
+    assert torch.equal(res['x'], x)
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('method', ['eps_greedy', 'beam'])
 def test_streams_are_isolated(manifest, method, dtype):
     """Equal seeds with equal inputs give bit-identical rows; a seed's result does not depend on its position or on its companions' seeds

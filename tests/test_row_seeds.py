@@ -87,8 +87,8 @@ def test_eps_greedy_draws_per_image():
                     continue
                 (g, mode, scale), (g1, mode1, scale1) = item, one
                 assert mode.shape == scale.shape == (3, len(order)) and mode.dtype == torch.int32 and scale.dtype == torch.float32
-                assert mode1.shape == scale1.shape == (3,)                         # without row_seeds: one coin per candidate, as ever
-                assert torch.equal(mode[:, b], mode1) and torch.equal(scale[:, b], scale1)
+                assert mode1.shape == scale1.shape == (3, 1)                       # without row_seeds: one lane, one coin per candidate, as ever
+                assert torch.equal(mode[:, b], mode1[:, 0]) and torch.equal(scale[:, b], scale1[:, 0])
                 for n in range(3):
                     assert g[n].shape == (len(order),) + SHAPE1 and torch.equal(g[n][b:b + 1], g1[n]), (s, n)
                     assert float(scale[n, b]) == 0.0 or int(mode[n, b]) == 1
@@ -97,7 +97,7 @@ def test_eps_greedy_draws_per_image():
     # a one-image source with its seed is the global stream after manual_seed, item for item
     for item, one in zip(eps_greedy_stream(sm._Source([5]), 1), solo[5]):
         if isinstance(item, tuple):
-            assert torch.equal(item[1].reshape(-1), one[1]) and torch.equal(item[2].reshape(-1), one[2])
+            assert torch.equal(item[1].reshape(-1), one[1][:, 0]) and torch.equal(item[2].reshape(-1), one[2][:, 0])
             assert all(torch.equal(a, b) for a, b in zip(item[0], one[0]))
         else:
             assert torch.equal(item, one)
