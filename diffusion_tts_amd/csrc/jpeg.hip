@@ -68,7 +68,9 @@ __constant__ uint8_t c_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32,
                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-constexpr int kBlockBufBytes = 256;      // bit-buffer bytes per 8x8 block: a block costs at most 64 * (16 + 11) bits = 216 bytes
+constexpr int kBlockMaxBits = 64 * (16 + 11);      // the most an 8x8 block costs: 64 coefficients of a 16-bit code and 11 value bits
+constexpr int kBlockBufBytes = 256;                // bit-buffer bytes per 8x8 block: kBlockMaxBits = 1728 bits = 216 bytes
+static_assert(kBlockMaxBits <= 8 * kBlockBufBytes, "a block's bits must fit its stretch of the bit buffer");
 constexpr int kBlockBufWords = kBlockBufBytes / 4;
 
 // ---- stage A ----------------------------------------------------------------------------------------------------------------------
@@ -286,7 +288,9 @@ constexpr int kHeaderBytes = 2 + (4 + 14) + 2 * (4 + 1 + 64) + (4 + 6 + 3 * 3) +
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 inline bool shape_ok(int n, int h, int w) {
   return n >= 1 && n <= 65535 && h >= 16 && w >= 16 && h % 16 == 0 && w % 16 == 0 && h <= 16384 && w <= 16384 &&
-         (int64_t)n * (h / 16) * (w / 16) * 6 <= (1 << 24);
+         (int64_t)n * (h / 16) * (w / 16) * 6 <= (1 << 24) &&
+         // bit counts, offsets and positions are int: an image's blocks, at the most a block costs, must stay below 2^31 bits
+         (int64_t)(h / 16) * (w / 16) * 6 * kBlockMaxBits < ((int64_t)1 << 31);
 }
 struct Layout {
   int nb;                                   // 8x8 blocks per image
@@ -311,7 +315,7 @@ extern "C" int64_t dts_jpeg_workspace_bytes(int n, int h, int w) { return shape_
 extern "C" int dts_jpeg_size(const uint8_t* img, int32_t* sizes, int n, int h, int w, const uint16_t* qtab, void* workspace,
                              int64_t workspace_bytes, int16_t* coef_out, dts_stream s) {
   DTS_CHECK_ARG(img && sizes && qtab && workspace, "dts_jpeg_size: null pointer");
-  DTS_CHECK_ARG(shape_ok(n, h, w), "dts_jpeg_size: n=%d h=%d w=%d: whole 16x16 MCUs only (h, w multiples of 16), 1 <= n <= 65535", n, h, w);
+  DTS_CHECK_ARG(shape_ok(n, h, w), "dts_jpeg_size: n=%d h=%d w=%d: whole 16x16 MCUs only (h, w multiples of 16), 1 <= n <= 65535, blocks per image * %d bits < 2^31", n, h, w, kBlockMaxBits);
   const Layout L = layout(n, h, w);
   DTS_CHECK_ARG(workspace_bytes >= L.bytes && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
                 "dts_jpeg_size: workspace of %lld bytes, 16-byte aligned, needed (dts_jpeg_workspace_bytes); got %lld", (long long)L.bytes,

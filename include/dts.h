@@ -415,7 +415,9 @@ int dts_u8_to_unit_f32(const uint8_t* img, float* out, int64_t count, dts_stream
  * the entropy-coded bytes in a scratch bit buffer (for the count of 0xFF bytes, each of which the file follows with a stuffed 0x00), plus the
  * fixed header and the EOI marker.  Integer arithmetic throughout: the result is exact, not an estimate.
  * img uint8 NCHW [n][3][h][w] (what dts_quantize_u8 writes); h and w multiples of 16 (whole MCUs; other sizes return DTS_ERR_ARG: a partial MCU
- * is completed by libjpeg with dummy blocks, a rule this entry does not implement), 1 <= n <= 65535.
+ * is completed by libjpeg with dummy blocks, a rule this entry does not implement), 1 <= n <= 65535, h, w <= 16384, n * blocks <= 2^24, and
+ * blocks * 1728 < 2^31 (blocks = h/16 * w/16 * 6 per image; 1728 = 64 * (16 + 11) bits, the most one block can cost): bit counts and offsets
+ * are int, so an image whose scan could reach 2^31 bits is refused (DTS_ERR_ARG), not counted wrongly.  That is 207 126 MCUs, e.g. 7280 x 7280.
  * qtab: device uint16 [2][64], the luma and chroma quantisation tables for q in natural (row-major) order.
  * workspace: device scratch of at least dts_jpeg_workspace_bytes(n, h, w) bytes, 16-byte aligned; the query returns 0 for a refused shape.
  * coef_out (nullable): int16 [n][blocks][64], the quantised coefficients in zigzag order, blocks in scan order (per 16x16 MCU, row-major over

@@ -90,3 +90,60 @@ def layer_norm_vectors(c):
 
 # c -> (register vectors in use, lanes of the last one): 8 is the single-lane row, 1544 the fourth vector on ONE lane, 2048 all four whole
 LAYER_NORM_WIDTHS = {8: (1, 1), 1544: (4, 1), 2048: (4, 64)}
+
+
+# ---- dts_jpeg_size (csrc/jpeg.hip) ------------------------------------------------------------------------------------------------------------
+JPEG_BLOCK_BUF_BYTES = 256          # bit-buffer bytes per 8x8 block (kBlockBufBytes)
+JPEG_BLOCK_MAX_BITS = 64 * (16 + 11)     # the most a block costs: 64 coefficients of a 16-bit code and 11 value bits (kBlockMaxBits)
+JpegLayout = collections.namedtuple('JpegLayout', 'nb coef bitoff totals bitbuf bytes')
+
+
+def align256(x):
+    return (x + 255) & ~255
+
+
+def jpeg_layout(n, h, w):
+    """byte offsets of the workspace's four arrays (layout() of the host part): int16 coefficients [n][nb][64], int bit counts / offsets
+    [n][nb], int totals [n], the bit buffer of 256 bytes per block; every array starts on a multiple of 256 bytes"""
+    nb = (h // 16) * (w // 16) * 6
+    blocks = n * nb
+    coef = 0
+    bitoff = coef + align256(blocks * 128)
+    totals = bitoff + align256(blocks * 4)
+    bitbuf = totals + align256(n * 4)
+    return JpegLayout(nb, coef, bitoff, totals, bitbuf, bitbuf + align256(blocks * JPEG_BLOCK_BUF_BYTES))
+
+
+def jpeg_shape_ok(n, h, w):
+    """shape_ok() of the host part: whole MCUs, the caps on n, h, w and on all blocks of a call, and the bits of one image's scan -- at the
+    most a block can cost -- below 2^31, because bit counts, offsets and positions are int"""
+    mcus = (h // 16) * (w // 16)
+    return (1 <= n <= 65535 and h >= 16 and w >= 16 and h % 16 == 0 and w % 16 == 0 and h <= 16384 and w <= 16384
+            and n * mcus * 6 <= 1 << 24 and mcus * 6 * JPEG_BLOCK_MAX_BITS < 1 << 31)
+
+
+def jpeg_scan_plan(nb):
+    """jpeg_scan_kernel, one workgroup of 256 threads per image: (per = blocks a thread sums and rewrites, busy = threads that own at least
+    one block, last = blocks of the last busy thread); thread t owns [min(t * per, nb), min(t * per + per, nb))"""
+    per = ceil_div(nb, 256)
+    busy = ceil_div(nb, per)
+    return per, busy, nb - (busy - 1) * per
+
+
+# (h, w) -> (nb, per, busy, last) of every shape the stream tests run: one block per thread with idle threads (nb <= 256), 2 and 3 per
+# thread with the upper threads clamped to nothing, 4 per thread with a last busy thread that owns 2 (the only clamp of `hi`: nb is a
+# multiple of 6, so per = 2 and 3 divide it), and 24 per thread with every thread busy
+JPEG_SCAN_SHAPES = {
+    (16, 16): (6, 1, 6, 1),
+    (32, 32): (24, 1, 24, 1),
+    (64, 64): (96, 1, 96, 1),
+    (48, 80): (90, 1, 90, 1),
+    (80, 48): (90, 1, 90, 1),
+    (112, 112): (294, 2, 147, 2),
+    (176, 160): (660, 3, 220, 3),
+    (48, 688): (774, 4, 194, 2),
+    (512, 512): (6144, 24, 256, 24),
+}
+# (n, h, w) of every call of the stream tests
+JPEG_STREAM_CALLS = [(9, 16, 16), (9, 48, 80), (9, 80, 48), (9, 112, 112), (9, 176, 160), (9, 48, 688), (1, 512, 512), (9, 32, 32),
+                     (1, 64, 64), (5, 64, 64), (64, 64, 64)]

@@ -35,7 +35,7 @@ test does for erfc): expf 3 ulp, logf 3 ulp, sinf / cosf 4 ulp, sqrtf 3 ulp, div
 test_grid_stride_wrap runs every grid-stride kernel once at 524 288 + 257 elements -- one more than the 2048 x 256 threads a launch is
 capped at -- against the same references: the second trip of the loop.
 
-Left out because already held exactly elsewhere: resample_u8 and lut_u8_f32 (tests/test_clip_preprocess.py), candidate_noise_sd
+Left out because already held exactly elsewhere: resample_u8 and lut_u8_f32 (tests/test_gpu_clip_preprocess_ops.py), candidate_noise_sd
 (tests/test_gpu_sd.py), split2_f16 / split3_f16 (tests/test_gpu_resample.py: every finite float16 value and its float32 neighbours
 against the bit models of tests/resample_reference.py).
 """

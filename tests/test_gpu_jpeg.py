@@ -1,7 +1,11 @@
 """GPU: ops.jpeg_size / CompressibilityScorer(codec='hip') against Pillow itself -- the byte length of the file
 `PIL.Image.save(format='JPEG', quality=q)` writes, exact (no tolerance anywhere in this file), the quantised coefficients against an
 integer numpy model of the transform stage, the scorer against the default codec and the reference-made fixture, one search with
-either codec, and the refusals."""
+either codec, and the refusals.
+
+Every stage of dts_jpeg_size is also held to the stream of Pillow's own file, entropy-decoded on the CPU (jpeg_helpers.decode_scan): the
+coefficients, every block's bit offset, the bit total, every bit of the emitted stream and the zeros behind it, then the size -- in a
+workspace the test owns, pre-filled with 0xFF between guard bands, read by the layout tests/launch_rules.py restates."""
 import re
 
 import numpy as np
@@ -11,8 +15,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from helpers import tiny_edm, T                                                          # noqa: E402
-from jpeg_helpers import ZIGZAG, make_images, parse_segments, pil_jpeg, zrl_image       # noqa: E402
-from diffusion_tts_amd import ops, scorers                                               # noqa: E402
+import launch_rules as R                                                                # noqa: E402
+from jpeg_helpers import (all_kinds, decode_scan, make_images, model_coefficients, parse_segments, pil_jpeg, stream_bits,     # noqa: E402
+                          zrl_image)
+from diffusion_tts_amd import _lib, ops, scorers                                              # noqa: E402
 from diffusion_tts_amd.hashing import seed0_scale                                        # noqa: E402
 
 DEV = 'cuda'
@@ -90,62 +96,132 @@ def test_inputs_reach_byte_stuffing_zrl_and_blocks_without_eob():
     assert np.array_equal(sizes.cpu().numpy(), pil_sizes(imgs))
 
 
+# ---- every stage against the decoded stream of Pillow's file -----------------------------------------------------------------------------
+GUARD = 4096
+
+
+def run_stages(imgs, quality):
+    """dts_jpeg_size on imgs uint8 [n, 3, h, w] with a workspace, a coefficient output and a size output that each sit between guard bands
+    in a buffer pre-filled with 0xFF -> (sizes, coefficients, the workspace's bytes), numpy; asserts that nothing outside them was written"""
+    n, _, h, w = imgs.shape
+    lay = R.jpeg_layout(n, h, w)
+    need = _lib.load().dts_jpeg_workspace_bytes(n, h, w)
+    assert need == lay.bytes, (need, lay)
+    dev_img = torch.from_numpy(imgs).to(DEV)
+    qtab = torch.tensor(ops.jpeg_quant_tables(quality), dtype=torch.int16, device=DEV)
+    bufs = {name: torch.full((GUARD + nbytes + GUARD,), 0xFF, dtype=torch.uint8, device=DEV)
+            for name, nbytes in (('workspace', lay.bytes), ('coef', n * lay.nb * 128), ('sizes', n * 4))}
+    ptr = {name: b.data_ptr() + GUARD for name, b in bufs.items()}
+    assert all(p % 16 == 0 for p in ptr.values())
+    ops._call('dts_jpeg_size', dev_img.data_ptr(), ptr['sizes'], n, h, w, qtab.data_ptr(), ptr['workspace'], lay.bytes, ptr['coef'])
+    torch.cuda.synchronize()
+    host = {name: b.cpu().numpy() for name, b in bufs.items()}
+    for name, b in host.items():
+        assert (b[:GUARD] == 0xFF).all() and (b[-GUARD:] == 0xFF).all(), f'{name}: wrote outside the buffer'
+    ws = host['workspace'][GUARD:-GUARD]
+    # with coef_out given the workspace's own coefficient array is not used, and the padding between the arrays never is
+    blocks = n * lay.nb
+    for lo, hi in ((lay.coef, lay.bitoff), (lay.bitoff + blocks * 4, lay.totals), (lay.totals + n * 4, lay.bitbuf),
+                   (lay.bitbuf + blocks * R.JPEG_BLOCK_BUF_BYTES, lay.bytes)):
+        assert (ws[lo:hi] == 0xFF).all(), f'workspace bytes [{lo}, {hi}) were written'
+    return (host['sizes'][GUARD:-GUARD].view(np.int32), host['coef'][GUARD:-GUARD].view(np.int16).reshape(n, lay.nb, 64), ws)
+
+
+def check_stages(imgs, quality, names=None):
+    """every image of the call: coefficients, block bit offsets, bit total, the stream bit for bit, zeros behind it, and the size"""
+    n, _, h, w = imgs.shape
+    lay = R.jpeg_layout(n, h, w)
+    sizes, coef, ws = run_stages(imgs, quality)
+    bitoff = ws[lay.bitoff:lay.bitoff + n * lay.nb * 4].view(np.int32).reshape(n, lay.nb)
+    totals = ws[lay.totals:lay.totals + n * 4].view(np.int32)
+    # bit i of the stream is bit 31 - (i & 31) of word i >> 5: the words' big-endian bytes are the stream's bytes
+    words = ws[lay.bitbuf:lay.bitbuf + n * lay.nb * R.JPEG_BLOCK_BUF_BYTES].view('<u4').reshape(n, lay.nb * R.JPEG_BLOCK_BUF_BYTES // 4)
+    for im in range(n):
+        what = f'{h}x{w} quality {quality} image {im}' + (f' ({names[im]})' if names else '')
+        data = pil_jpeg(imgs[im], quality)
+        ref = decode_scan(data)
+        assert ref.coef.shape == (lay.nb, 64)
+        if not np.array_equal(coef[im], ref.coef):
+            b, k = np.argwhere(coef[im] != ref.coef)[0]
+            raise AssertionError(f'{what}: coefficients differ first in block {b} at zigzag position {k}: {coef[im][b, k]}, Pillow {ref.coef[b, k]}')
+        if not np.array_equal(bitoff[im], ref.start):
+            b = int(np.nonzero(bitoff[im] != ref.start)[0][0])
+            raise AssertionError(f'{what}: bit offsets differ first at block {b}: {bitoff[im][b]}, Pillow {ref.start[b]}')
+        assert totals[im] == ref.total, f'{what}: {totals[im]} bits, Pillow {ref.total}'
+        got = stream_bits(words[im].astype('>u4').tobytes())
+        want = stream_bits(ref.stream, ref.total)
+        if not np.array_equal(got[:ref.total], want):
+            i = int(np.nonzero(got[:ref.total] != want)[0][0])
+            b = int(np.searchsorted(ref.start, i, side='right')) - 1
+            raise AssertionError(f'{what}: the stream differs first at bit {i} (bit {i - ref.start[b]} of block {b}): {got[i]}, Pillow {want[i]}')
+        stray = np.nonzero(got[ref.total:])[0]
+        assert len(stray) == 0, f'{what}: {len(stray)} bits set behind the end of the stream ({ref.total}), the first at bit {ref.total + int(stray[0])}'
+        assert sizes[im] == len(data), f'{what}: size {sizes[im]}, Pillow {len(data)} ({ref.stuffed} stuffed bytes)'
+    return sizes
+
+
+def scan_plan_holds(h, w):
+    nb, per, busy, last = R.JPEG_SCAN_SHAPES[(h, w)]
+    assert R.jpeg_layout(1, h, w).nb == nb and R.jpeg_scan_plan(nb) == (per, busy, last)
+    return per, busy
+
+
+@pytest.mark.parametrize('quality', [80, 100])
+@pytest.mark.parametrize('h,w', [(16, 16), (48, 80), (80, 48), (112, 112), (176, 160), (48, 688)])
+def test_every_stage_equals_pillows_stream(h, w, quality):
+    """One image of every kind in one call.  16x16: one MCU; 48x80 and 80x48: rows != columns either way; 112x112, 176x160, 48x688: 2, 3, 4
+    blocks per thread in the offset scan with the upper threads clamped to nothing (48x688: the last busy thread stops short).  Quality 100
+    brings the DC categories 11 and the AC categories 10 of the constructed images (tests/test_jpeg_decoder_cpu.py)."""
+    per, busy = scan_plan_holds(h, w)
+    assert (per, busy < 256) == {(16, 16): (1, True), (48, 80): (1, True), (80, 48): (1, True), (112, 112): (2, True), (176, 160): (3, True),
+                                 (48, 688): (4, True)}[(h, w)]
+    names, imgs = all_kinds(h, w)
+    assert (len(imgs), h, w) in R.JPEG_STREAM_CALLS
+    check_stages(imgs, quality, names)
+
+
+def test_every_stage_equals_pillows_stream_512():
+    """6 144 blocks: 24 per thread in the offset scan, every thread busy; `smooth` is the kind whose stream holds no 0xFF byte, so that the
+    size alone cannot see it"""
+    assert scan_plan_holds(512, 512) == (24, 256) and (1, 512, 512) in R.JPEG_STREAM_CALLS
+    check_stages(make_images('smooth', 1, 512, 512), 80, ['smooth'])
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('n', [1, 5, 64])
+def test_every_stage_equals_pillows_stream_over_batches(n, kind):
+    """every image has its own offsets, its own total and its own stretch of the bit buffer"""
+    assert (n, 64, 64) in R.JPEG_STREAM_CALLS and scan_plan_holds(64, 64) == (1, 96)
+    check_stages(make_images(kind, n, 64, 64), 80, [kind] * n)
+
+
+@pytest.mark.parametrize('quality', [1, 49, 50, 80, 100])
+def test_every_stage_equals_pillows_stream_over_qualities(quality):
+    """quality 1: every table entry 255 and runs of 62 in both tables (the tiled zrl_image); 49 / 50: either side of the scale rule"""
+    names, imgs = all_kinds(32, 32, seed=quality)
+    assert (len(imgs), 32, 32) in R.JPEG_STREAM_CALLS and scan_plan_holds(32, 32) == (1, 24)
+    check_stages(imgs, quality, names)
+
+
+def test_cached_workspace_serves_smaller_and_differently_shaped_calls():
+    """ops.jpeg_size keeps one workspace per device and reuses it for any call it is large enough for: a small call after a large one
+    finds the large one's bits and offsets in it.  Each call equals Pillow and its own result from an empty cache."""
+    calls = [('noise', 64, 64, 64, 100), ('flat', 1, 16, 16, 80), ('smooth', 5, 32, 32, 80)]
+    ops._JPEG_WS.clear()
+    reused = [gpu_sizes(make_images(kind, n, h, w), q) for kind, n, h, w, q in calls]
+    assert len(ops._JPEG_WS) == 1
+    (ws,) = ops._JPEG_WS.values()
+    assert ws.numel() == R.jpeg_layout(64, 64, 64).bytes                    # the first call's: the later ones did not replace it
+    for (kind, n, h, w, q), got in zip(calls, reused):
+        imgs = make_images(kind, n, h, w)
+        ops._JPEG_WS.clear()
+        fresh = gpu_sizes(imgs, q)
+        want = pil_sizes(imgs, q)
+        print(f'{kind} n={n} {h}x{w} quality {q}: Pillow {want[:5]}, reused workspace {got[:5]}, fresh {fresh[:5]}')
+        assert np.array_equal(got, want) and np.array_equal(fresh, want), (kind, n, h, w)
+
+
 # ---- stage A alone ----------------------------------------------------------------------------------------------------------------------
-BASE_LUMA = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-             18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99]
-BASE_CHROMA = [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32
-
-
-def model_fdct(b):
-    """the "slow integer" 8x8 forward DCT over the last two axes of an int64 array: 13-bit constants, 2 extra bits through the row pass,
-    rounding right shifts, output scaled by 8"""
-    def one_pass(d, first):
-        d = [d[..., i] for i in range(8)]
-        t0, t7, t1, t6, t2, t5, t3, t4 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6], d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
-        t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
-        n = 11 if first else 15
-
-        def ds(x, n=n):
-            return (x + (1 << (n - 1))) >> n
-        o = [None] * 8
-        o[0], o[4] = ((t10 + t11) << 2, (t10 - t11) << 2) if first else (ds(t10 + t11, 2), ds(t10 - t11, 2))
-        z1 = (t12 + t13) * 4433
-        o[2], o[6] = ds(z1 + t13 * 6270), ds(z1 - t12 * 15137)
-        z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
-        z5 = (z3 + z4) * 9633
-        z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
-        o[7], o[5], o[3], o[1] = ds(t4 * 2446 + z1 + z3), ds(t5 * 16819 + z2 + z4), ds(t6 * 25172 + z2 + z3), ds(t7 * 12299 + z1 + z4)
-        return np.stack(o, axis=-1)
-    rows = one_pass(b, True)
-    return np.swapaxes(one_pass(np.swapaxes(rows, -1, -2), False), -1, -2)
-
-
-def model_coefficients(img, quality):
-    """img uint8 [3, h, w] -> int16 [h/16 * w/16 * 6, 64]: colour, 2x2 chroma mean, level shift, DCT, quantisation; zigzag, scan order"""
-    R, G, B = (img[i].astype(np.int64) for i in range(3))
-    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
-    Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
-    Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
-    h, w = Y.shape
-    bias = np.tile(np.array([1, 2]), w // 4)[None, :]
-    Cb, Cr = ((c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + bias) >> 2 for c in (Cb, Cr))
-    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
-    ql, qc = (np.clip((np.array(base) * scale + 50) // 100, 1, 255).reshape(8, 8) * 8 for base in (BASE_LUMA, BASE_CHROMA))
-    px, q8 = [], []
-    for my in range(h // 16):
-        for mx in range(w // 16):
-            for by in range(2):
-                for bx in range(2):
-                    px.append(Y[my * 16 + by * 8:my * 16 + by * 8 + 8, mx * 16 + bx * 8:mx * 16 + bx * 8 + 8])
-                    q8.append(ql)
-            for c in (Cb, Cr):
-                px.append(c[my * 8:my * 8 + 8, mx * 8:mx * 8 + 8])
-                q8.append(qc)
-    c, q8 = model_fdct(np.stack(px) - 128), np.stack(q8)
-    v = np.sign(c) * ((np.abs(c) + (q8 >> 1)) // q8)
-    return v.reshape(-1, 64)[:, ZIGZAG].astype(np.int16)
-
-
 @pytest.mark.parametrize('kind', ['noise', 'smooth'])
 def test_coefficients_equal_the_integer_model(kind):
     imgs = make_images(kind, 2, 32, 32, seed=3)

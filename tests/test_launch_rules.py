@@ -1,6 +1,7 @@
 """CPU: the tables of tests/launch_rules.py against its restatement of the launchers' rules -- each case that exists to take the second
-trip of a size-driven loop does take it, by the margin its comment states.  No GPU and nothing of the library: if a cap or a heuristic
-changes there, the restatement has to follow, and these assertions then say which cases lost their coverage."""
+trip of a size-driven loop does take it, by the margin its comment states.  No GPU and, but for one host-only size query (the JPEG workspace), nothing of
+the library: if a cap or a heuristic changes there, the restatement has to follow, and these assertions then say which cases lost their
+coverage."""
 import pytest
 
 import launch_rules as L
@@ -60,3 +61,34 @@ def test_layer_norm_widths():
     for c, want in L.LAYER_NORM_WIDTHS.items():
         assert L.layer_norm_vectors(c) == want and c % 8 == 0 and c <= 2048
     assert all(L.layer_norm_vectors(c)[0] <= 3 for c in (64, 128, 320, 1024, 1280))      # the older widths never reach the fourth vector
+
+
+# ---- dts_jpeg_size --------------------------------------------------------------------------------------------------------------------------
+def test_jpeg_scan_shapes_take_every_form_of_the_per_thread_loop():
+    for (h, w), (nb, per, busy, last) in L.JPEG_SCAN_SHAPES.items():
+        assert L.jpeg_layout(1, h, w).nb == nb and L.jpeg_scan_plan(nb) == (per, busy, last), (h, w)
+        assert (busy - 1) * per + last == nb and 1 <= last <= per and busy <= 256
+    plans = set(v[1:] for v in L.JPEG_SCAN_SHAPES.values())
+    assert {p[0] for p in plans} >= {1, 2, 3, 4, 24}
+    assert any(per > 1 and busy < 256 and last == per for per, busy, last in plans)        # trailing threads own nothing
+    assert any(per > 1 and busy < 256 and last < per for per, busy, last in plans)         # ... and the last busy one stops short of `per`
+    assert any(per > 1 and busy == 256 for per, busy, last in plans)
+    assert {(h, w) for _, h, w in L.JPEG_STREAM_CALLS} == set(L.JPEG_SCAN_SHAPES)
+
+
+def test_jpeg_layout_equals_the_librarys_workspace_query():
+    """dts_jpeg_workspace_bytes is host arithmetic: the library loads and answers without a GPU.  The stage tests read the workspace by the
+    restated layout, so a changed layout fails here first."""
+    from diffusion_tts_amd import _lib
+    lib = _lib.load()
+    shapes = L.JPEG_STREAM_CALLS + [(1, 16, 16), (3, 16, 32), (64, 512, 512), (64, 1024, 1024), (65535, 16, 16)]
+    for n, h, w in shapes:
+        lay = L.jpeg_layout(n, h, w)
+        assert L.jpeg_shape_ok(n, h, w) and lib.dts_jpeg_workspace_bytes(n, h, w) == lay.bytes, (n, h, w)
+        assert lay.coef == 0 and lay.coef < lay.bitoff < lay.totals < lay.bitbuf < lay.bytes
+        assert all(v % 256 == 0 for v in lay[1:])
+        assert lay.bitoff >= n * lay.nb * 128 and lay.totals - lay.bitoff >= n * lay.nb * 4 and lay.bitbuf - lay.totals >= n * 4
+        assert lay.bytes - lay.bitbuf >= n * lay.nb * L.JPEG_BLOCK_BUF_BYTES
+    assert L.JPEG_BLOCK_MAX_BITS <= 8 * L.JPEG_BLOCK_BUF_BYTES
+    for n, h, w in [(0, 16, 16), (65536, 16, 16), (1, 8, 16), (1, 24, 16), (1, 16, 16400), (2797, 512, 512)]:
+        assert not L.jpeg_shape_ok(n, h, w) and lib.dts_jpeg_workspace_bytes(n, h, w) == 0, (n, h, w)
