@@ -129,8 +129,23 @@ __device__ __forceinline__ void att_block(const AttP& p, int& nh, int& qb) {
 //   * the select to -inf that masks the tail past t takes the lane's own limit (nothing of a disallowed key reaches the output as long
 //     as v is finite); only the diagonal tile (causal) and the tile that holds kend pay for it.
 //   * key rows from kend on are staged as zeros, not read.
-template <typename T, int D, int QT, int DV = D, bool PREF = true, bool DB = false, bool DMA = false, bool MASK = false>
+// DM < D (head dims 40 and 80 of the SD-1.x heads; DV = D, PREF, no DMA, no MASK; their third, 160, is a multiple of 32 and simply D = DM = 160,
+// 5 k-steps and 10 value tiles with nothing to pad): DM is the head dim IN MEMORY -- q | k | v blocks and out
+// are heads * DM wide, a head's row is 2 DM bytes (80 / 160 / 320: whole 16-byte chunks) -- and D stays the on-chip K width, DM rounded up to
+// the 32 of the matrix instruction (64 / 96 / 160: 2 / 3 / 5 k-steps).  The zero padding that the caller would otherwise keep in HBM happens here:
+//   * 16-byte chunks c >= DM/8 of a Q fragment and of a K or V row in LDS are zeros that are never loaded (the bytes there belong to the next
+//     head or the next block of the row).  A zero tail adds exact zeros to the f32 scores, so S, the softmax and P are those of a head
+//     zero-padded to 64 / 128 / 256 in memory;
+//   * the staging keeps ONE chunk grid for K and V, the on-chip one: CH = D/8 = 8 / 12 / 20 chunks per row, NCH = 64 CH / 256 = 2 / 3 / 5 per
+//     thread -- whole numbers, where the DM/8 = 5 / 10 / 20 chunks in memory give 1.25 / 2.5 / 5, i.e. the same 2 / 3 / 5 prefetch registers
+//     with a ragged last trip.  A thread whose chunk lies in the tail stages a zero it never loaded;
+//   * V rows sit in LDS at the K stride (ROWB = 2 D + 32 = 160 / 224 / 352 B: 40 / 56 / 88 dwords, each 8 x an odd number, so eight
+//     consecutive rows start 8 banks apart over all 64 banks exactly as at 160 / 288 / 544 B: the b128 row reads and the transposed reads
+//     stay conflict-free), but only DT = ceil(DM/16) = 3 / 5 / 10 value tiles are multiplied.  NSL stays 1: these are not value slices;
+//   * the store writes channels < DM only: at DM = 40 lane groups 2 and 3 of the third tile hold channels 40..47, the next head's (or row's).
+template <typename T, int D, int QT, int DV = D, bool PREF = true, bool DB = false, bool DMA = false, bool MASK = false, int DM = D>
 __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
+  static_assert(DM == D || (DM < D && DM % 8 == 0 && D == (DM + 31) / 32 * 32 && DV == D && PREF && !DMA && !MASK), "head dim in memory: whole 16-byte chunks, K width the next multiple of 32, the register-prefetch forms");
   static_assert(!DB || PREF, "double buffering rides on the register prefetch");
   static_assert(!DMA || (D == 512 && DV == 256 && QT == 1 && !PREF && !DB), "LDS-DMA staging: the head-dim-512 form only");
   static_assert(!MASK || (D == 64 && QT == 1 && DV == D && PREF && !DB && !DMA), "masked form: head dim 64, one query tile, single-buffered register prefetch");
@@ -139,8 +154,9 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
   constexpr int CH = D / 8;                        // 16-byte chunks per K row
   constexpr int CHV = DV / 8;                      // ... per V-slice row
   constexpr int KSTEPS = D / 32;                   // MFMA k-steps for Q.K
-  constexpr int DT = DV / 16;                      // output d tiles
-  constexpr int NSL = D / DV;                      // value slices
+  constexpr int CHM = DM / 8;                      // 16-byte chunks per row that exist in memory (DM < D: chunks CHM .. CH-1 are zeros on chip)
+  constexpr int DT = DM == D ? DV / 16 : (DM + 15) / 16;   // output d tiles (DM < D: the tiles that hold a channel < DM, not the K width's)
+  constexpr int NSL = D / DV;                      // value slices (1 when DM < D: fewer value tiles than k-steps is not a slice)
   constexpr bool WIDE = DMA;                       // fragment reads issued four at a time (see the Q.K^T loop); at D = 256, with the register
                                                    // prefetch at the 256-VGPR limit, hipcc serialises them again and the DDPM++ step measured 1-3 % slower
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -154,9 +170,9 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
   int vs = 0;
   if constexpr (NSL > 1) { vs = nh % NSL; nh /= NSL; }
   const int n = nh / p.heads, head = nh - n * p.heads;
-  const int C = p.heads * D;
+  const int C = p.heads * DM;
   const size_t rowstride = (size_t)3 * C * ES;
-  const char* base = p.qkv + (size_t)n * p.t * rowstride + (size_t)head * D * ES;
+  const char* base = p.qkv + (size_t)n * p.t * rowstride + (size_t)head * DM * ES;
   const int q0 = qblk * (64 * QT) + wid * (16 * QT);
   // kend: the keys of this sample; lim: this lane's query sees keys < lim (>= 1); ntiles: the key tiles this block walks
   int kend = p.t, lim = p.t, ntiles = (p.t + 63) / 64;
@@ -174,7 +190,7 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
     for (int s = 0; s < KSTEPS; ++s) {
       const int qrow = q0 + qt * 16 + lq;
       qf[qt][s] = make_uint4(0, 0, 0, 0);
-      if (qrow < p.t) qf[qt][s] = *reinterpret_cast<const uint4*>(base + (size_t)qrow * rowstride + (lg + 4 * s) * 16);
+      if (qrow < p.t && (DM == D || lg + 4 * s < CHM)) qf[qt][s] = *reinterpret_cast<const uint4*>(base + (size_t)qrow * rowstride + (lg + 4 * s) * 16);
     }
   // softmax(q.k*scale) == softmax2(q.k * scale*log2e): q stays as stored, S = q.k accumulates un-scaled in f32, and sc2 = scale*log2e
   // is applied in f32 inside the exponent's fused multiply-add, exp2(fma(s, sc2, -m*sc2)) (see the online softmax below).
@@ -204,12 +220,12 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
   _Pragma("unroll") for (int u = 0; u < NCH; ++u) {                                               \
     const int idx = tid + 256 * u, r = idx / CH, c = idx - r * CH;                                \
     pk[u] = make_uint4(0, 0, 0, 0);                                                               \
-    if ((key0_) + r < kend) pk[u] = *reinterpret_cast<const uint4*>(base + (size_t)((key0_) + r) * rowstride + c * 16 + (size_t)C * ES); \
+    if ((key0_) + r < kend && (DM == D || c < CHM)) pk[u] = *reinterpret_cast<const uint4*>(base + (size_t)((key0_) + r) * rowstride + c * 16 + (size_t)C * ES); \
   }                                                                                               \
   _Pragma("unroll") for (int u = 0; u < NCHV; ++u) {                                              \
     const int idx = tid + 256 * u, r = idx / CHV, c = idx - r * CHV;                              \
     pv[u] = make_uint4(0, 0, 0, 0);                                                               \
-    if ((key0_) + r < kend) pv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)((key0_) + r) * rowstride + c * 16); \
+    if ((key0_) + r < kend && (DM == D || c < CHM)) pv[u] = *reinterpret_cast<const uint4*>(vbase + (size_t)((key0_) + r) * rowstride + c * 16); \
   }
 #define ATT_STAGE_TILE(boff_)                                                                     \
   _Pragma("unroll") for (int u = 0; u < NCH; ++u) {                                               \
@@ -422,11 +438,14 @@ __global__ __launch_bounds__(256) void attention16_kernel(const AttP p) {
     const int qrow = q0 + qt * 16 + lq;
     if (qrow < p.t) {
       const float inv = 1.f / ol[qt][0];
-      T* orow = reinterpret_cast<T*>(p.out) + ((size_t)n * p.t + qrow) * C + head * D + vs * DV;
+      T* orow = reinterpret_cast<T*>(p.out) + ((size_t)n * p.t + qrow) * C + head * DM + vs * DV;
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
+      for (int dt = 0; dt < DT; ++dt) {
+        // DM = 40: channels 40..47 of the last tile are another block's to write
+        if constexpr (DM % 16 != 0) { if (dt * 16 + lg * 4 >= DM) continue; }
 #pragma unroll
         for (int r = 0; r < 4; ++r) st1<T>(orow + dt * 16 + lg * 4 + r, o[qt][dt][r] * inv);
+      }
     }
   }
 }
@@ -862,7 +881,7 @@ int launch_att(K kernel, const AttP& p0, size_t lds, hipStream_t st, int qblock 
 template <typename T>
 int att16(const AttP& p, hipStream_t st) {
   const int g_att_qt = dts_knob_get(DTS_KNOB_ATT_QT) > 0 ? dts_knob_get(DTS_KNOB_ATT_QT) : 0;    // DTS_ATT_QT=1|2 forces the query tiles per wave
-  const size_t lds = (size_t)2 * 64 * (p.d * 2 + 32);
+  const size_t lds = (size_t)2 * 64 * ((p.d + 31) / 32 * 32 * 2 + 32);       // K and V rows at the on-chip K width (the head dim up to a multiple of 32)
   // double-buffered tiles measured no faster (T=1024: 167.6 vs 166.3 us; T=256: 27.0 vs 25.7 us, profiles/r02_attention_variants.txt):
   // the barrier was not what the waves wait on.  Kept behind DTS_ATT_DB=1 for the record; default single-buffered.
   const bool db = dts_knob_get(DTS_KNOB_ATT_DB) == 1 && p.t > 64;
@@ -873,6 +892,14 @@ int att16(const AttP& p, hipStream_t st) {
         return db ? launch_att(attention16_kernel<T, 64, 2, 64, true, true>, p, 2 * lds, st, 128)
                   : launch_att(attention16_kernel<T, 64, 2>, p, lds, st, 128);
       return db ? launch_att(attention16_kernel<T, 64, 1, 64, true, true>, p, 2 * lds, st) : launch_att(attention16_kernel<T, 64, 1>, p, lds, st);
+    case 40:    // head dim 40 in memory on the forms of 64, by the rule of 64
+      if (g_att_qt == 2 || (g_att_qt == 0 && p.t >= 256 && (long long)((p.t + 127) / 128) * p.n * p.heads >= 512))
+        return db ? launch_att(attention16_kernel<T, 64, 2, 64, true, true, false, false, 40>, p, 2 * lds, st, 128)
+                  : launch_att(attention16_kernel<T, 64, 2, 64, true, false, false, false, 40>, p, lds, st, 128);
+      return db ? launch_att(attention16_kernel<T, 64, 1, 64, true, true, false, false, 40>, p, 2 * lds, st)
+                : launch_att(attention16_kernel<T, 64, 1, 64, true, false, false, false, 40>, p, lds, st);
+    case 80: return launch_att(attention16_kernel<T, 96, 1, 96, true, false, false, false, 80>, p, lds, st);
+    case 160: return launch_att(attention16_kernel<T, 160, 1>, p, lds, st);     // a multiple of 32: nothing to pad, 5 k-steps and 10 value tiles
     case 128:
       return db ? launch_att(attention16_kernel<T, 128, 1, 128, true, true>, p, 2 * lds, st) : launch_att(attention16_kernel<T, 128, 1>, p, lds, st);
     case 256: return launch_att(attention16_kernel<T, 256, 1>, p, lds, st);
@@ -956,8 +983,8 @@ extern "C" int dts_attention_masked(const void* qkv, void* out, int dtype, int n
 extern "C" int dts_attention(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, dts_stream s) {
   DTS_CHECK_ARG(qkv && out, "dts_attention: null pointer");
   DTS_CHECK_ARG(n > 0 && t > 0 && heads > 0, "dts_attention: bad shape");
-  DTS_CHECK_ARG(d == 64 || d == 128 || d == 256 || (d == 512 && dtype != DTS_F32),
-                "dts_attention: head dim %d unsupported (64/128/256; 512 in the 16-bit types)", d);
+  DTS_CHECK_ARG(d == 64 || d == 128 || d == 256 || ((d == 512 || d == 40 || d == 80 || d == 160) && dtype != DTS_F32),
+                "dts_attention: head dim %d unsupported (64/128/256; 40/80/160/512 in the 16-bit types)", d);
   AttP p{(const char*)qkv, (char*)out, n, t, heads, d, scale * 1.4426950408889634f, 0, 1, 0};
   hipStream_t st = to_stream(s);
   switch (dtype) {

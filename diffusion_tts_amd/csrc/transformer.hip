@@ -45,12 +45,17 @@ struct XAttP {
   int qblocks, qchunks;          // blocks per (sample, head); chunks of 64 queries per block
 };
 
-template <typename T, int D>
+// DM < D (head dims 40 and 80 in memory on K widths 64 and 96; 160 is its own width), as in attention16_kernel: q, the k | v rows and out are
+// heads * DM wide, the staging walks the on-chip chunk grid and writes zeros it never loaded for chunks >= DM/8 (they are the next head's
+// bytes), the Q fragments get the same zero tail, ceil(DM/16) value tiles are multiplied and only channels < DM are stored.
+template <typename T, int D, int DM = D>
 __global__ __launch_bounds__(256) void cross_attention_kernel(const XAttP p) {
+  static_assert(DM == D || (DM < D && DM % 8 == 0 && D == (DM + 31) / 32 * 32), "head dim in memory: whole 16-byte chunks, K width the next multiple of 32");
   constexpr int ES = 2, ROWB = D * ES + 32;        // LDS row stride: conflict-free for the b128 row reads of K and the transposed reads of V
   constexpr int CH = D / 8;                        // 16-byte chunks per row
+  constexpr int CHM = DM / 8;                      // ... that exist in memory
   constexpr int KSTEPS = D / 32;
-  constexpr int DT = D / 16;
+  constexpr int DT = DM == D ? D / 16 : (DM + 15) / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sK = smem;
   char* sV = smem + p.tkp * ROWB;
@@ -58,10 +63,10 @@ __global__ __launch_bounds__(256) void cross_attention_kernel(const XAttP p) {
   const int lq = lane & 15, lg = lane >> 4;
   const int nh = blockIdx.x / p.qblocks, qblk = blockIdx.x - nh * p.qblocks;
   const int n = nh / p.heads, head = nh - n * p.heads;
-  const int C = p.heads * D;
+  const int C = p.heads * DM;
   int kvn = p.kv_rows ? p.kv_rows[n] : n;
   kvn = min(max(kvn, 0), p.kv_n - 1);              // memory safety only: the caller's map is in range
-  const char* kbase = p.kv + (size_t)kvn * p.tk * ((size_t)2 * C * ES) + (size_t)head * D * ES;
+  const char* kbase = p.kv + (size_t)kvn * p.tk * ((size_t)2 * C * ES) + (size_t)head * DM * ES;
   const size_t kvstride = (size_t)2 * C * ES;
 
   // ---- K and V of this (sample, head), zero rows from tk up to tkp (a multiple of 32: whole P.V k-steps)
@@ -70,7 +75,7 @@ __global__ __launch_bounds__(256) void cross_attention_kernel(const XAttP p) {
   for (int idx = tid; idx < nchunks; idx += 256) {
     const int r = idx / CH, c = idx - r * CH;
     uint4 k = make_uint4(0, 0, 0, 0), v = make_uint4(0, 0, 0, 0);
-    if (r < p.tk) {
+    if (r < p.tk && (DM == D || c < CHM)) {
       const char* src = kbase + (size_t)r * kvstride + c * 16;
       k = *reinterpret_cast<const uint4*>(src);
       v = *reinterpret_cast<const uint4*>(src + (size_t)C * ES);
@@ -83,7 +88,7 @@ __global__ __launch_bounds__(256) void cross_attention_kernel(const XAttP p) {
   const float sc2 = p.scale_log2e;
   const uint4 ones = make_uint4(XMma<T>::ONES2, XMma<T>::ONES2, XMma<T>::ONES2, XMma<T>::ONES2);
   const size_t qstride = (size_t)C * ES;
-  const char* qbase = p.q + (size_t)n * p.tq * qstride + (size_t)head * D * ES;
+  const char* qbase = p.q + (size_t)n * p.tq * qstride + (size_t)head * DM * ES;
 
   for (int qc = 0; qc < p.qchunks; ++qc) {
     const int q0 = (qblk * p.qchunks + qc) * 64 + wid * 16;
@@ -94,7 +99,7 @@ __global__ __launch_bounds__(256) void cross_attention_kernel(const XAttP p) {
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
       qf[s] = make_uint4(0, 0, 0, 0);
-      if (qrow < p.tq) qf[s] = *reinterpret_cast<const uint4*>(qbase + (size_t)qrow * qstride + (lg + 4 * s) * 16);
+      if (qrow < p.tq && (DM == D || lg + 4 * s < CHM)) qf[s] = *reinterpret_cast<const uint4*>(qbase + (size_t)qrow * qstride + (lg + 4 * s) * 16);
     }
     // ---- S^T: up to 8 tiles of 16 keys x 16 queries; lane holds keys j*16 + lg*4 + r of query lq
     f32x4_t sacc[8];
@@ -156,9 +161,11 @@ __global__ __launch_bounds__(256) void cross_attention_kernel(const XAttP p) {
     // ---- store: lane holds channels dt*16 + lg*4 .. +4 of query lq (8 bytes)
     if (qrow < p.tq) {
       const float inv = 1.f / ol[0];
-      char* orow = p.out + ((size_t)n * p.tq + qrow) * qstride + (size_t)head * D * ES;
+      char* orow = p.out + ((size_t)n * p.tq + qrow) * qstride + (size_t)head * DM * ES;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
+        // DM = 40: channels 40..47 of the last tile are another block's to write
+        if constexpr (DM % 16 != 0) { if (dt * 16 + lg * 4 >= DM) continue; }
         uint2 w;
         w.x = XMma<T>::pack2(o[dt][0] * inv, o[dt][1] * inv);
         w.y = XMma<T>::pack2(o[dt][2] * inv, o[dt][3] * inv);
@@ -193,8 +200,11 @@ int launch_xatt(K kernel, const XAttP& p, size_t lds, unsigned grid, hipStream_t
 
 template <typename T>
 int xatt(const XAttP& p, int d, unsigned grid, hipStream_t st) {
-  const size_t lds = (size_t)2 * p.tkp * (d * 2 + 32);
+  const size_t lds = (size_t)2 * p.tkp * ((d + 31) / 32 * 32 * 2 + 32);     // K and V rows at the on-chip K width (the head dim up to a multiple of 32)
   switch (d) {
+    case 40: return launch_xatt(cross_attention_kernel<T, 64, 40>, p, lds, grid, st);
+    case 80: return launch_xatt(cross_attention_kernel<T, 96, 80>, p, lds, grid, st);
+    case 160: return launch_xatt(cross_attention_kernel<T, 160>, p, lds, grid, st);
     case 64: return launch_xatt(cross_attention_kernel<T, 64>, p, lds, grid, st);
     case 128: return launch_xatt(cross_attention_kernel<T, 128>, p, lds, grid, st);
     case 256: return launch_xatt(cross_attention_kernel<T, 256>, p, lds, grid, st);
@@ -230,7 +240,7 @@ extern "C" int dts_cross_attention(const void* q, const void* kv, const int32_t*
   DTS_CHECK_ARG(kv_rows != nullptr || kv_n == n, "dts_cross_attention: %d key/value rows for %d samples need a kv_rows map", kv_n, n);
   int (*run)(const XAttP&, int, unsigned, hipStream_t) = nullptr;
   DTS_DISPATCH_16BIT("dts_cross_attention", dtype, run = xatt<T>);
-  DTS_CHECK_ARG(d == 64 || d == 128 || d == 256, "dts_cross_attention: head dim %d unsupported (64/128/256)", d);
+  DTS_CHECK_ARG(d == 64 || d == 128 || d == 256 || d == 40 || d == 80 || d == 160, "dts_cross_attention: head dim %d unsupported (40/64/80/128/160/256)", d);
   DTS_CHECK_ARG(scale > 0.f && isfinite(scale), "dts_cross_attention: scale must be positive and finite");
   DTS_CHECK_ARG(((uintptr_t)q | (uintptr_t)kv | (uintptr_t)out) % 16 == 0, "dts_cross_attention: pointers must be 16-byte aligned");
   if (tk > 128) {

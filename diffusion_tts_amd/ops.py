@@ -591,14 +591,17 @@ def fused_down_weight(w, taps=FIR_TAPS, cpad=None, out_dtype=torch.float32):
 
 
 # ---- attention ----------------------------------------------------------------------------------
-def attention(qkv, heads, scale, x3=False, split_out=False):
-    """qkv [n, t, 3*heads*d] (q|k|v blocks) -> [n, t, heads*d].  x3 (split-precision mode, float32 qkv or a SplitQKV, head dim 64): Q.K^T and
+def attention(qkv, heads, scale, x3=False, split_out=False, out=None):
+    """qkv [n, t, 3*heads*d] (q|k|v blocks) -> [n, t, heads*d] (dts_attention).  Head dims 64 / 128 / 256 in every dtype; 40 / 80 / 160 (the
+    SD-1.x heads, stored unpadded) and 512 in float16 / bfloat16.  out (the plain kernel only): written and returned where given.  x3 (split-precision mode, float32 qkv or a SplitQKV, head dim 64): Q.K^T and
     P.V on the 16-bit matrix cores with hi/lo operand pairs (dts_attention_x3) instead of the f32 matrix instruction; same accuracy.
     split_out (with x3): the result leaves as the operand image of the proj convolution (SplitAct [n, t, 1, C])."""
     n, t, c3 = qkv.shape
     c = c3 // 3
     d = c // heads
     pre = isinstance(qkv, SplitQKV)
+    if out is not None and (pre or x3 or split_out):
+        raise ValueError('attention: out= goes with the plain kernel (no x3, no split_out, no SplitQKV)')
     # (short sequences stay on the f32 kernel: at T = 64 the split pass alone costs what that launch does -- tools/att_bench.py --x3)
     if pre or (x3 and d == 64 and t >= 128 and qkv.dtype == torch.float32):
         if pre:
@@ -613,8 +616,8 @@ def attention(qkv, heads, scale, x3=False, split_out=False):
         out = torch.empty((n, t, c), dtype=torch.float32, device=qkv.device)
         _call('dts_attention_x3', _ptr(sp), _ptr(out), 0, n, t, heads, d, float(scale))
         return out
-    out = torch.empty((n, t, c), dtype=qkv.dtype, device=qkv.device)
-    _call('dts_attention', _ptr(qkv), _ptr(out), dt_code(qkv.dtype), n, t, heads, d, float(scale))
+    out = _out('attention', out, (n, t, c), qkv.dtype, qkv.device)
+    _call('dts_attention', _ptr(qkv), _ptr(out, 'out', qkv.dtype), dt_code(qkv.dtype), n, t, heads, d, float(scale))
     return out
 
 
@@ -665,7 +668,8 @@ def attention_x3_ok(t, d):
 
 
 def cross_attention(q, kv, heads, scale, kv_rows=None, out=None):
-    """q [n, tq, heads*d], kv [m, tk, 2*heads*d] (k | v blocks; 1 <= tk <= 128) -> [n, tq, heads*d] (dts_cross_attention; float16 / bfloat16).
+    """q [n, tq, heads*d], kv [m, tk, 2*heads*d] (k | v blocks; 1 <= tk <= 128) -> [n, tq, heads*d] (dts_cross_attention; float16 / bfloat16;
+    head dims 40 / 64 / 80 / 128 / 160 / 256, each stored at its own width).
     kv_rows: int32 [n] on the device, sample i attends to kv[kv_rows[i]] (entries in [0, m)); None: m == n, row for row.
     out: written and returned where given."""
     n, tq, c = q.shape

@@ -18,7 +18,9 @@ The forward is a host part (argument checks, the timestep, grouping) and a fixed
 a row map in, no host read) that graphs.GraphCache captures once per shape and replays, like the EDM denoisers' forwards.
 Activations are NHWC in `dtype` (float16 like the reference pipeline, or bfloat16).  The 4 latent channels are zero-padded to 64 for the
 MFMA conv (cin % 64 == 0) and conv_out's 4 output channels likewise (cout % 64 == 0).  SD-1.5's head dims 40 / 80 / 160 are zero-padded to
-64 / 128 / 256 at load time (rows of to_q / to_k / to_v, columns of to_out.0; scale = 1/sqrt(true dim)): exact, see pad_head_rows.
+64 / 128 / 256 at load time (rows of to_q / to_k / to_v, columns of to_out.0; scale = 1/sqrt(true dim)): exact, see pad_head_rows.  That is
+head_dims='padded', the default; head_dims='native' keeps them as stored (the attention kernels take 40 / 80 / 160 and pad on chip), so
+the q/k/v/out projections run at 320 / 640 / 1280 channels instead of 512 / 1024 / 2048 (native_head_dim).
 
 Parameters: a state dict with diffusers' key names (`UNet2DConditionModel.state_dict()` / the safetensors file of SD-1.5's unet/).
 Stock SD-1.x configuration only (check_config); anything else is refused by name.
@@ -75,6 +77,19 @@ def padded_head_dim(d):
     raise ValueError(f'SDUNet: head dim {d} exceeds the attention kernels\' 256')
 
 
+HEAD_DIMS = ('padded', 'native')
+
+
+def native_head_dim(d, heads):
+    """head_dims='native': the smallest head dim the 16-bit attention kernels take (40 / 64 / 80 / 128 / 160 / 256) that holds a true head
+    dim d AND leaves heads * dn a multiple of 64 -- the projections are 1x1 dts_conv2d calls, which need cin % 64 == 0 (to_out.0 reads
+    heads * dn channels).  SD-1.x (8 heads of 40 / 80 / 160) keeps its own dims; 2 heads of 32 take 64, since 2 * 40 = 80 would not do."""
+    for dn in (40, 64, 80, 128, 160, 256):
+        if d <= dn and (heads * dn) % 64 == 0:
+            return dn
+    raise ValueError(f'SDUNet: head dim {d} exceeds the attention kernels\' 256')
+
+
 def pad_head_rows(w, heads, dpad):
     """to_q / to_k / to_v weight [heads*d, cin] -> [heads*dpad, cin]: each head's d output rows followed by dpad - d zero rows.  With the
     matching pad_head_cols of to_out.0 the attention is unchanged: the padded q and k components add 0 to every q.k, the padded v
@@ -99,9 +114,14 @@ class SDUNet:
     takes_context_rows = True       # __call__(..., context_rows=): the distinct contexts and a row map instead of one context per row
 
     def __init__(self, state_dict, block_out_channels=(320, 640, 1280, 1280), attention_head_dim=8, cross_attention_dim=768,
-                 layers_per_block=2, sample_size=64, device='cuda', dtype=torch.float16):
+                 layers_per_block=2, sample_size=64, device='cuda', dtype=torch.float16, head_dims='padded'):
         """attention_head_dim: the NUMBER of heads of every transformer block (diffusers' historical name for it, unet_2d_condition.py:
-        `num_attention_heads = num_attention_heads or attention_head_dim`)."""
+        `num_attention_heads = num_attention_heads or attention_head_dim`).
+        head_dims: 'padded' (default) zero-pads every head to 64 / 128 / 256 at load time (padded_head_dim); 'native' keeps the smallest
+        head dim the attention kernels take (native_head_dim: 40 / 80 / 160 as stored at SD-1.x widths, nothing padded)."""
+        if head_dims not in HEAD_DIMS:
+            raise ValueError(f'SDUNet: head_dims={head_dims!r} is not one of {HEAD_DIMS}')
+        self.head_dims = head_dims
         blocks.require_gpu('SDUNet')
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError('SDUNet: activations are float16 or bfloat16')
@@ -116,11 +136,13 @@ class SDUNet:
         self._graphs = GraphCache(self._device_forward)      # one capture per (rows, latent size, number of distinct contexts)
 
     @classmethod
-    def from_pretrained(cls, path, device='cuda', dtype=torch.float16):
+    def from_pretrained(cls, path, device='cuda', dtype=torch.float16, head_dims='padded'):
         """Reads a diffusers `unet/` directory: `config.json` for the shape and `diffusion_pytorch_model[.fp16].safetensors` for the
-        parameters -- the on-disk format of SD-1.5's U-Net.  A `.bin` pickle is not read."""
+        parameters -- the on-disk format of SD-1.5's U-Net.  A `.bin` pickle is not read.  head_dims: as the constructor's."""
         import json
         import os
+        if head_dims not in HEAD_DIMS:
+            raise ValueError(f'SDUNet: head_dims={head_dims!r} is not one of {HEAD_DIMS}')
         cfg_file = os.path.join(path, 'config.json')
         if not os.path.exists(cfg_file):
             raise FileNotFoundError(f'{path}: no config.json (the configuration is not guessed: only a stock SD-1.x U-Net is accepted, by name)')
@@ -131,7 +153,7 @@ class SDUNet:
         kw = {k: cfg[k] for k in ('attention_head_dim', 'cross_attention_dim', 'layers_per_block', 'sample_size') if k in cfg}
         if 'block_out_channels' in cfg:
             kw['block_out_channels'] = tuple(cfg['block_out_channels'])
-        return cls(sd, device=device, dtype=dtype, **kw)
+        return cls(sd, device=device, dtype=dtype, head_dims=head_dims, **kw)
 
     # ---- parameters ----------------------------------------------------------------------------
     def _resnet_params(self, sd, key):
@@ -149,7 +171,7 @@ class SDUNet:
         if c % H:
             raise ValueError(f'SDUNet: {c} channels do not split into {H} heads')
         d = c // H
-        dp = padded_head_dim(d)
+        dp = native_head_dim(d, H) if self.head_dims == 'native' else padded_head_dim(d)
         A = types.SimpleNamespace(heads=H, scale=1.0 / math.sqrt(d), hp=H * dp)
         A.g, A.b = p.norm(sd, key + '.norm')
         if sd[key + '.proj_in.weight'].dim() != 4:

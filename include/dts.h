@@ -61,7 +61,9 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      122: dts_attention_x3_masked, dts_text_tokens_f32 (the CLIP text tower in DTS_F16X3);
                                      123: dts_ode_xhat, dts_ode_slope, dts_ode_correct (the general ODE step of the ablation sampler);
                                      124: dts_candidate_noise_rows (mode / scale per output row: searches of several seeds in lock-step);
-                                     125: dts_candidate_noise_sd_rows, dts_ddim_candidates_groups (the SD backend's searches of several seeds in lock-step)) */
+                                     125: dts_candidate_noise_sd_rows, dts_ddim_candidates_groups (the SD backend's searches of several seeds in lock-step);
+                                     125, domain widened without a signature change: dts_attention (16-bit types) and dts_cross_attention take
+                                          head dims 40 / 80 / 160 at their true width (SD-1.x's heads without zero padding)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -219,7 +221,14 @@ int dts_space_to_depth2(const void* x, int x_nchw_f32, void* out, int dtype, int
 
 /* ---- K6: fused self-attention (networks.py:113-118,181-185; unet.py:355-372,388-407) -------------- */
 /* qkv NHWC-flattened [n][t][3*heads*d] laid out q[heads][d] | k[heads][d] | v[heads][d];
- * out [n][t][heads*d]; softmax(q.k * scale) in f32. d in {64,128,256} (and 512 in the 16-bit types: the SD VAE's mid block); any t >= 1. */
+ * out [n][t][heads*d]; softmax(q.k * scale) in f32; any t >= 1.  Head dims per dtype:
+ *   DTS_F32            d in {64, 128, 256};
+ *   DTS_BF16 / DTS_F16 d in {64, 128, 256}, 512 (the SD VAE's mid block) and 40, 80, 160 (the heads of SD-1.x's U-Net).
+ * 40 / 80 / 160 are laid out like every other d: at the TRUE head dim, nothing padded in memory (a head's row is 80 / 160 / 320 bytes, whole
+ * 16-byte chunks).  The zero-tail rule: on chip the K dimension of Q.K^T is d rounded up to 32 (64 / 96 / 160) and the 16-byte chunks at or
+ * beyond d/8 of a Q fragment, K row or V row are zeros that are never loaded; P.V covers d rounded up to 16 channels and only channels < d are
+ * stored.  A zero tail adds exact zeros to the f32 scores, so the result has the bits of the same call on values zero-padded per head to
+ * 64 / 128 / 256 (with the scale of the true d).  Every other d returns an error that names it. */
 int dts_attention(const void* qkv, void* out, int dtype, int n, int t, int heads, int d, float scale, dts_stream s);
 /* the same attention in the split-precision mode (DTS_F16X3; d = 64): qkv_split = dts_split2_f16 of the f32 qkv tensor, f16 [n][t][6*heads*d] =
  * hi(3C) | lo(3C) per token (also what dts_conv2d writes with out_split2); out f32 [n][t][heads*d], or with out_split3 = 1 the f16 operand
@@ -250,7 +259,9 @@ int dts_attention_x3_masked(const void* qkv_split, void* out, int out_split3, in
 /* Attention of tq queries over a SHORT foreign sequence (the text tokens): q [n][tq][heads*d], kv [kv_n][tk][2*heads*d] laid out
  * k[heads][d] | v[heads][d], out [n][tq][heads*d]; DTS_BF16 / DTS_F16; softmax(q.k * scale) in f32, Q.K^T and P.V on the 16-bit matrix
  * cores.  1 <= tk <= 128 (any length: the tail is masked): K and V of a (sample, head) sit in LDS at once, one pass over the keys, no online
- * rescale; a longer tk returns DTS_ERR_UNSUPPORTED.  d in {64, 128, 256}; any tq >= 1; scale > 0.
+ * rescale; a longer tk returns DTS_ERR_UNSUPPORTED.  d in {40, 64, 80, 128, 160, 256} in both dtypes; any tq >= 1; scale > 0.  40 / 80 / 160
+ * are stored at the true head dim in q, kv and out, and follow dts_attention's zero-tail rule (K width 64 / 96 / 160 on chip, tail chunks zero
+ * and never loaded, channels < d stored; LDS per block 2 * tkp * (2 * width + 32) bytes): the bits of the call on zero-padded heads.
  * kv_rows (device int32 [n], nullable): sample i attends to kv row kv_rows[i] (the 2N rows of the search loop share two text contexts:
  * their k|v projections are computed once each and never expanded); NULL: kv_n == n and sample i reads row i.  Entries must lie in
  * [0, kv_n); the kernel clamps them for memory safety only. */

@@ -21,6 +21,7 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
                   | auto (f16 when the network pickle records use_fp16=True, f16x3 otherwise; the choice is printed)
     --unet      : SD backend: diffusers (default: the stock UNet2DConditionModel) | hip (sd_unet.SDUNet on this build's kernels, read from
                   $DTS_SD_UNET_DIR or the cached snapshot's unet/; no fallback).  --vae hip|diffusers likewise (default hip)
+    --unet-head-dims: --unet hip: padded (default: head dims 40 / 80 / 160 zero-padded to 64 / 128 / 256 at load time) | native (as stored)
     --text-encoder: SD backend: transformers (default: the stock CLIPTextModel) | hip (clip_text.CLIPTextTower on this build's kernels, read
                   from $DTS_SD_TEXT_ENCODER_DIR or the cached snapshot's text_encoder/; no fallback)
     --clip-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel image tower, float32 like the reference) | hip
@@ -105,11 +106,14 @@ def load_sd_vae(model_id, dev, kind='hip'):
     return VAEDecoder.from_pretrained(path, device=dev, dtype=torch.float16)
 
 
-def load_sd_unet(model_id, dev, kind='diffusers'):
+def load_sd_unet(model_id, dev, kind='diffusers', head_dims='padded'):
     """The SD U-Net of the search loop, the twin of load_sd_vae.  kind='hip' (`--unet hip`): this build's HIP U-Net (sd_unet.SDUNet, drop-in
     for `unet(sample, t, encoder_hidden_states=...)`) read from the safetensors `unet/` directory of the locally cached SD-1.5 snapshot (or
     $DTS_SD_UNET_DIR) -- and an error when that directory cannot be found or read: there is no silent fallback.  kind='diffusers' (the
-    default): the stock UNet2DConditionModel module."""
+    default): the stock UNet2DConditionModel module.  head_dims (`--unet-head-dims`, kind='hip' only): 'padded' (default) or 'native', see
+    sd_unet.SDUNet; any other value is refused before a file is touched."""
+    if head_dims not in ('padded', 'native'):
+        raise ValueError(f"--unet-head-dims must be 'padded' or 'native', got {head_dims!r}")
     if kind == 'diffusers':
         from diffusers import UNet2DConditionModel
         return UNet2DConditionModel.from_pretrained(model_id, subfolder='unet', torch_dtype=torch.float16, local_files_only=True).to(dev)
@@ -122,7 +126,7 @@ def load_sd_unet(model_id, dev, kind='diffusers'):
         path = os.path.join(snapshot_download(model_id, local_files_only=True, allow_patterns=['unet/*']), 'unet')
     if not os.path.isdir(path):
         raise FileNotFoundError(f'SD U-Net directory {path!r} not found (set DTS_SD_UNET_DIR, or pass --unet diffusers for the stock module)')
-    return SDUNet.from_pretrained(path, device=dev, dtype=torch.float16)
+    return SDUNet.from_pretrained(path, device=dev, dtype=torch.float16, head_dims=head_dims)
 
 
 def load_sd_text_encoder(model_id, dev, kind='transformers'):
@@ -174,7 +178,7 @@ def main_sd(args):
         torch.cuda.set_device(local)
         dist.init_process_group('nccl', device_id=torch.device('cuda', local))
     dev = torch.device('cuda', local) if world > 1 else torch.device(args.device)
-    unet = load_sd_unet(model_id, dev, unet_kind)
+    unet = load_sd_unet(model_id, dev, unet_kind, head_dims=getattr(args, 'unet_head_dims', 'padded'))
     vae = load_sd_vae(model_id, dev, vae_kind)
     tok = CLIPTokenizer.from_pretrained(model_id, subfolder='tokenizer', local_files_only=True)
     te = load_sd_text_encoder(model_id, dev, te_kind)
@@ -240,6 +244,9 @@ def build_parser():
                         help="SD backend: 'hip' = this build's VAE decoder (an error if its safetensors cannot be read), 'diffusers' = the stock module")
     parser.add_argument('--unet', type=str, default='diffusers', choices=['hip', 'diffusers'],
                         help="SD backend: 'hip' = this build's U-Net on the HIP kernels (an error if its safetensors cannot be read), 'diffusers' = the stock module")
+    parser.add_argument('--unet-head-dims', dest='unet_head_dims', type=str, default='padded', choices=['padded', 'native'],
+                        help="--unet hip: 'padded' = SD-1.x's head dims 40 / 80 / 160 zero-padded to 64 / 128 / 256 at load time, 'native' = kept as "
+                             "stored (the attention kernels pad on chip; the q/k/v/out projections run at the model's own widths)")
     parser.add_argument('--text-encoder', dest='text_encoder', type=str, default='transformers', choices=['transformers', 'hip'],
                         help="SD backend: 'hip' = this build's CLIP text tower on the HIP kernels in float16 (an error if its safetensors cannot be "
                              "read), 'transformers' = the stock CLIPTextModel")

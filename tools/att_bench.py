@@ -5,6 +5,7 @@ Variants (tuning knobs, include/dts.h dts_set_tuning) are timed INTERLEAVED in o
 (cdna_hip_programming.md section 5.4 rules 24/25); prints the median per variant and the algorithmic bytes per launch.
 
     python tools/att_bench.py --n 64 --variants att_xcd=0 att_xcd=1
+    python tools/att_bench.py --n 32 --dtype f16 --native        # head dims 40 / 80 / 160 as stored against the zero-padded route
 """
 import argparse
 import os
@@ -84,6 +85,41 @@ def x3_kernel_table(a):
         print(f'{name:20s} T={t:5d} | ' + ' | '.join(f'{m * 1e3:7.1f} us {fl / m / 1e9:6.1f} TF/s' for m in med) + f' | outputs {"identical" if same else "DIFFER"}', flush=True)
 
 
+NATIVE_SHAPES = [('SD-1.5 64x64 d40', 4096, 8, 40), ('SD-1.5 32x32 d80', 1024, 8, 80), ('SD-1.5 16x16 d160', 256, 8, 160)]       # (name, tokens, heads, head dim)
+
+
+def native_table(a, dt):
+    """--native: dts_attention at the SD-1.x head dims as stored (40 / 80 / 160) against the padded route (the same values zero-padded per head
+    to 64 / 128 / 256, the kernel of that head dim, scale of the true dim), alternating launch group by launch group in one process; the
+    FLOP rate counts the true head dim for both."""
+    print(f'native vs padded head dims, {a.n} rows x 8 heads, {a.dtype}: us per launch (median of {a.rounds}, min .. max)')
+    for name, t, heads, d in NATIVE_SHAPES:
+        dp = {40: 64, 80: 128, 160: 256}[d]
+        x = torch.randn(a.n, t, 3, heads, d, device='cuda')
+        xp = torch.zeros(a.n, t, 3, heads, dp, device='cuda')
+        xp[..., :d] = x
+        x, xp = x.view(a.n, t, 3 * heads * d).to(dt), xp.view(a.n, t, 3 * heads * dp).to(dt)
+        fl = 4.0 * a.n * heads * t * t * d
+        fns = {'native': lambda: ops.attention(x, heads, d ** -0.5), 'padded': lambda: ops.attention(xp, heads, d ** -0.5)}
+        outs = {k: f() for k, f in fns.items()}
+        same = torch.equal(outs['native'].view(a.n, t, heads, d), outs['padded'].view(a.n, t, heads, dp)[..., :d])
+        ts = {k: [] for k in fns}
+        for r in range(a.rounds + 1):
+            for k, f in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda._sleep(200_000)
+                e0.record()
+                for _ in range(4):
+                    f()
+                e1.record()
+                torch.cuda.synchronize()
+                if r:
+                    ts[k].append(e0.elapsed_time(e1) / 4)
+        med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+        print(f'{name:20s} T={t:5d} | ' + ' | '.join(f'{k} {med[k] * 1e3:7.1f} us ({min(ts[k]) * 1e3:.1f} .. {max(ts[k]) * 1e3:.1f}) {fl / med[k] / 1e9:6.1f} TF/s' for k in fns)
+              + f' | native / padded {med["native"] / med["padded"]:.3f} | outputs {"identical" if same else "DIFFER"}', flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=64)
@@ -93,8 +129,11 @@ def main():
     ap.add_argument('--variants-x3', type=int, nargs='*', default=[], help='(--x3-kernel) A/B: 0 = the kernel without the three latency changes of round 6 (K fragment prefetch, one-round max exchange, V prefetch)')
     ap.add_argument('--x3-kernel', action='store_true', help='attention_x3_kernel alone on split images, att_qt variants')
     ap.add_argument('--x3', action='store_true', help='f32 qkv: the f32-MFMA kernel vs the split-precision kernel (split pass included)')
+    ap.add_argument('--native', action='store_true', help='head dims 40 / 80 / 160 as stored against the zero-padded route (SD-1.5 shapes; --n 32 for config 4)')
     a = ap.parse_args()
     dt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[a.dtype]
+    if a.native:
+        return native_table(a, dt)
     if a.x3_kernel:
         return x3_kernel_table(a)
     if a.x3:

@@ -18,7 +18,12 @@ map, no host synchronisation).  `ms_per_forward` stays what it was before replay
 of different commits compare.  `grouping` times ops.group_rows plus the readback of its count against torch.unique(dim=0,
 return_inverse=True), which waits for the size of its own result, on the same [32, 59136] 16-bit rows (host clock around work that ends in a
 synchronise).
---replay-only N: nothing but N replayed context_rows forwards after the warm-up, for a kernel trace of its own.  No pass/fail threshold."""
+--replay-only N: nothing but N replayed context_rows forwards after the warm-up, for a kernel trace of its own (--replay-head-dims picks
+the mode of that model).  No pass/fail threshold.
+--head-dims padded,native: instead of the above, per dtype one model of each listed SDUNet head_dims mode in ONE process on the same inputs;
+replayed context_rows forwards alternate between the modes, forward by forward, device events around each; reports the median, minimum
+and maximum of --iters forwards per mode after the warm-up, the ratio of the medians against the first listed mode, and rel. max
+|difference| of the outputs.  The padded mode is the default path, so it is what native is measured against in the same minute."""
 import argparse
 import json
 import os
@@ -115,6 +120,45 @@ def grouping(ehs, reps=20):
     return out
 
 
+def head_dims_table(a, res, sd, x32, c2):
+    """--head-dims: the listed modes against each other, alternating forward by forward through graph replay with context_rows="""
+    modes = a.head_dims.split(',')
+    res['what'] += '; head_dims modes alternating, graph replay, context_rows='
+    res['head_dims'] = modes
+    for name in a.dtypes.split(','):
+        dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[name]
+        x = x32.to('cuda', dt)
+        t = torch.tensor(501, device='cuda')
+        ctx = c2.to('cuda', dt).contiguous()
+        rmap = torch.tensor([0] * (a.rows // 2) + [1] * (a.rows - a.rows // 2), dtype=torch.int32).to('cuda')
+        unets = {m: SDUNet(sd, device='cuda', dtype=dt, head_dims=m) for m in modes}
+        run = lambda u: u(x, t, encoder_hidden_states=ctx, context_rows=rmap)[0]
+        for _ in range(max(a.warmup, 3)):
+            outs = {m: run(u) for m, u in unets.items()}
+        torch.cuda.synchronize()
+        for m, u in unets.items():
+            assert u._graphs.captures == 1 and u._graphs.replays > 0, (m, u._graphs.path_report())
+        times = {m: [] for m in modes}
+        for _ in range(a.iters):
+            for m, u in unets.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                outs[m] = run(u)
+                e1.record()
+                torch.cuda.synchronize()
+                times[m].append(e0.elapsed_time(e1))
+        stat = lambda v: {'ms_median': round(statistics.median(v), 3), 'ms_min': round(min(v), 3), 'ms_max': round(max(v), 3)}
+        base = outs[modes[0]].float()
+        res['dtypes'][name] = {'replay_context_rows': {m: stat(v) for m, v in times.items()},
+                               'median_ratio_to_' + modes[0]: {m: round(statistics.median(times[m]) / statistics.median(times[modes[0]]), 4) for m in modes},
+                               'rel_max_diff_to_' + modes[0]: {m: float((outs[m].float() - base).abs().max() / base.abs().max()) for m in modes},
+                               'attention_channels': {m: sorted({A.hp for A in u._tfm}) for m, u in unets.items()},
+                               'output_finite': all(bool(torch.isfinite(o).all()) for o in outs.values())}
+        del unets
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=32)
@@ -122,6 +166,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtypes', default='f16,bf16')
     ap.add_argument('--replay-only', type=int, default=0, help='only this many replayed context_rows forwards after the warm-up (for a kernel trace)')
+    ap.add_argument('--head-dims', default='', help="e.g. padded,native: time these SDUNet head_dims modes against each other (see the module docstring)")
+    ap.add_argument('--replay-head-dims', default='padded', choices=['padded', 'native'], help='the head_dims mode of the --replay-only model')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('sd_unet_bench: needs a GPU (no CPU fallback, nothing is measured without one)')
@@ -134,9 +180,11 @@ def main():
            'peak_flops_16bit_dense': PEAK_16BIT_DENSE, 'device': torch.cuda.get_device_name(0), 'iters': a.iters, 'warmup': a.warmup, 'dtypes': {}}
     x32 = torch.randn(a.rows, 4, 64, 64, generator=g)
     c2 = torch.randn(2, 77, 768, generator=g)
+    if a.head_dims:
+        return head_dims_table(a, res, sd, x32, c2)
     for name in a.dtypes.split(','):
         dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[name]
-        unet = SDUNet(sd, device='cuda', dtype=dt)
+        unet = SDUNet(sd, device='cuda', dtype=dt, head_dims=a.replay_head_dims if a.replay_only else 'padded')
         x = x32.to('cuda', dt)
         ehs = torch.cat([c2[:1].expand(a.rows // 2, -1, -1), c2[1:].expand(a.rows - a.rows // 2, -1, -1)]).to('cuda', dt).contiguous()
         t = torch.tensor(501, device='cuda')
