@@ -8,14 +8,14 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libdts_hip.so')
-SOURCES = ['conv_igemm.hip', 'conv_igemm_phase.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip', 'resample.hip', 'transformer.hip', 'group_rows.hip', 'vit.hip', 'jpeg.hip']
+SOURCES = ['conv_igemm.hip', 'conv_igemm_phase.hip', 'conv_igemm_stride.hip', 'conv_small.hip', 'groupnorm.hip', 'attention.hip', 'elementwise.hip', 'resample.hip', 'transformer.hip', 'group_rows.hip', 'vit.hip', 'jpeg.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 # per-source extras.  attention: keep the MFMA accumulators in VGPRs -- the online-softmax rescale reads and rewrites them
 # every key tile, and with the default AGPR form hipcc emitted 80 v_accvgpr_read/write per tile (a quarter of the loop's VALU).
 EXTRA = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1']}
 # sources that include another source (rebuilt when it changes)
-INCLUDES = {'conv_igemm_phase.hip': ['conv_igemm.hip']}
+INCLUDES = {'conv_igemm_phase.hip': ['conv_igemm.hip'], 'conv_igemm_stride.hip': ['conv_igemm.hip']}
 
 
 def _newer(a, b):
@@ -57,7 +57,7 @@ def build(force=False, verbose=False):
 OBJDUMP = os.environ.get('LLVM_OBJDUMP', '/opt/rocm/lib/llvm/bin/llvm-objdump')
 READELF = os.environ.get('LLVM_READELF', os.path.join(os.path.dirname(OBJDUMP), 'llvm-readelf'))
 # objects whose kernels write M0 in inline asm (LDS-DMA destination) and await the loads with hand-counted s_waitcnt vmcnt(N)
-M0_OBJECTS = ['conv_igemm.o', 'conv_igemm_phase.o', 'attention.o']
+M0_OBJECTS = ['conv_igemm.o', 'conv_igemm_phase.o', 'conv_igemm_stride.o', 'attention.o']
 
 
 def _device_object(obj, tmp):

@@ -35,6 +35,8 @@ static_assert(sizeof(dts_conv_args) == 208, "dts_conv_args layout changed: bump 
 // kernels compile beside this file instead of lengthening the longest compile of the build.  The two units meet in this one function; its
 // arguments are this file's ConvPlan, ConvP and ConvCall (internal types, identical in both units since both are this text).
 int dts_conv_launch_phase_form(const void* plan, const void* params, const void* call);
+// The stride-2 forms (S2 = true, dts_conv_args.up == -1) likewise: conv_igemm_stride.hip, this file compiled with DTS_CONV_STRIDE_TU.
+int dts_conv_launch_stride_form(const void* plan, const void* params, const void* call);
 
 namespace {
 
@@ -758,7 +760,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& kp, f32x4_t (&acc)[MT
 // four phases of a pixel tile read the same activation rows from L2); tap t reads low-resolution offset ((t >> 1) - 1 + py,
 // (t & 1) - 1 + px) -- the padding after the upsample is exactly the low-resolution out-of-range row -- and the epilogue addresses the
 // output, bias_nc and the residual through a PhaseTileMap.  No K split (the plan refuses one).
-template <typename T, int MT, int NT, int WM, int WN, bool PF, int STAGES = 2, typename OT = T, bool PH = false>
+// S2 (16-bit types only; dts_conv_args.up == -1): the 3x3 convolution with zero padding 1 and STRIDE 2, hout = (hin + 1) / 2, wout = (win + 1) / 2.
+// Only the gather differs: the pixel rows of a tile are output pixels as always, tap (dh, dw) of output pixel (ho, wo) reads input pixel
+// (2 ho + dh, 2 wo + dw), and that coordinate is checked against the INPUT extent (an odd size has a live bottom / right tap where an even
+// one has padding).  Tile maps, K split, reduce pass, statistics and epilogues work in output pixels and do not know of it.
+template <typename T, int MT, int NT, int WM, int WN, bool PF, int STAGES = 2, typename OT = T, bool PH = false, bool S2 = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)) void conv_igemm_kernel(const ConvP kp) {
   const char* const p_x1 = kp.x1; const char* const p_x2 = kp.x2; const char* const p_w = kp.w;
   const int p_c1 = kp.c1, p_c2 = kp.c2, p_cin = kp.cin, p_hin = kp.hin, p_win = kp.win, p_hout = kp.hout, p_wout = kp.wout;
@@ -772,6 +778,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
   constexpr bool X3I = !std::is_same<T, OT>::value;
   static_assert(!X3I || std::is_same<T, f16_t>::value, "split precision runs on the f16 matrix instruction");
   static_assert(!PH || X3I, "the phase form is the split-precision mode's");
+  static_assert(!S2 || (!X3I && !PH && sizeof(T) == 2), "the stride-2 form is the 16-bit modes'");
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(STAGES >= 2 && STAGES <= 4, "ring depth");
   constexpr int SLAB = 8 * NW;             // rows staged by one wave-instruction round of the whole block
@@ -833,9 +840,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || STAGES == 2 ? 2 : 1)
     const char* xb; int cs, cofs;                                                                             \
     if ((ci0_) < p_c1) { xb = p_x1; cs = p_c1; cofs = (ci0_); } else { xb = p_x2; cs = p_c2; cofs = (ci0_) - p_c1; } \
     _Pragma("unroll") for (int j = 0; j < RB; ++j) {                                                          \
-      const int hu = (pix_hw[j] >> 16) + dh_, wu = (pix_hw[j] & 0xffff) + dw_;                                \
-      const bool ok = pix_n[j] >= 0 && (unsigned)hu < (unsigned)g_h && (unsigned)wu < (unsigned)g_w;          \
-      const int hs = (!PH && p_up) ? (hu >> 1) : hu, ws = (!PH && p_up) ? (wu >> 1) : wu;                     \
+      const int hu = (S2 ? 2 : 1) * (pix_hw[j] >> 16) + dh_, wu = (S2 ? 2 : 1) * (pix_hw[j] & 0xffff) + dw_;  \
+      const bool ok = pix_n[j] >= 0 && (unsigned)hu < (unsigned)(S2 ? p_hin : g_h) && (unsigned)wu < (unsigned)(S2 ? p_win : g_w); \
+      const int hs = (!PH && !S2 && p_up) ? (hu >> 1) : hu, ws = (!PH && !S2 && p_up) ? (wu >> 1) : wu;       \
       brow[j] = ok ? xb + ((size_t)(pix_n[j] + hs * p_win + ws) * cs + cofs) * ES + schunk : zsrc;            \
     }                                                                                                         \
   }
@@ -1732,7 +1739,8 @@ ConvKnobs conv_knobs() {
 }
 
 // the fields of dts_conv_plan_info (include/dts.h says what each means) + why dts_conv2d must refuse the call, where `refused` is set
-struct ConvPlan : dts_conv_plan_info { char refuse[200]; };
+// stride2: the S2 form of conv_igemm_kernel (up == -1), stride_f16 its element type (f16, else bf16) for the launch in the other unit
+struct ConvPlan : dts_conv_plan_info { char refuse[200]; bool stride2, stride_f16; };
 
 // ---- the launcher: a plan becomes a launch
 template <auto KERNEL>
@@ -1753,13 +1761,13 @@ int conv_launch(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
 }
 
 // conv_igemm_kernel of one tile (MT x 4 MFMA tiles per wave, WM x WN waves in its 4-wave form; the 8-wave form halves the couts per wave)
-template <typename T, typename OT, int MT, int WM, int WN, bool PF, bool PH = false>
+template <typename T, typename OT, int MT, int WM, int WN, bool PF, bool PH = false, bool S2 = false>
 int conv_launch_igemm(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
-#define DTS_IGEMM(MT_, WM_, STAGES_) conv_launch<&conv_igemm_kernel<T, MT_, 4, WM_, WN, PF, STAGES_, OT, PH>>(pl, q, call)
+#define DTS_IGEMM(MT_, WM_, STAGES_) conv_launch<&conv_igemm_kernel<T, MT_, 4, WM_, WN, PF, STAGES_, OT, PH, S2>>(pl, q, call)
   if constexpr (sizeof(T) == 2) {                            // (f32: the 2-deep ring with 4 waves only)
     if (pl.waves == 8) return pl.stages == 3 ? DTS_IGEMM(MT / 2, WM * 2, 3) : DTS_IGEMM(MT / 2, WM * 2, 2);
     if (pl.stages == 3) return DTS_IGEMM(MT, WM, 3);
-    if constexpr (std::is_same<T, OT>::value)
+    if constexpr (std::is_same<T, OT>::value && !S2)       // (the stride-2 form has 2- and 3-deep rings: the plan names no other)
       if (pl.stages == 4) return DTS_IGEMM(MT, WM, 4);
   }
   return DTS_IGEMM(MT, WM, 2);
@@ -1837,6 +1845,7 @@ int pp_splits(int nblk, int nk, double slab, bool x3, bool ws, long long ws_byte
 
 // the shapes the ping-pong / halo kernel takes (and with it the fused GroupNorm apply)
 bool conv_pp_eligible(int dtype, int ksize, int cout, int c1, int c2, int n, int hin, int win, int up) {
+  if (up < 0) return false;                                        // stride 2: the halo staging assumes stride 1
   const int ho = up ? 2 * hin : hin, wo = up ? 2 * win : win;      // the tile geometry lives in OUTPUT coordinates
   const long long P = (long long)n * ho * wo;
   return dtype != DTS_F32 && cout % 192 == 0 && ho == wo && wo >= 16 && (wo & (wo - 1)) == 0 && P % 256 == 0 && P < (1ll << 30) &&
@@ -1897,6 +1906,10 @@ int conv_pp_dbg(int variant) {
 template <typename T, typename OT = T>
 int conv_launch_plan(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
   if constexpr (sizeof(T) == 2) {
+    if constexpr (std::is_same<T, OT>::value) {
+      // the stride-2 form (instantiated in conv_igemm_stride.hip): every tile, fragment prefetch, 4 | 8 waves, 2- | 3-deep ring
+      if (pl.stride2) return dts_conv_launch_stride_form(&pl, &q, &call);
+    }
 #define DTS_PP(DBG_, GN_, MT_, SK_) conv_launch<&conv_pp_kernel<T, 9, DBG_, GN_, MT_, OT, SK_>>(pl, q, call)
     if constexpr (!std::is_same<T, OT>::value) {
       // the phase form (instantiated in conv_igemm_phase.hip): 192- / 128-cout tiles, fragment prefetch; waves and ring depth (2 | 3) are conv_launch_igemm's
@@ -1933,7 +1946,8 @@ int conv_launch_plan(const ConvPlan& pl, const ConvP& q, const ConvCall& call) {
 void conv_shape_from_args(const dts_conv_args* a, ConvP& p) {
   p.c1 = a->c1; p.c2 = a->c2; p.cin = a->c1 + a->c2;
   p.n = a->n; p.hin = a->hin; p.win = a->win;
-  p.hout = a->up ? 2 * a->hin : a->hin; p.wout = a->up ? 2 * a->win : a->win;
+  // up: 0 same size, 1 / 2 nearest-2x upsampled input, -1 stride 2 (odd sizes keep their last row / column: ceil)
+  p.hout = a->up < 0 ? (a->hin + 1) / 2 : (a->up ? 2 * a->hin : a->hin); p.wout = a->up < 0 ? (a->win + 1) / 2 : (a->up ? 2 * a->win : a->win);
   p.cout = a->cout; p.taps = a->ksize * a->ksize; p.up = a->up;
   p.P = (int)((long long)p.n * p.hout * p.wout);
   p.residual = (const char*)a->residual; p.gn_coef = a->gn_coef;
@@ -1949,21 +1963,24 @@ ConvPlan conv_plan(const dts_conv_args* a) {
   const bool f32 = a->dtype == DTS_F32, x3 = a->dtype == DTS_F16X3;
   // the fused GroupNorm apply is the 192-cout ping-pong form's, without upsample; the grid rule of conv_pick_pp, without its exceptions
   // (with gn_coef the kernel choice does not depend on the residual)
-  pl.fuses_gn = a->ksize == 3 && k.variant != 0 && k.tile <= 0 && !a->up &&
+  pl.fuses_gn = a->ksize == 3 && k.variant != 0 && k.tile <= 0 && a->up == 0 &&
                 conv_pp_eligible(a->dtype, a->ksize, a->cout, a->c1, a->c2, a->n, a->hin, a->win, a->up) &&
                 (k.variant == 1 || (long long)(a->cout / 192) * (((long long)a->n * a->hin * a->win + 255) / 256) >= 64);
   // (these leave kernel = -1: what dts_conv_kernel calls invalid arguments)
   if (a->ksize != 1 && a->ksize != 3) return refuse("dts_conv2d: ksize %d", a->ksize);
   if (a->n <= 0 || a->hin <= 0 || a->win <= 0) return refuse("dts_conv2d: bad shape");
   if (a->cout <= 0) return refuse("dts_conv2d: cout %d must be a multiple of 64", a->cout);
-  if ((long long)a->n * a->hin * a->win * (a->up ? 4 : 1) >= (1ll << 30)) return refuse("dts_conv2d: too many pixels");
+  if (a->up < -1) return refuse("dts_conv2d: up %d (0, 1, 2 or -1)", a->up);
+  if ((long long)a->n * a->hin * a->win * (a->up > 0 ? 4 : 1) >= (1ll << 30)) return refuse("dts_conv2d: too many pixels");
   ConvP p;
   conv_shape_from_args(a, p);
   // up == 2: the phase form of conv_igemm_kernel (`w` holds four 2x2-tap weights); never the ping-pong kernel, whose ring protocol is
   // derived for nine-tap chunks
   const bool ph = a->up == 2;
   if (ph) p.taps = 4;
-  const int mt = ph ? 0 : conv_pick_pp(k, f32, p, x3);
+  // up == -1: the stride-2 form of conv_igemm_kernel; never the ping-pong kernel either (its halo staging assumes stride 1)
+  const bool s2 = a->up == -1;
+  const int mt = (ph || s2) ? 0 : conv_pick_pp(k, f32, p, x3);
   pl.kernel = mt;
   // ---- grid and K loop
   int unit = 1;                                              // K steps that stay together in a split
@@ -1991,7 +2008,7 @@ ConvPlan conv_plan(const dts_conv_args* a) {
   {
     const int su = a->skip_up ? 1 : 0;
     // forced ping-pong (DTS_CONV_VARIANT=1): any grid folds, unsplit -- the tests' small shapes
-    pl.folds_skip = x3 && mt != 0 && !a->up && a->residual == nullptr && !a->out_split2 && a->gn_coef == nullptr &&
+    pl.folds_skip = x3 && mt != 0 && a->up == 0 && a->residual == nullptr && !a->out_split2 && a->gn_coef == nullptr &&
                     a->skip_c > 0 && a->skip_c % 64 == 0 && k.skip_fold != 0 && k.splits <= 0 && !(su && ((a->hin | a->win) & 1)) &&
                     (!pp_considers_split(pl.nblk) || k.variant == 1) &&
                     (long long)a->n * (a->hin >> su) * (a->win >> su) * a->skip_c * 2 < (1ll << 31) && (long long)a->cout * a->skip_c * 2 < (1ll << 31);
@@ -2003,6 +2020,16 @@ ConvPlan conv_plan(const dts_conv_args* a) {
   if ((long long)p.cin * (f32 ? 4 : 2) + 128 > (long long)sizeof(g_zero16))
     return refuse("dts_conv2d: %d input channels exceed the zero-row page (%d bytes)", p.cin, (int)sizeof(g_zero16));
   if (p.hout >= 32768 || p.wout >= 32768) return refuse("dts_conv2d: spatial size too large");
+  // ---- up == -1, the stride-2 form: 16-bit, 3x3, nothing that belongs to the ping-pong kernel or to the split-precision mode
+  if (s2) {
+    if (a->dtype != DTS_F16 && a->dtype != DTS_BF16) return refuse("dts_conv2d: up = -1 (stride 2) runs in DTS_F16 and DTS_BF16, dtype %d", a->dtype);
+    if (a->ksize != 3) return refuse("dts_conv2d: up = -1 (stride 2) needs ksize 3, got %d", a->ksize);
+    if (a->gn_coef != nullptr) return refuse("dts_conv2d: up = -1 (stride 2) takes no gn_coef");
+    if (a->skip_c != 0 || a->skip_w != nullptr || a->skip_x != nullptr) return refuse("dts_conv2d: up = -1 (stride 2) takes no skip_*");
+    if (a->out_split2) return refuse("dts_conv2d: up = -1 (stride 2) takes no out_split2");
+    if (a->acc_scale != 0.f && a->acc_scale != 1.f) return refuse("dts_conv2d: up = -1 (stride 2) takes no acc_scale");
+    pl.stride2 = true; pl.stride_f16 = a->dtype == DTS_F16;
+  }
   if (a->out_split2 && !(x3 && a->stats_out == nullptr)) return refuse("dts_conv2d: out_split2 is the split-precision mode's, without strip statistics");
   if (a->acc_scale != 0.f && a->acc_scale != 1.f && !x3) return refuse("dts_conv2d: acc_scale is the split-precision mode's (DTS_F16X3)");
   if (pl.gn && !pl.fuses_gn) return refuse("dts_conv2d: gn_coef given for a launch that cannot fuse the GroupNorm apply (ask dts_conv_fuses_gn first)");
@@ -2062,6 +2089,7 @@ ConvPlan conv_plan(const dts_conv_args* a) {
   pl.stages = (one_per_cu && pl.ks_per_split >= 3) ? 3 : 2;
   if (k.stages >= 2 && k.stages <= 4) pl.stages = k.stages;
   if (f32) pl.stages = 2;                                    // parity mode: one configuration
+  if (s2 && pl.stages == 4) pl.stages = 3;                   // (the stride-2 form is instantiated with 2- and 3-deep rings)
   const int stage_bytes = (pl.tile + (pl.tile == 64 ? 256 : 128)) * 128;
   if (pl.stages * stage_bytes > 160 * 1024) pl.stages = 3;
   // 8 waves per block (the same tile, half the couts per wave) when the grid leaves one block per CU; 16-bit operands only
@@ -2074,7 +2102,23 @@ ConvPlan conv_plan(const dts_conv_args* a) {
 
 }  // namespace
 
-#ifdef DTS_CONV_PHASE_TU
+#if defined(DTS_CONV_STRIDE_TU)
+// conv_igemm_stride.hip: the launch of a plan with stride2 set, and with it the only instantiations of conv_igemm_kernel<.., S2 = true>
+template <typename T>
+int conv_launch_stride(const ConvPlan& pl, const ConvP& q, const ConvCall& c) {
+  switch (pl.tile) {
+    case 192: return conv_launch_igemm<T, T, 6, 2, 2, true, false, true>(pl, q, c);
+    case 128: return conv_launch_igemm<T, T, 4, 2, 2, true, false, true>(pl, q, c);
+    default: return conv_launch_igemm<T, T, 4, 1, 4, true, false, true>(pl, q, c);
+  }
+}
+int dts_conv_launch_stride_form(const void* plan, const void* params, const void* call) {
+  const ConvPlan& pl = *static_cast<const ConvPlan*>(plan);
+  const ConvP& q = *static_cast<const ConvP*>(params);
+  const ConvCall& c = *static_cast<const ConvCall*>(call);
+  return pl.stride_f16 ? conv_launch_stride<f16_t>(pl, q, c) : conv_launch_stride<bf16_t>(pl, q, c);
+}
+#elif defined(DTS_CONV_PHASE_TU)
 // conv_igemm_phase.hip: the launch of a plan with phases = 1, and with it the only instantiations of conv_igemm_kernel<.., PH = true>
 int dts_conv_launch_phase_form(const void* plan, const void* params, const void* call) {
   const ConvPlan& pl = *static_cast<const ConvPlan*>(plan);

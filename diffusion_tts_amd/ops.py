@@ -215,19 +215,28 @@ def _conv_workspace(device):
     return ws
 
 
-def _conv_args(x1, w, x2, up):
+def _conv_args(x1, w, x2, up, stride=1):
     n, hin, win, c1 = x1.shape
     a = L.ConvArgs()
     a.c1, a.c2 = c1, 0 if x2 is None else x2.shape[-1]
     a.n, a.hin, a.win, a.cout, a.ksize = n, hin, win, w.shape[0], w.shape[1]
-    a.up, a.dtype = int(up), dt_code(x1.dtype)
+    a.up, a.dtype = _up_field(up, stride), dt_code(x1.dtype)
     return a
 
 
-def conv_kernel(x1, w, x2=None, up=False, residual=None, gn_coef=None, gn_stats=False):
-    """Which kernel ops.conv2d launches for these arguments: 0 = 4-wave implicit GEMM (its phase form included), 6 / 4 = ping-pong kernel
-    with 192- / 128-cout blocks (dts_conv_kernel; measurement aid for bench.py)."""
-    a = _conv_args(x1, w, x2, up)
+def _up_field(up, stride):
+    """dts_conv_args.up of conv2d(up=, stride=): 0 / 1, or -1 for stride 2 (which takes no upsample)"""
+    if stride not in (1, 2):
+        raise ValueError(f'conv2d: stride {stride!r} (1 or 2)')
+    if stride == 2 and up:
+        raise ValueError('conv2d: stride=2 takes no up=True')
+    return -1 if stride == 2 else int(up)
+
+
+def conv_kernel(x1, w, x2=None, up=False, residual=None, gn_coef=None, gn_stats=False, stride=1):
+    """Which kernel ops.conv2d launches for these arguments: 0 = 4-wave implicit GEMM (its phase and stride-2 forms included), 6 / 4 = ping-pong
+    kernel with 192- / 128-cout blocks (dts_conv_kernel; measurement aid for bench.py)."""
+    a = _conv_args(x1, w, x2, up, stride)
     if isinstance(w, X3Weight):           # the launch sees one 16-bit source of 2*(c1+c2) channels
         a.c1, a.c2, a.dtype = 2 * (a.c1 + a.c2), 0, L.DTS_F16X3
     a.residual = _ptr(residual)
@@ -293,7 +302,7 @@ def conv_folds_skip(x1, w, skip):
 
 
 def _conv2d_args(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, out_scale=1.0, out=None, gn_stats=False,
-                 timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None, phases=None):
+                 timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None, phases=None, stride=1):
     """the dts_conv_args of conv2d(...) (and of conv_plan(...): one builder, so the two cannot differ): (args, out, statistics buffer or None,
     out_split2, tensors the arguments point into)"""
     n, hin, win, c1 = x1.shape
@@ -301,8 +310,14 @@ def _conv2d_args(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=F
     cout, kh, kw, cin = w.shape
     if cin != c1 + c2 or kh != kw:
         raise ValueError(f'conv2d: weight {tuple(w.shape)} does not match inputs ({c1}+{c2})')
-    ho, wo = (2 * hin, 2 * win) if up else (hin, win)
+    up_field = _up_field(up, stride)
     x3 = isinstance(w, X3Weight)
+    if stride == 2:         # the 16-bit 3x3 form alone (dts.h: dts_conv_args.up == -1); refused here, before the library is called
+        for given, what in ((gn_coef is not None, 'gn_coef'), (skip is not None, 'skip'), (out_split2, 'out_split2'), (x3, 'a split-precision weight'),
+                            (x1.dtype == torch.float32, 'float32 activations'), (kh != 3, f'a {kh}x{kh} weight')):
+            if given:
+                raise ValueError(f'conv2d: stride=2 takes no {what}')
+    ho, wo = ((hin + 1) // 2, (win + 1) // 2) if stride == 2 else (2 * hin, 2 * win) if up else (hin, win)
     if x3 and (x1.dtype != torch.float32 or gn_coef is not None):
         raise ValueError('conv2d: a split-precision weight takes float32 activations (and no fused input GroupNorm)')
     if isinstance(x1, SplitAct) and (not x3 or x2 is not None):
@@ -330,7 +345,7 @@ def _conv2d_args(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=F
         raise ValueError(f'conv2d: residual shape {tuple(residual.shape)} != {(n, ho, wo, cout)}')
     a.out = _ptr(out, 'out', torch.float16 if out_split2 else x1.dtype)
     a.n, a.hin, a.win, a.cout, a.ksize = n, hin, win, cout, kh
-    a.up, a.out_scale, a.dtype = int(up), float(out_scale), (L.DTS_F16X3 if x3 else dt_code(x1.dtype))
+    a.up, a.out_scale, a.dtype = up_field, float(out_scale), (L.DTS_F16X3 if x3 else dt_code(x1.dtype))
     ws = _conv_workspace(x1.device)
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     st = None
@@ -363,8 +378,11 @@ def conv_plan(*args, **kw):
 
 
 def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, out_scale=1.0, out=None, gn_stats=False,
-           timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None, phases=None):
-    """phases (up=True with a weight packed with up_phases=True): None = the phase form where conv_takes_phases() says so, False = never,
+           timing_events=None, gn_coef=None, gn_silu=True, out_split2=False, skip=None, phases=None, stride=1):
+    """stride=2 (float16 / bfloat16, 3x3 weights): zero padding 1 and stride 2, an SD Downsample2D; the output (and a residual) is
+    [n, (hin+1)//2, (win+1)//2, cout], odd sizes included, `w` the ordinary pack_conv_weight of the [C, C, 3, 3] tensor.  Not with up=True,
+    gn_coef, skip, out_split2, an X3Weight or float32 activations (ValueError).
+    phases (up=True with a weight packed with up_phases=True): None = the phase form where conv_takes_phases() says so, False = never,
     True = always (the library refuses what it cannot run).
     skip=(SplitAct, X3Weight, up): the block's 1x1 skip convolution of that operand accumulated by this launch (only where conv_folds_skip()
     says so; `bias` is then the sum of the two layers' biases and there is no `residual`).
@@ -374,7 +392,7 @@ def conv2d(x1, w, bias=None, *, x2=None, bias_nc=None, residual=None, up=False, 
     group_norm(), which then skips its own pass over the tensor."""
     a, out, st, out_split2, _keep = _conv2d_args(x1, w, bias, x2=x2, bias_nc=bias_nc, residual=residual, up=up, out_scale=out_scale, out=out,
                                                  gn_stats=gn_stats, timing_events=timing_events, gn_coef=gn_coef, gn_silu=gn_silu,
-                                                 out_split2=out_split2, skip=skip, phases=phases)
+                                                 out_split2=out_split2, skip=skip, phases=phases, stride=stride)
     _call('dts_conv2d', C.byref(a))
     if out_split2:
         return SplitQKV(out, (out.shape[0], out.shape[1], out.shape[2], out.shape[3] // 2))

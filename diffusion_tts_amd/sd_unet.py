@@ -12,7 +12,8 @@ and the VAE decoder, plus the three the transformer blocks need:
   attention over the text tokens     -> dts_cross_attention (K and V of a head in LDS at once; rows that share a context share its k|v)
   LayerNorm, GEGLU                   -> dts_layer_norm, dts_geglu
   time embedding                     -> dts_pos_embedding, dts_linear (f32)
-  Downsample2D (3x3, stride 2)       -> dts_space_to_depth2 + a 3x3 stride-1 conv over 4C channels (ops.stride2_conv_weight)
+  Downsample2D (3x3, stride 2)       -> dts_space_to_depth2 + a 3x3 stride-1 conv over 4C channels (ops.stride2_conv_weight): downsample='s2d',
+                                        the default; downsample='strided': dts_conv2d's stride-2 form over the C channels themselves
   torch.unique(dim=0) over the contexts -> dts_group_rows (which rows carry the same text context, in order of first occurrence, no sort)
 The forward is a host part (argument checks, the timestep, grouping) and a fixed-shape device part (_device_forward: the distinct contexts and
 a row map in, no host read) that graphs.GraphCache captures once per shape and replays, like the EDM denoisers' forwards.
@@ -78,6 +79,7 @@ def padded_head_dim(d):
 
 
 HEAD_DIMS = ('padded', 'native')
+DOWNSAMPLE = ('s2d', 'strided')
 
 
 def native_head_dim(d, heads):
@@ -114,14 +116,19 @@ class SDUNet:
     takes_context_rows = True       # __call__(..., context_rows=): the distinct contexts and a row map instead of one context per row
 
     def __init__(self, state_dict, block_out_channels=(320, 640, 1280, 1280), attention_head_dim=8, cross_attention_dim=768,
-                 layers_per_block=2, sample_size=64, device='cuda', dtype=torch.float16, head_dims='padded'):
+                 layers_per_block=2, sample_size=64, device='cuda', dtype=torch.float16, head_dims='padded', downsample='s2d'):
         """attention_head_dim: the NUMBER of heads of every transformer block (diffusers' historical name for it, unet_2d_condition.py:
         `num_attention_heads = num_attention_heads or attention_head_dim`).
         head_dims: 'padded' (default) zero-pads every head to 64 / 128 / 256 at load time (padded_head_dim); 'native' keeps the smallest
-        head dim the attention kernels take (native_head_dim: 40 / 80 / 160 as stored at SD-1.x widths, nothing padded)."""
+        head dim the attention kernels take (native_head_dim: 40 / 80 / 160 as stored at SD-1.x widths, nothing padded).
+        downsample: 's2d' (default) runs the three Downsample2D layers as space-to-depth + a 3x3 stride-1 convolution over 4*C channels
+        (9 of its 36 tap-by-phase slots live); 'strided' runs them as the stride-2 3x3 convolution they are (ops.conv2d(stride=2): a
+        quarter of the multiply-adds and of the packed weight, no space-to-depth pass).  Independent of head_dims."""
         if head_dims not in HEAD_DIMS:
             raise ValueError(f'SDUNet: head_dims={head_dims!r} is not one of {HEAD_DIMS}')
-        self.head_dims = head_dims
+        if downsample not in DOWNSAMPLE:
+            raise ValueError(f'SDUNet: downsample={downsample!r} is not one of {DOWNSAMPLE}')
+        self.head_dims, self.downsample = head_dims, downsample
         blocks.require_gpu('SDUNet')
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError('SDUNet: activations are float16 or bfloat16')
@@ -136,13 +143,15 @@ class SDUNet:
         self._graphs = GraphCache(self._device_forward)      # one capture per (rows, latent size, number of distinct contexts)
 
     @classmethod
-    def from_pretrained(cls, path, device='cuda', dtype=torch.float16, head_dims='padded'):
+    def from_pretrained(cls, path, device='cuda', dtype=torch.float16, head_dims='padded', downsample='s2d'):
         """Reads a diffusers `unet/` directory: `config.json` for the shape and `diffusion_pytorch_model[.fp16].safetensors` for the
-        parameters -- the on-disk format of SD-1.5's U-Net.  A `.bin` pickle is not read.  head_dims: as the constructor's."""
+        parameters -- the on-disk format of SD-1.5's U-Net.  A `.bin` pickle is not read.  head_dims, downsample: as the constructor's."""
         import json
         import os
         if head_dims not in HEAD_DIMS:
             raise ValueError(f'SDUNet: head_dims={head_dims!r} is not one of {HEAD_DIMS}')
+        if downsample not in DOWNSAMPLE:
+            raise ValueError(f'SDUNet: downsample={downsample!r} is not one of {DOWNSAMPLE}')
         cfg_file = os.path.join(path, 'config.json')
         if not os.path.exists(cfg_file):
             raise FileNotFoundError(f'{path}: no config.json (the configuration is not guessed: only a stock SD-1.x U-Net is accepted, by name)')
@@ -153,7 +162,7 @@ class SDUNet:
         kw = {k: cfg[k] for k in ('attention_head_dim', 'cross_attention_dim', 'layers_per_block', 'sample_size') if k in cfg}
         if 'block_out_channels' in cfg:
             kw['block_out_channels'] = tuple(cfg['block_out_channels'])
-        return cls(sd, device=device, dtype=dtype, head_dims=head_dims, **kw)
+        return cls(sd, device=device, dtype=dtype, head_dims=head_dims, downsample=downsample, **kw)
 
     # ---- parameters ----------------------------------------------------------------------------
     def _resnet_params(self, sd, key):
@@ -231,7 +240,9 @@ class SDUNet:
                 layers.append((self._resnet_params(sd, f'down_blocks.{i}.resnets.{j}'),
                                self._transformer_params(sd, f'down_blocks.{i}.attentions.{j}', c) if cross else None))
             ds = None
-            if i != len(boc) - 1:
+            if i != len(boc) - 1 and self.downsample == 'strided':
+                ds = p.conv(sd, f'down_blocks.{i}.downsamplers.0.conv')              # the plain 3x3 layer [C, 3, 3, C]
+            elif i != len(boc) - 1:
                 w = ops.stride2_conv_weight(p.f32(sd[f'down_blocks.{i}.downsamplers.0.conv.weight']))
                 ds = p.pack(w, p.f32(sd[f'down_blocks.{i}.downsamplers.0.conv.bias']))
             self.down.append((layers, ds))
@@ -301,7 +312,10 @@ class SDUNet:
                     x = self._transformer(x, A, kv, kv_rows)
                 skips.append(x)
             if ds is not None:
-                x = ops.conv2d(ops.space_to_depth2(x, self.dtype), *ds, gn_stats=True)
+                if self.downsample == 'strided':
+                    x = ops.conv2d(x, *ds, stride=2, gn_stats=True)
+                else:
+                    x = ops.conv2d(ops.space_to_depth2(x, self.dtype), *ds, gn_stats=True)
                 skips.append(x)
         x = self._resnet(x, self.mid[0], temb)
         x = self._transformer(x, self.mid[1], kv, kv_rows)

@@ -63,7 +63,8 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      124: dts_candidate_noise_rows (mode / scale per output row: searches of several seeds in lock-step);
                                      125: dts_candidate_noise_sd_rows, dts_ddim_candidates_groups (the SD backend's searches of several seeds in lock-step);
                                      125, domain widened without a signature change: dts_attention (16-bit types) and dts_cross_attention take
-                                          head dims 40 / 80 / 160 at their true width (SD-1.x's heads without zero padding)) */
+                                          head dims 40 / 80 / 160 at their true width (SD-1.x's heads without zero padding); dts_conv_args.up
+                                          takes -1 (3x3, stride 2: SD-1.x's downsamplers without space-to-depth; it was read as "upsample" before)) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -104,7 +105,15 @@ typedef struct dts_conv_args {
                                      2*py + px, taps (ty, tx) row-major at the low-resolution offsets (ty - 1 + py, tx - 1 + px), each tap the sum
                                      of the 3x3 taps that fall on that input pixel (rows, py = 0: {w0, w1+w2}; py = 1: {w0+w1, w2}; columns
                                      alike), `acc_scale` that tensor's power of two; the output is [n][2*hin][2*win][cout] as for 1, 4/9 of the
-                                     multiply-adds.  Only launches for which dts_conv_takes_phases() returns 1 accept it */
+                                     multiply-adds.  Only launches for which dts_conv_takes_phases() returns 1 accept it;
+                                     -1 (DTS_F16 / DTS_BF16, ksize 3 only): zero padding 1, STRIDE 2 (an SD Downsample2D): the output is
+                                     [n][(hin+1)/2][(win+1)/2][cout], output pixel (i, j) reads input rows 2i-1 .. 2i+1 and columns 2j-1 .. 2j+1, taps
+                                     outside the image are zero; odd sizes are allowed.  `w` is the ordinary packed 3x3 weight.  x2 / c2, bias,
+                                     bias_nc, residual (at the output size), out_scale, stats_out (hout*wout % 64 == 0), workspace (K split) and
+                                     the timing events work as for 0; DTS_F32, DTS_F16X3, ksize 1, gn_coef, skip_*, out_split2 and an acc_scale
+                                     other than 0 / 1 are refused.  Always conv_igemm_kernel (dts_conv_kernel 0; the three queries below answer
+                                     0), with 4 | 8 waves and a 2- | 3-deep ring: DTS_CONV_STAGES=4 runs the 3-deep ring, and dts_conv_plan reports
+                                     what runs.  Values below -1 are refused */
   float out_scale;                /* out = (conv + bias + bias_nc + residual) * out_scale  (networks.py:179,186 skip_scale) */
   int32_t dtype;
   void* workspace;                /* optional scratch (16-byte aligned) for split-K partial sums; NULL disables split-K */

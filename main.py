@@ -22,6 +22,8 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
     --unet      : SD backend: diffusers (default: the stock UNet2DConditionModel) | hip (sd_unet.SDUNet on this build's kernels, read from
                   $DTS_SD_UNET_DIR or the cached snapshot's unet/; no fallback).  --vae hip|diffusers likewise (default hip)
     --unet-head-dims: --unet hip: padded (default: head dims 40 / 80 / 160 zero-padded to 64 / 128 / 256 at load time) | native (as stored)
+    --unet-downsample: --unet hip: s2d (default: the stride-2 downsamplers as space-to-depth + a stride-1 conv over 4C channels) | strided
+              (the stride-2 3x3 convolution itself: a quarter of the multiply-adds, no space-to-depth pass); refused without --unet hip
     --text-encoder: SD backend: transformers (default: the stock CLIPTextModel) | hip (clip_text.CLIPTextTower on this build's kernels, read
                   from $DTS_SD_TEXT_ENCODER_DIR or the cached snapshot's text_encoder/; no fallback)
     --clip-tower: SD backend, --scorer clip: transformers (default: the stock CLIPModel image tower, float32 like the reference) | hip
@@ -106,14 +108,19 @@ def load_sd_vae(model_id, dev, kind='hip'):
     return VAEDecoder.from_pretrained(path, device=dev, dtype=torch.float16)
 
 
-def load_sd_unet(model_id, dev, kind='diffusers', head_dims='padded'):
+def load_sd_unet(model_id, dev, kind='diffusers', head_dims='padded', downsample='s2d'):
     """The SD U-Net of the search loop, the twin of load_sd_vae.  kind='hip' (`--unet hip`): this build's HIP U-Net (sd_unet.SDUNet, drop-in
     for `unet(sample, t, encoder_hidden_states=...)`) read from the safetensors `unet/` directory of the locally cached SD-1.5 snapshot (or
     $DTS_SD_UNET_DIR) -- and an error when that directory cannot be found or read: there is no silent fallback.  kind='diffusers' (the
     default): the stock UNet2DConditionModel module.  head_dims (`--unet-head-dims`, kind='hip' only): 'padded' (default) or 'native', see
-    sd_unet.SDUNet; any other value is refused before a file is touched."""
+    sd_unet.SDUNet; any other value is refused before a file is touched.  downsample (`--unet-downsample`): 's2d' (default) or 'strided',
+    see sd_unet.SDUNet; any other value, and 'strided' with another kind than 'hip', is refused before a file is touched."""
     if head_dims not in ('padded', 'native'):
         raise ValueError(f"--unet-head-dims must be 'padded' or 'native', got {head_dims!r}")
+    if downsample not in ('s2d', 'strided'):
+        raise ValueError(f"--unet-downsample must be 's2d' or 'strided', got {downsample!r}")
+    if downsample != 's2d' and kind != 'hip':
+        raise ValueError(f"--unet-downsample {downsample} goes with --unet hip (the stock module has one downsampler), got --unet {kind}")
     if kind == 'diffusers':
         from diffusers import UNet2DConditionModel
         return UNet2DConditionModel.from_pretrained(model_id, subfolder='unet', torch_dtype=torch.float16, local_files_only=True).to(dev)
@@ -126,7 +133,7 @@ def load_sd_unet(model_id, dev, kind='diffusers', head_dims='padded'):
         path = os.path.join(snapshot_download(model_id, local_files_only=True, allow_patterns=['unet/*']), 'unet')
     if not os.path.isdir(path):
         raise FileNotFoundError(f'SD U-Net directory {path!r} not found (set DTS_SD_UNET_DIR, or pass --unet diffusers for the stock module)')
-    return SDUNet.from_pretrained(path, device=dev, dtype=torch.float16, head_dims=head_dims)
+    return SDUNet.from_pretrained(path, device=dev, dtype=torch.float16, head_dims=head_dims, downsample=downsample)
 
 
 def load_sd_text_encoder(model_id, dev, kind='transformers'):
@@ -178,7 +185,8 @@ def main_sd(args):
         torch.cuda.set_device(local)
         dist.init_process_group('nccl', device_id=torch.device('cuda', local))
     dev = torch.device('cuda', local) if world > 1 else torch.device(args.device)
-    unet = load_sd_unet(model_id, dev, unet_kind, head_dims=getattr(args, 'unet_head_dims', 'padded'))
+    unet = load_sd_unet(model_id, dev, unet_kind, head_dims=getattr(args, 'unet_head_dims', 'padded'),
+                        downsample=getattr(args, 'unet_downsample', 's2d'))
     vae = load_sd_vae(model_id, dev, vae_kind)
     tok = CLIPTokenizer.from_pretrained(model_id, subfolder='tokenizer', local_files_only=True)
     te = load_sd_text_encoder(model_id, dev, te_kind)
@@ -220,8 +228,18 @@ def main_sd(args):
     return best
 
 
+class _Parser(argparse.ArgumentParser):
+    """the flags that only go together are refused where the command line is parsed (usage message, exit status 2)"""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if getattr(ns, 'unet_downsample', 's2d') != 's2d' and getattr(ns, 'unet', 'diffusers') != 'hip':
+            self.error(f'--unet-downsample {ns.unet_downsample} goes with --unet hip, got --unet {ns.unet}')
+        return ns
+
+
 def build_parser():
-    parser = argparse.ArgumentParser(description='Unified Diffusion Image Generator (EDM/SD), MI355X-native hot path',
+    parser = _Parser(description='Unified Diffusion Image Generator (EDM/SD), MI355X-native hot path',
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument('--backend', type=str, choices=['edm', 'sd'], required=True, help='Backend: edm or sd')
     parser.add_argument('--scorer', type=str, choices=['brightness', 'compressibility', 'clip', 'imagenet'], required=True,
@@ -247,6 +265,9 @@ def build_parser():
     parser.add_argument('--unet-head-dims', dest='unet_head_dims', type=str, default='padded', choices=['padded', 'native'],
                         help="--unet hip: 'padded' = SD-1.x's head dims 40 / 80 / 160 zero-padded to 64 / 128 / 256 at load time, 'native' = kept as "
                              "stored (the attention kernels pad on chip; the q/k/v/out projections run at the model's own widths)")
+    parser.add_argument('--unet-downsample', dest='unet_downsample', type=str, default='s2d', choices=['s2d', 'strided'],
+                        help="--unet hip only: 's2d' = the three stride-2 downsamplers as space-to-depth + a stride-1 3x3 convolution over 4C channels, "
+                             "'strided' = the stride-2 3x3 convolution itself (a quarter of the multiply-adds and of the packed weight)")
     parser.add_argument('--text-encoder', dest='text_encoder', type=str, default='transformers', choices=['transformers', 'hip'],
                         help="SD backend: 'hip' = this build's CLIP text tower on the HIP kernels in float16 (an error if its safetensors cannot be "
                              "read), 'transformers' = the stock CLIPTextModel")

@@ -23,7 +23,10 @@ the mode of that model).  No pass/fail threshold.
 --head-dims padded,native: instead of the above, per dtype one model of each listed SDUNet head_dims mode in ONE process on the same inputs;
 replayed context_rows forwards alternate between the modes, forward by forward, device events around each; reports the median, minimum
 and maximum of --iters forwards per mode after the warm-up, the ratio of the medians against the first listed mode, and rel. max
-|difference| of the outputs.  The padded mode is the default path, so it is what native is measured against in the same minute."""
+|difference| of the outputs.  The padded mode is the default path, so it is what native is measured against in the same minute.
+--downsample s2d,strided: the same table for the SDUNet downsample modes (head_dims padded), plus `downsample_layers`: the three Downsample2D
+launches alone at --rows rows ([rows, 64 / 32 / 16, .., 320 / 640 / 1280] inputs), both routes alternating, a device-event pair around each
+route's launches (the space-to-depth pass counts with its convolution), median / min / max of --iters in microseconds."""
 import argparse
 import json
 import os
@@ -120,18 +123,51 @@ def grouping(ehs, reps=20):
     return out
 
 
-def head_dims_table(a, res, sd, x32, c2):
-    """--head-dims: the listed modes against each other, alternating forward by forward through graph replay with context_rows="""
-    modes = a.head_dims.split(',')
-    res['what'] += '; head_dims modes alternating, graph replay, context_rows='
-    res['head_dims'] = modes
+def downsample_layers(a, dt, boc=(320, 640, 1280), res=64):
+    """the three Downsample2D launches alone, both routes on the same input and weight, alternating launch by launch"""
+    g = torch.Generator().manual_seed(1)
+    out = {}
+    for i, c in enumerate(boc):
+        hw = res >> i
+        x = torch.randn(a.rows, hw, hw, c, generator=g).to('cuda', dt)
+        w = (torch.randn(c, c, 3, 3, generator=g) / (3.0 * c ** 0.5)).to('cuda')
+        b = torch.randn(c, generator=g).to('cuda')
+        w1, w4 = ops.pack_conv_weight(w, dt), ops.pack_conv_weight(ops.stride2_conv_weight(w), dt)
+        routes = {'s2d': lambda: ops.conv2d(ops.space_to_depth2(x, dt), w4, b, gn_stats=True),
+                  'strided': lambda: ops.conv2d(x, w1, b, stride=2, gn_stats=True)}
+        plans = {'s2d': ops.conv_plan(ops.space_to_depth2(x, dt), w4, b, gn_stats=True), 'strided': ops.conv_plan(x, w1, b, stride=2, gn_stats=True)}
+        times = {r: [] for r in routes}
+        for it in range(max(a.warmup, 3) + a.iters):
+            for r, f in routes.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                y = f()
+                e1.record()
+                torch.cuda.synchronize()
+                if it >= max(a.warmup, 3):
+                    times[r].append(e0.elapsed_time(e1) * 1e3)
+        ys = {r: f() for r, f in routes.items()}
+        out[f'{hw}x{hw}x{c}'] = {r: {'us_median': round(statistics.median(v), 1), 'us_min': round(min(v), 1), 'us_max': round(max(v), 1),
+                                     'plan': {k: plans[r][k] for k in ('kernel', 'tile', 'waves', 'stages', 'splits', 'ks_per_split', 'nblk')}}
+                                 for r, v in times.items()}
+        out[f'{hw}x{hw}x{c}']['median_ratio_strided_to_s2d'] = round(statistics.median(times['strided']) / statistics.median(times['s2d']), 4)
+        out[f'{hw}x{hw}x{c}']['rel_max_diff'] = float((ys['strided'].float() - ys['s2d'].float()).abs().max() / ys['s2d'].float().abs().max())
+    return out
+
+
+def head_dims_table(a, res, sd, x32, c2, key='head_dims'):
+    """--head-dims / --downsample: the listed modes of that SDUNet keyword against each other, alternating forward by forward through graph
+    replay with context_rows="""
+    modes = getattr(a, key).split(',')
+    res['what'] += f'; {key} modes alternating, graph replay, context_rows='
+    res[key] = modes
     for name in a.dtypes.split(','):
         dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[name]
         x = x32.to('cuda', dt)
         t = torch.tensor(501, device='cuda')
         ctx = c2.to('cuda', dt).contiguous()
         rmap = torch.tensor([0] * (a.rows // 2) + [1] * (a.rows - a.rows // 2), dtype=torch.int32).to('cuda')
-        unets = {m: SDUNet(sd, device='cuda', dtype=dt, head_dims=m) for m in modes}
+        unets = {m: SDUNet(sd, device='cuda', dtype=dt, **{key: m}) for m in modes}
         run = lambda u: u(x, t, encoder_hidden_states=ctx, context_rows=rmap)[0]
         for _ in range(max(a.warmup, 3)):
             outs = {m: run(u) for m, u in unets.items()}
@@ -154,6 +190,9 @@ def head_dims_table(a, res, sd, x32, c2):
                                'rel_max_diff_to_' + modes[0]: {m: float((outs[m].float() - base).abs().max() / base.abs().max()) for m in modes},
                                'attention_channels': {m: sorted({A.hp for A in u._tfm}) for m, u in unets.items()},
                                'output_finite': all(bool(torch.isfinite(o).all()) for o in outs.values())}
+        if key == 'downsample':
+            res['dtypes'][name]['downsampler_cin'] = {m: [d[0].shape[3] for _, d in u.down[:3]] for m, u in unets.items()}
+            res['dtypes'][name]['downsample_layers'] = downsample_layers(a, dt)
         del unets
         torch.cuda.empty_cache()
     print(json.dumps(res))
@@ -167,6 +206,7 @@ def main():
     ap.add_argument('--dtypes', default='f16,bf16')
     ap.add_argument('--replay-only', type=int, default=0, help='only this many replayed context_rows forwards after the warm-up (for a kernel trace)')
     ap.add_argument('--head-dims', default='', help="e.g. padded,native: time these SDUNet head_dims modes against each other (see the module docstring)")
+    ap.add_argument('--downsample', default='', help="e.g. s2d,strided: time these SDUNet downsample modes against each other, and the three downsample launches alone")
     ap.add_argument('--replay-head-dims', default='padded', choices=['padded', 'native'], help='the head_dims mode of the --replay-only model')
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -182,6 +222,8 @@ def main():
     c2 = torch.randn(2, 77, 768, generator=g)
     if a.head_dims:
         return head_dims_table(a, res, sd, x32, c2)
+    if a.downsample:
+        return head_dims_table(a, res, sd, x32, c2, key='downsample')
     for name in a.dtypes.split(','):
         dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[name]
         unet = SDUNet(sd, device='cuda', dtype=dt, head_dims=a.replay_head_dims if a.replay_only else 'padded')
