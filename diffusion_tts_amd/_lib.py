@@ -81,6 +81,9 @@ SIGNATURES = {
     'dts_heun_xhat': [_p, _i, _i, _p, _i, _d, _p, _i, _i, _p],
     'dts_heun_euler': [_p, _p, _d, _d, _p, _p, _i64, _p],
     'dts_heun_correct': [_p, _p, _p, _d, _d, _p, _i64, _p],
+    'dts_heun_xhat_rows': [_p, _i, _i, _p, _i, _p, _p, _i, _i, _p],
+    'dts_heun_euler_rows': [_p, _p, _p, _p, _p, _p, _i, _i, _p],
+    'dts_heun_correct_rows': [_p, _p, _p, _p, _p, _p, _i, _i, _p],
     'dts_ode_xhat': [_p, _p, _i, _d, _d, _d, _p, _p, _i64, _p],
     'dts_ode_slope': [_p, _p, _d, _d, _p, _d, _d, _p, _p, _p, _i64, _p],
     'dts_ode_correct': [_p, _p, _p, _p, _d, _d, _d, _d, _d, _p, _i64, _p],
@@ -118,6 +121,9 @@ def load():
         raise RuntimeError(f'{LIB_PATH} not found: the HIP extension is required (no CPU fallback). '
                            f'Build it with `python -m diffusion_tts_amd.build` or __graft_entry__.build().')
     lib = C.CDLL(LIB_PATH)
+    missing = [name for name in list(SIGNATURES) + list(OTHER) if not hasattr(lib, name)]
+    if missing:       # entry points added under an unchanged ABI number (dts_heun_*_rows): an older build passes the version check below
+        raise RuntimeError(f'{LIB_PATH} lacks {missing[:3]}: rebuild with `python -m diffusion_tts_amd.build --force`')
     for name, argt in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argt, _i

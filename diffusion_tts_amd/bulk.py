@@ -69,19 +69,24 @@ def seed_inputs(seed: int, net, class_idx: Optional[int] = None):
     return latents, labels
 
 
-def image_result(res, b, count, local_search):
+def image_result(res, b, count, local_search, mcts=False):
     """Image b's part of the result dict of a lock-step generate_image_grid(row_seeds=...) call over `count` images, shaped like a one-image
     call's: the image's slice of x, image, final_scores, rewards, selected, beam_parents and best_noises; `net_rows` is the call's count
     divided by the batch size (exact: the searches run in lock-step); `row_seeds` stays the whole batch's.  local_search: eps-greedy /
-    zero-order, whose rewards are [N, B] (every other trace tensor has the image first)."""
+    zero-order, whose rewards are [N, B] (every other trace tensor has the image first).  mcts: a lock-step MCTS call (mcts_lockstep=True),
+    whose trees are ragged: the image's rewards are its rows [group] of the [S, group] tensors, what its one-image call appends, and its
+    `net_rows` is its own entry of `search_rows`."""
     one = dict(res)
     for key in ('x', 'image', 'final_scores'):
         one[key] = res[key][b:b + 1]
     one['avg_score'] = float(one['final_scores'].float().mean())
-    one['rewards'] = [r[:, b:b + 1] if local_search else r[b:b + 1] for r in res['rewards']]
+    one['rewards'] = [r[b] if mcts else r[:, b:b + 1] if local_search else r[b:b + 1] for r in res['rewards']]
     one['selected'] = [s[b:b + 1] for s in res['selected']]
     one['beam_parents'] = [s[b:b + 1] for s in res['beam_parents']]
     one['best_noises'] = {i: v[:, b:b + 1] for i, v in res['best_noises'].items()}
+    if mcts:
+        one['net_rows'] = res['search_rows'][b]
+        return one
     assert res['net_rows'] % count == 0, (res['net_rows'], count)
     one['net_rows'] = res['net_rows'] // count
     return one
@@ -91,22 +96,30 @@ def image_result(res, b, count, local_search):
 def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAIVE, sampling_params: Optional[Dict[str, Any]] = None,
                    class_idx: Optional[int] = None, max_batch_size: int = 64, subdirs: bool = False, device='cuda',
                    compute_dtype=ops.F16X3, verbose=False, search_batch: int = 1, rank: Optional[int] = None, world: Optional[int] = None,
-                   **sampler_kwargs):
+                   mcts_lockstep: bool = False, **sampler_kwargs):
     """Returns {seed: result dict of generate_image_grid} for the seeds this rank generated.  This rank's seeds are split into batches of up to
     `search_batch` (rank_batches; rank / world default to torch.distributed's when it is initialised, else 0 / 1) and the searches of a batch
     run in lock-step as ONE generate_image_grid(row_seeds=batch) call -- search_batch x the rows in every denoiser and scorer call; image b
     draws from its own seed's stream, so a seed's search is the one it runs alone (search_batch=1: bit for bit the `seed=` call's; larger
     batches: up to the launch forms the row count selects).  One PNG per seed; each seed's dict is its slice of the call's (image_result).
-    MCTS, and calls with forced_selections / precomputed_noise (per search by nature), run one `seed=` call per seed as before.
+    MCTS, and calls with forced_selections / precomputed_noise (per search by nature), run one `seed=` call per seed as before --
+    unless `mcts_lockstep=True` (MCTS only): then the trees of a batch's seeds advance as one batch too (generate_image_grid(row_seeds=batch,
+    mcts_lockstep=True)), seed s on its own torch stream and on numpy.random.RandomState(s) for its rollout child draws.
     `max_batch_size` is accepted for the reference's signature; the split is by `search_batch`.  sampler_kwargs go to every call:
     `share_identical=True` (eps-greedy / zero-order / beam_search=True) evaluates the identical candidates of a sigma step without churn
     noise once per image -- the same PNGs from fewer denoiser rows."""
     rank, world = rank_world(rank, world)
     if int(search_batch) < 1:
         raise ValueError(f'search_batch: a positive number of seeds per lock-step batch, got {search_batch}')
+    if mcts_lockstep and sampling_method != SamplingMethod.MCTS:
+        raise ValueError(f'mcts_lockstep=True: SamplingMethod.MCTS only, got {sampling_method.name}')
+    per_search = any(sampler_kwargs.get(k) is not None for k in ('forced_selections', 'precomputed_noise'))
+    if mcts_lockstep and per_search:
+        raise ValueError('mcts_lockstep=True: forced_selections / precomputed_noise are not supported with per-image random streams')
     net = load_network(network, device=device, dtype=compute_dtype)
-    lock_step = sampling_method != SamplingMethod.MCTS and not any(
-        sampler_kwargs.get(k) is not None for k in ('forced_selections', 'precomputed_noise'))
+    lock_step = (sampling_method != SamplingMethod.MCTS or mcts_lockstep) and not per_search
+    if mcts_lockstep:
+        sampler_kwargs = dict(sampler_kwargs, mcts_lockstep=True)
     local_search = sampling_method in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER)
     done = {}
 
@@ -125,7 +138,7 @@ def generate_seeds(network, seeds, outdir, *, sampling_method=SamplingMethod.NAI
         labels = None if inputs[0][1] is None else torch.cat([lab for _, lab in inputs], dim=0)
         res = generate_image_grid(net, None, latents, labels, row_seeds=batch, **common)
         for b, seed in enumerate(batch):
-            done[seed] = image_result(res, b, len(batch), local_search)
+            done[seed] = image_result(res, b, len(batch), local_search, mcts=mcts_lockstep)
             save_image(done[seed]['image'][0].permute(1, 2, 0).contiguous().numpy(), seed_png_path(outdir, seed, subdirs))
     return done
 

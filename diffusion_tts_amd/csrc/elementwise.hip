@@ -188,6 +188,20 @@ __global__ void precond_out_kernel(const double* __restrict__ x, const float* __
 }
 
 // ---- K9: Heun / Euler step, fp64 state (edm/main.py:82-96) ---------------------------------------------
+// Each op is ONE body over one element, given the step's scalars; a kernel is a form of where the scalars come from:
+//   scalar   kernel arguments, one step for the whole launch (dt = t_next - t_hat once per thread, as ever)
+//   per row  float64 device arrays with one entry per row (the MCTS expansions of several searches in one launch stand at different sigma
+//            steps): row i computes what the scalar form computes when launched with coef[i], t_hat[i], t_next[i], bit for bit.
+__device__ __forceinline__ double heun_xhat_at(double x, double coef, double eps) { return x + coef * eps; }
+__device__ __forceinline__ void heun_euler_at(double xh, double D, double t_hat, double dt, double& d, double& xn) {
+  d = (xh - D) / t_hat;
+  xn = xh + dt * d;
+}
+__device__ __forceinline__ double heun_correct_at(double xh, double xn, double D2, double d_cur, double t_next, double dt) {
+  const double dp = (xn - D2) / t_next;
+  return xh + dt * (0.5 * d_cur + 0.5 * dp);
+}
+
 template <typename E>
 __global__ void heun_xhat_kernel(const double* __restrict__ x_cur, int xb, int bcast, const E* __restrict__ eps, double coef,
                                  double* __restrict__ x_hat, int nb, int chw) {
@@ -197,25 +211,57 @@ __global__ void heun_xhat_kernel(const double* __restrict__ x_cur, int xb, int b
     const int row = (int)(i / chw);
     const long long e = i - (long long)row * chw;
     const int src = bcast ? row / rep : row % xb;
-    x_hat[i] = x_cur[(long long)src * chw + e] + coef * (double)eps[i];
+    x_hat[i] = heun_xhat_at(x_cur[(long long)src * chw + e], coef, (double)eps[i]);
+  }
+}
+template <typename E>
+__global__ void heun_xhat_rows_kernel(const double* __restrict__ x_cur, int xb, int bcast, const E* __restrict__ eps,
+                                      const double* __restrict__ coef, double* __restrict__ x_hat, int nb, int chw) {
+  const long long total = (long long)nb * chw;
+  const int rep = nb / xb;
+  GSL(i, total) {
+    const int row = (int)(i / chw);
+    const long long e = i - (long long)row * chw;
+    const int src = bcast ? row / rep : row % xb;
+    x_hat[i] = heun_xhat_at(x_cur[(long long)src * chw + e], coef[row], (double)eps[i]);
   }
 }
 __global__ void heun_euler_kernel(const double* __restrict__ x_hat, const float* __restrict__ D, double t_hat, double t_next,
                                   double* __restrict__ d_cur, double* __restrict__ x_next, long long count) {
   const double dt = t_next - t_hat;
   GSL(i, count) {
-    const double xh = x_hat[i];
-    const double d = (xh - (double)D[i]) / t_hat;
+    double d, xn;
+    heun_euler_at(x_hat[i], (double)D[i], t_hat, dt, d, xn);
     d_cur[i] = d;
-    x_next[i] = xh + dt * d;
+    x_next[i] = xn;
+  }
+}
+__global__ void heun_euler_rows_kernel(const double* __restrict__ x_hat, const float* __restrict__ D, const double* __restrict__ t_hat,
+                                       const double* __restrict__ t_next, double* __restrict__ d_cur, double* __restrict__ x_next, int n,
+                                       int chw) {
+  const long long total = (long long)n * chw;
+  GSL(i, total) {
+    const int row = (int)(i / chw);
+    const double th = t_hat[row];
+    double d, xn;
+    heun_euler_at(x_hat[i], (double)D[i], th, t_next[row] - th, d, xn);
+    d_cur[i] = d;
+    x_next[i] = xn;
   }
 }
 __global__ void heun_correct_kernel(const double* __restrict__ x_hat, const float* __restrict__ D2, const double* __restrict__ d_cur,
                                     double t_hat, double t_next, double* __restrict__ x_next, long long count) {
   const double dt = t_next - t_hat;
-  GSL(i, count) {
-    const double dp = (x_next[i] - (double)D2[i]) / t_next;
-    x_next[i] = x_hat[i] + dt * (0.5 * d_cur[i] + 0.5 * dp);
+  GSL(i, count) x_next[i] = heun_correct_at(x_hat[i], x_next[i], (double)D2[i], d_cur[i], t_next, dt);
+}
+__global__ void heun_correct_rows_kernel(const double* __restrict__ x_hat, const float* __restrict__ D2, const double* __restrict__ d_cur,
+                                         const double* __restrict__ t_hat, const double* __restrict__ t_next, double* __restrict__ x_next,
+                                         int n, int chw) {
+  const long long total = (long long)n * chw;
+  GSL(i, total) {
+    const int row = (int)(i / chw);
+    const double tn = t_next[row];
+    x_next[i] = heun_correct_at(x_hat[i], x_next[i], (double)D2[i], d_cur[i], tn, tn - t_hat[row]);
   }
 }
 
@@ -828,6 +874,41 @@ extern "C" int dts_heun_correct(const double* x_hat, const float* D2, const doub
   hipLaunchKernelGGL(heun_correct_kernel, dim3(grid1d(count)), dim3(256), 0, st, x_hat, D2, d_cur, t_hat, t_next, x_next,
                      (long long)count);
   DTS_CHECK_LAUNCH("dts_heun_correct");
+  return DTS_OK;
+}
+// The per-row forms: the coefficient arrays live on the device and are read by the kernel alone, so t_hat[i] == 0 / t_next[i] == 0 cannot be
+// refused here without a host read; the caller holds the host values and checks them before it uploads them (ops.py).
+extern "C" int dts_heun_xhat_rows(const double* x_cur, int xb, int bcast, const void* eps, int eps_f32, const double* noise_coef,
+                                  double* x_hat, int nb, int chw, dts_stream s) {
+  DTS_CHECK_ARG(x_cur && eps && noise_coef && x_hat && nb > 0 && chw > 0, "dts_heun_xhat_rows: bad args");
+  DTS_CHECK_ARG(xb > 0 && nb % xb == 0, "dts_heun_xhat_rows: nb=%d not a multiple of xb=%d", nb, xb);
+  ST;
+  const int g = grid1d((long long)nb * chw);
+  if (eps_f32)
+    hipLaunchKernelGGL((heun_xhat_rows_kernel<float>), dim3(g), dim3(256), 0, st, x_cur, xb, bcast, (const float*)eps, noise_coef, x_hat,
+                       nb, chw);
+  else
+    hipLaunchKernelGGL((heun_xhat_rows_kernel<double>), dim3(g), dim3(256), 0, st, x_cur, xb, bcast, (const double*)eps, noise_coef, x_hat,
+                       nb, chw);
+  DTS_CHECK_LAUNCH("dts_heun_xhat_rows");
+  return DTS_OK;
+}
+extern "C" int dts_heun_euler_rows(const double* x_hat, const float* D, const double* t_hat, const double* t_next, double* d_cur,
+                                   double* x_next, int n, int chw, dts_stream s) {
+  DTS_CHECK_ARG(x_hat && D && t_hat && t_next && d_cur && x_next && n > 0 && chw > 0, "dts_heun_euler_rows: bad args");
+  ST;
+  hipLaunchKernelGGL(heun_euler_rows_kernel, dim3(grid1d((long long)n * chw)), dim3(256), 0, st, x_hat, D, t_hat, t_next, d_cur, x_next, n,
+                     chw);
+  DTS_CHECK_LAUNCH("dts_heun_euler_rows");
+  return DTS_OK;
+}
+extern "C" int dts_heun_correct_rows(const double* x_hat, const float* D2, const double* d_cur, const double* t_hat, const double* t_next,
+                                     double* x_next, int n, int chw, dts_stream s) {
+  DTS_CHECK_ARG(x_hat && D2 && d_cur && t_hat && t_next && x_next && n > 0 && chw > 0, "dts_heun_correct_rows: bad args");
+  ST;
+  hipLaunchKernelGGL(heun_correct_rows_kernel, dim3(grid1d((long long)n * chw)), dim3(256), 0, st, x_hat, D2, d_cur, t_hat, t_next, x_next,
+                     n, chw);
+  DTS_CHECK_LAUNCH("dts_heun_correct_rows");
   return DTS_OK;
 }
 

@@ -1085,6 +1085,62 @@ def heun_correct(x_hat, D2, d_cur, t_hat, t_next, x_next):
     return x_next
 
 
+def row_scalars(values, n, name, device, nonzero=False):
+    """The per-row scalars of a dts_heun_*_rows launch: `values`, a sequence or a tensor of n numbers, as a float64 device tensor [n].  A
+    tensor that is already that is passed through unread (the caller checked it on the host before uploading it, once for several launches);
+    anything else is a host array, checked here -- with nonzero=True an entry equal to 0 is refused by name, which the kernel's entry point
+    cannot do without a host read -- and uploaded."""
+    if isinstance(values, torch.Tensor) and values.is_cuda:
+        if values.dtype != torch.float64 or tuple(values.shape) != (n,):
+            raise ValueError(f'{name}: a device tensor must be float64 [{n}], got {values.dtype} {tuple(values.shape)}')
+        return values.contiguous()
+    host = torch.as_tensor(values, dtype=torch.float64).reshape(-1)
+    if host.numel() != n:
+        raise ValueError(f'{name}: need one value per row, got {host.numel()} values for {n} rows')
+    if nonzero and bool((host == 0).any()):
+        raise ValueError(f'{name} == 0 in row {int((host == 0).nonzero()[0])}')
+    return host.to(device).contiguous()
+
+
+def heun_xhat_rows(x_cur, eps, noise_coef, nb, interleave=False):
+    """heun_xhat with a noise coefficient per row: x_hat[i] = x_cur[src(i)] + noise_coef[i]*eps[i].  noise_coef: nb numbers (sequence or
+    tensor).  Row i has the bits of heun_xhat launched with noise_coef[i]; a row whose coefficient is 0.0 is its source row."""
+    xb = x_cur.shape[0]
+    chw = x_cur[0].numel()
+    if eps.dtype not in (torch.float64, torch.float32):
+        raise ValueError('eps must be float64 or float32')
+    if eps.shape[0] != nb:
+        raise ValueError('eps rows != nb')
+    coef = row_scalars(noise_coef, nb, 'heun_xhat_rows: noise_coef', x_cur.device)
+    x_hat = torch.empty((nb,) + tuple(x_cur.shape[1:]), dtype=torch.float64, device=x_cur.device)
+    _call('dts_heun_xhat_rows', _ptr(x_cur, 'x_cur', torch.float64), xb, int(interleave), _ptr(eps, 'eps'),
+          int(eps.dtype == torch.float32), _ptr(coef), _ptr(x_hat), nb, chw)
+    return x_hat
+
+
+def heun_euler_rows(x_hat, D, t_hat, t_next):
+    """heun_euler with t_hat / t_next per row (n numbers each); a host array holding t_hat == 0 is refused before any launch"""
+    n, chw = x_hat.shape[0], x_hat[0].numel()
+    th = row_scalars(t_hat, n, 'heun_euler_rows: t_hat', x_hat.device, nonzero=True)
+    tn = row_scalars(t_next, n, 'heun_euler_rows: t_next', x_hat.device)
+    d_cur = torch.empty_like(x_hat)
+    x_next = torch.empty_like(x_hat)
+    _call('dts_heun_euler_rows', _ptr(x_hat, 'x_hat', torch.float64), _ptr(D, 'D', torch.float32), _ptr(th), _ptr(tn),
+          _ptr(d_cur), _ptr(x_next), n, chw)
+    return d_cur, x_next
+
+
+def heun_correct_rows(x_hat, D2, d_cur, t_hat, t_next, x_next):
+    """heun_correct with t_hat / t_next per row (in place on x_next); a host array holding t_next == 0 (the last sigma step is Euler only) is
+    refused before any launch"""
+    n, chw = x_hat.shape[0], x_hat[0].numel()
+    th = row_scalars(t_hat, n, 'heun_correct_rows: t_hat', x_hat.device)
+    tn = row_scalars(t_next, n, 'heun_correct_rows: t_next', x_hat.device, nonzero=True)
+    _call('dts_heun_correct_rows', _ptr(x_hat, 'x_hat', torch.float64), _ptr(D2, 'D2', torch.float32),
+          _ptr(d_cur, 'd_cur', torch.float64), _ptr(th), _ptr(tn), _ptr(x_next, 'x_next', torch.float64), n, chw)
+    return x_next
+
+
 # ---- the general ODE step (ablation sampler, edm/generate.py:156-174) ---------------------------
 def ode_xhat(x_cur, eps, ratio, noise_coef, s_hat=1.0):
     """x_hat = ratio * x_cur + noise_coef * eps (eps float64 | float32; None exactly when noise_coef == 0: no noise is read).

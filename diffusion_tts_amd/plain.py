@@ -224,6 +224,22 @@ def heun_step(net, x_cur, eps, churn, t_next, last, labels, nb=None, interleave=
     return x_next, D1, D
 
 
+def heun_step_rows(net, x_cur, eps, t_hat, coef, t_next, labels, interleave=True):
+    """`heun_step` with the step's scalars PER ROW (the per-row K9 kernels): rows of one launch stand at different sigma steps, none at the last
+    one.  t_hat, coef, t_next: host sequences of eps.shape[0] numbers -- checked here (no t_hat or t_next of 0: the device arrays cannot be
+    checked without a read), uploaded once and shared by the three kernels and, as the per-row sigma, by the two denoiser calls.  x_cur
+    [xb, ...] f64 is broadcast to the rows of eps.  Row r is the row `heun_step` computes with churn = (t_hat[r], coef[r]) and t_next[r].
+    Returns x_next."""
+    nb, dev = eps.shape[0], x_cur.device
+    th = ops.row_scalars(t_hat, nb, 'heun_step_rows: t_hat', dev, nonzero=True)
+    tn = ops.row_scalars(t_next, nb, 'heun_step_rows: t_next', dev, nonzero=True)
+    x_hat = ops.heun_xhat_rows(x_cur, eps, ops.row_scalars(coef, nb, 'heun_step_rows: coef', dev), nb, interleave)
+    D = net(x_hat, th, labels)
+    d_cur, x_next = ops.heun_euler_rows(x_hat, D, th, tn)
+    D = net(x_next, tn, labels)
+    return ops.heun_correct_rows(x_hat, D, d_cur, th, tn, x_next)
+
+
 def heun_loop(net, x_next, labels, t_steps, churn, draw):
     """The search-free trajectory over t_steps (the last one 0): per step one host draw `draw(x)` for the whole batch (made at zero-noise
     steps too: the stream is the reference's), uploaded, and one `heun_step`.  churn(t_cur) -> (t_hat, coef)."""

@@ -24,7 +24,7 @@ import torch
 from . import ops
 from .hashing import builtin_scale
 from .parallel import CandidateShards
-from .plain import churn_of, edm_sigmas, heun_loop, heun_step
+from .plain import churn_of, edm_sigmas, heun_loop, heun_step, heun_step_rows
 from .scorers import Scorer, CompressibilityScorer
 
 
@@ -172,6 +172,9 @@ class _Loop:
         self.chunk = None                     # generate_image_grid(candidate_chunk=...)
         self.src = _Source()                  # generate_image_grid(row_seeds=...): one stream per image
         self.shared = frozenset()             # generate_image_grid(share_identical=True): identical_steps(...) of this schedule
+        self.row_seeds = None                 # generate_image_grid(row_seeds=...) as given: the MCTS lock-step's numpy streams are seeded from it
+        self.mcts_ragged_launches = self.mcts_mixed_launches = 0    # mcts_lockstep=True: per-row step launches; those over >= 2 sigma steps
+        self.search_rows = None               # mcts_lockstep=True: the denoiser rows of each search
 
     def up(self, t, dtype=None):
         return t.to(self.dev, dtype).contiguous() if dtype is not None else t.to(self.dev).contiguous()
@@ -189,6 +192,16 @@ class _Loop:
         if live is not None and live != nb and evals0 is not None:       # padding rows went through the denoiser but are not counted
             self.net.evals = evals0 + (self.net.evals - evals0) // nb * live
         return x_next, (D1 if first_denoised else D)
+
+    def step_rows(self, x_cur, t_hat, coef, t_next, eps, labels, live=None):
+        """`step` with the scalars of the sigma step per row (plain.heun_step_rows): x_cur [xb, ...] in repeat_interleave form, never the last
+        sigma step; live as in `step`.  Returns x_next."""
+        nb = eps.shape[0]
+        evals0 = getattr(self.net, 'evals', None)
+        x_next = heun_step_rows(self.net, x_cur, eps, t_hat, coef, t_next, labels)
+        if live is not None and live != nb and evals0 is not None:
+            self.net.evals = evals0 + (self.net.evals - evals0) // nb * live
+        return x_next
 
     def score(self, scorer, x, labels):
         img = ops.quantize_u8(x)
@@ -616,6 +629,158 @@ def _mcts(L: _Loop, t_steps, x_next, labels, p, pre):
     return torch.cat(results, dim=0)
 
 
+# granularity the lock-step MCTS batches ABOVE 16 rows are padded to (copies of row 0, not counted as evaluations): with S searches the
+# expansion and rollout batches take every size up to 16 * S, and each size would be a launch form and a captured graph of its own (graphs.py
+# keeps 4 large shapes per module).  Batches of at most 16 rows keep the rule above.  DTS_MCTS_LOCKSTEP_PAD_ROWS sets it (1 = no padding);
+# the choice is measured: DESIGN.md section 5, "MCTS in lock-step".
+def _mcts_lockstep_pad_rows():
+    v = os.environ.get('DTS_MCTS_LOCKSTEP_PAD_ROWS')
+    try:
+        return 32 if v is None else max(1, int(v))
+    except ValueError:
+        import warnings
+        warnings.warn(f'DTS_MCTS_LOCKSTEP_PAD_ROWS={v!r} is not an integer: the default granule is used')
+        return 32
+
+
+MCTS_LOCKSTEP_PAD_ROWS = _mcts_lockstep_pad_rows()
+
+
+def _pad_rows(t, rows):
+    """t [k, ...] with copies of its row 0 appended up to `rows` rows"""
+    return t if t.shape[0] >= rows else torch.cat([t, t[:1].expand(rows - t.shape[0], *t.shape[1:])], dim=0).contiguous()
+
+
+def _mcts_lockstep(L: _Loop, t_steps, x_next, labels, p, pre):
+    """generate_image_grid(row_seeds=..., mcts_lockstep=True): the MCTS searches of n seeds as one batch.  Search s is `_mcts` with B = 1 (one
+    tree; the reference's micro-batch of two images does not arise) on streams of its own: its torch draws -- the num_steps float32 draws
+    [1, b, C, H, W] up front, then the b discarded [1, C, H, W] draws of every expanding simulation -- come from lane s of `L.src`, its
+    child draws from numpy.random.RandomState(row_seeds[s]), the stream numpy's global generator gives after numpy.random.seed(row_seeds[s]);
+    the global generator is neither read nor advanced.  The trees are aligned by simulation index.  Per sigma step i (all roots at depth i):
+      root expansions   of every search whose root has no children: one scalar-sigma step of <= n * b rows;
+      simulation k      (serial: simulation k + 1 of a search may descend into the node simulation k made) every search descends its own
+                        tree on the host; the expansions of all searches that expand at k -- each at the sigma step of its own leaf --
+                        are ONE `heun_step_rows` of <= n * b rows with t_hat, noise coefficient, t_next and the network's sigma per row;
+      rollouts          of the group's simulations of all searches advance together, one scalar step per sigma step j over those that have
+                        reached it (<= 16 * n rows);
+      scoring           one scorer call for the group's n * group final states, then back-propagation and the root's best child per search.
+    Batches above 16 rows are padded to MCTS_LOCKSTEP_PAD_ROWS (expansions: to whole nodes of b rows); padding is not counted."""
+    b, S, n, ns = p.N, p.S, x_next.shape[0], L.num_steps
+    shape1 = tuple(x_next.shape[1:])
+    rngs = [np.random.RandomState(s) for s in L.row_seeds]
+    noise = [torch.stack([L.src.randn(s, (1, b) + shape1, dtype=torch.float32)[0] for i in range(ns)]) for s in range(n)]   # :446, lane by lane
+    noise = L.up(torch.stack(noise, dim=1))                                        # [ns, n, b, ...] float32
+    roots = [_Node(x_next[s:s + 1].clone(), visit=1) for s in range(n)]
+    rows = [0] * n                                                                 # denoiser rows of each search: what its solo call counts
+    G = MCTS_LOCKSTEP_PAD_ROWS
+    churn = [L.churn(t_steps[i]) for i in range(ns)]
+    stages = lambda j: 1 if j >= ns - 1 else 2
+
+    def lab_of(searches, rep=1):
+        if labels is None:
+            return None
+        return labels.index_select(0, L.up(torch.tensor(searches))).repeat_interleave(rep, dim=0).contiguous()
+
+    def padded(k):
+        """rows a batch of k live rows is launched with"""
+        if k <= 16:
+            g_ = MCTS_PAD_ROLLOUTS if getattr(L.net, 'dtype', None) != torch.float32 else 1
+            return -(-k // g_) * g_
+        return -(-k // G) * G
+
+    def padded_nodes(k):
+        """nodes a batch of k expanding nodes (b rows each) is launched with: whole nodes, the rows of a node stay together"""
+        unit = max(1, G // b)
+        return k if k * b <= 16 else -(-k // unit) * unit
+
+    for i in range(ns):
+        todo = [s for s in range(n) if not roots[s].children]
+        if todo:
+            nodes = padded_nodes(len(todo))
+            xe = _pad_rows(torch.cat([roots[s].x for s in todo], dim=0), nodes)
+            ne = _pad_rows(noise[i].index_select(0, L.up(torch.tensor(todo))).reshape(len(todo) * b, *shape1), nodes * b)
+            xn, _ = L.step(xe, t_steps[i], t_steps[i + 1], i, ne, lab_of(todo + todo[:1] * (nodes - len(todo)), b), interleave=True,
+                           live=len(todo) * b)
+            for q, s in enumerate(todo):
+                roots[s].children = [_Node(xn[q * b + j:q * b + j + 1]) for j in range(b)]
+                rows[s] += b * stages(i)
+        group = min(16, S)
+        for g0 in range(0, S, group):
+            sims = range(g0, min(g0 + group, S))
+            paths = [[] for _ in range(n)]
+            starts = [[] for _ in range(n)]
+            for k in sims:
+                leaves = []
+                for s in range(n):
+                    node, it = roots[s], i
+                    path = [node]
+                    while node.children:
+                        ucb = [float('inf') if c.visit == 0 else
+                               c.reward / c.visit + np.sqrt(2 * np.log(node.visit) / c.visit) for c in node.children]
+                        node = node.children[int(np.argmax(ucb))]
+                        it += 1
+                        path.append(node)
+                    leaves.append((node, it, path))
+                grow = [s for s in range(n) if leaves[s][1] < ns - 1]
+                if grow:
+                    for s in grow:
+                        for j in range(b):
+                            L.src.randn(s, (1,) + shape1, dtype=torch.float32)    # the reference's eager .get() default (:578-579): drawn, unused
+                    its = [leaves[s][1] for s in grow]
+                    nodes = padded_nodes(len(grow))
+                    xe = _pad_rows(torch.cat([leaves[s][0].x for s in grow], dim=0), nodes)
+                    ne = _pad_rows(torch.cat([noise[it][s] for s, it in zip(grow, its)], dim=0), nodes * b)
+                    le = lab_of(grow + grow[:1] * (nodes - len(grow)), b)
+                    per_row = lambda v: [v[it] for it in its + its[:1] * (nodes - len(its)) for _ in range(b)]
+                    xc = L.step_rows(xe, per_row([c[0] for c in churn]), per_row([c[1] for c in churn]),
+                                     per_row([float(t) for t in t_steps[1:]]), ne, le, live=len(grow) * b)
+                    L.mcts_ragged_launches += 1
+                    L.mcts_mixed_launches += len(set(its)) > 1
+                    for q, s in enumerate(grow):
+                        node, it, path = leaves[s]
+                        node.children = [_Node(xc[q * b + j:q * b + j + 1]) for j in range(b)]
+                        rows[s] += 2 * b
+                        node = node.children[rngs[s].randint(0, b)]                # :593, from the search's own numpy stream
+                        path.append(node)
+                        leaves[s] = (node, it + 1, path)
+                for s in range(n):
+                    paths[s].append(leaves[s][2])
+                    starts[s].append((leaves[s][0].x, leaves[s][1]))
+            # the group's rollouts of all searches, search-major; every live row at sigma step j shares its scalars
+            flat = [(s, q) for s in range(n) for q in range(len(sims))]
+            cur = {sq: starts[sq[0]][sq[1]][0] for sq in flat}
+            for j in range(min(starts[s][q][1] for s, q in flat), ns):
+                act = [sq for sq in flat if starts[sq[0]][sq[1]][1] <= j]
+                ka = len(act)
+                kp = padded(ka)
+                xa = _pad_rows(torch.cat([cur[sq] for sq in act], dim=0), kp)
+                la = lab_of([s for s, _ in act] + [act[0][0]] * (kp - ka))
+                xo, _ = L.step(xa, t_steps[j], t_steps[j + 1], j, torch.zeros_like(xa), la, live=ka)
+                for r_, sq in enumerate(act):
+                    cur[sq] = xo[r_:r_ + 1]
+                    rows[sq[0]] += stages(j)
+            den = torch.cat([cur[sq] for sq in flat], dim=0)
+            rew = L.score(p.scorer, den, lab_of([s for s, _ in flat])).to(L.dev, torch.float32).cpu().reshape(n, len(sims))
+            L.rewards.append(rew)
+            for s in range(n):
+                for path, r in zip(paths[s], rew[s]):
+                    for nd in path:
+                        nd.reward += r.item()
+                        nd.visit += 1
+        chosen = []
+        for s in range(n):
+            best, best_r, best_j = None, -float('inf'), -1
+            for j, c in enumerate(roots[s].children):
+                if c.visit > 0 and c.reward / c.visit > best_r:
+                    best, best_r, best_j = c, c.reward / c.visit, j
+            assert best is not None
+            chosen.append(best_j)
+            roots[s] = best
+        L.selected.append(torch.tensor(chosen))
+    L.search_rows = rows
+    return torch.cat([r.x for r in roots], dim=0)
+
+
 _METHODS = {
     SamplingMethod.NAIVE: _naive, SamplingMethod.REJECTION_SAMPLING: _rejection, SamplingMethod.BEAM_SEARCH: _beam,
     SamplingMethod.MCTS: _mcts, SamplingMethod.ZERO_ORDER: _eps_greedy, SamplingMethod.EPS_GREEDY: _eps_greedy,
@@ -634,7 +799,7 @@ def generate_image_grid(
     *, scale_fn: Callable[[int, int, int], float] = builtin_scale, compute_dtype=ops.F16X3, verbose=True,
     reuse_winner: Optional[bool] = None, record_noises: bool = False, shard_candidates: bool = True,
     forced_selections: Optional[Sequence[int]] = None, candidate_chunk: Optional[int] = None, beam_search: bool = False,
-    row_seeds: Optional[Sequence[int]] = None, share_identical: bool = False,
+    row_seeds: Optional[Sequence[int]] = None, share_identical: bool = False, mcts_lockstep: bool = False,
 ):
     """Same positional/keyword surface as edm/main.py:47-55.  Keyword-only extras: `scale_fn` (the hash-derived step
     table, edm/main.py:776), `compute_dtype` (default ops.F16X3: split precision, the reference's fp32 selections at a third of the 16-bit
@@ -657,7 +822,15 @@ def generate_image_grid(
     run in lock-step as one batch (bulk.generate_seeds(search_batch=...)); eps-greedy / zero-order coins then differ from image to image:
     mode / scale are [N, B] instead of [N, 1] and the candidates come from ops.candidate_noise_rows (the rebuilt pivots always do, one launch
     of B rows); the result dict gains `row_seeds`;
-    not with MCTS, forced_selections, precomputed_noise or candidates sharded over ranks), `share_identical` (eps-greedy / zero-order and
+    not with MCTS (but see `mcts_lockstep`), forced_selections, precomputed_noise or candidates sharded over ranks), `mcts_lockstep`
+    (SamplingMethod.MCTS with row_seeds only; `_mcts_lockstep`: the trees of the seeds advance as one batch, aligned by simulation index, the
+    expansions of one index -- each search at the sigma step of its own leaf -- in ONE step with per-row scalars.  Search b is the one-image
+    call seed=row_seeds[b] made after numpy.random.seed(row_seeds[b]): its torch draws come from its own generator and its rollout child
+    draws from numpy.random.RandomState(row_seeds[b]); numpy's global generator is neither read nor advanced, which is a deviation from
+    the reference of this mode alone.  `selected` holds one [S] tensor per sigma step, `rewards` one
+    [S, group] tensor per (sigma step, group of simulations); the result dict gains `search_rows` (the denoiser rows of each search; `net_rows` is
+    their sum, padding rows are not counted), `mcts_ragged_launches` (per-row step launches) and `mcts_mixed_launches` (those that held rows
+    of at least two sigma steps)), `share_identical` (eps-greedy / zero-order and
     beam_search=True; not the reference's.  True: at the sigma steps `identical_steps` lists -- noise coefficient exactly 0, so every
     candidate is the unchanged state -- the identical rows go through the denoiser and the scorer once instead of K * N times per image (beam:
     one row per class of beam rows known to be equal).  Draws, selections (exact ties, index 0), the pivot steps and so `x`, `image` and
@@ -681,11 +854,22 @@ def generate_image_grid(
     # `net_rows` equals the reference's count (config 3: 8 995); the 16-bit throughput modes reuse the row (8 960 rows, same values).
     L.reuse_winner = (compute_dtype not in (torch.float32, ops.F16X3)) if reuse_winner is None else bool(reuse_winner)
     L.record_noises = bool(record_noises)
+    if mcts_lockstep:
+        if sampling_method != SamplingMethod.MCTS:
+            raise ValueError(f'mcts_lockstep=True: SamplingMethod.MCTS only, got {sampling_method.name}')
+        if row_seeds is None:
+            raise ValueError('mcts_lockstep=True: needs row_seeds (one seed per image: every search runs on its own torch and numpy streams)')
+        for name, given in (('forced_selections', forced_selections is not None), ('precomputed_noise', precomputed_noise is not None)):
+            if given:
+                raise ValueError(f'mcts_lockstep=True: {name} is not supported with per-image random streams')
+        if not shards.solo:
+            raise ValueError('mcts_lockstep=True: candidate sharding over more than one rank is not supported (shard_candidates=False: '
+                             'lock-step batches go with seed sharding)')
     if row_seeds is not None:
         row_seeds = [int(s) for s in row_seeds]
         if len(row_seeds) != latents.shape[0]:
             raise ValueError(f'row_seeds: need one seed per image, got {len(row_seeds)} seeds for {latents.shape[0]} images')
-        if sampling_method == SamplingMethod.MCTS:
+        if sampling_method == SamplingMethod.MCTS and not mcts_lockstep:
             raise ValueError('row_seeds: SamplingMethod.MCTS is not supported (its numpy child draw and its ragged trees are per search)')
         for name, given in (('forced_selections', forced_selections is not None), ('precomputed_noise', precomputed_noise is not None)):
             if given:
@@ -693,7 +877,7 @@ def generate_image_grid(
         if not shards.solo:
             raise ValueError('row_seeds: candidate sharding over more than one rank is not supported (shard_candidates=False: lock-step '
                              'batches go with seed sharding)')
-        L.src = _Source(row_seeds)
+        L.src, L.row_seeds = _Source(row_seeds), row_seeds
     if forced_selections is not None:
         if sampling_method not in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER) or latents.shape[0] != 1:
             raise ValueError('forced_selections: eps-greedy / zero-order search of one image only')
@@ -705,7 +889,7 @@ def generate_image_grid(
         if sampling_method not in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER) or int(candidate_chunk) < 1:
             raise ValueError('candidate_chunk: a positive candidate count, eps-greedy / zero-order search only')
         L.chunk = int(candidate_chunk)
-    method_fn = _METHODS[sampling_method]
+    method_fn = _mcts_lockstep if mcts_lockstep else _METHODS[sampling_method]
     if share_identical:
         if sampling_method not in (SamplingMethod.EPS_GREEDY, SamplingMethod.ZERO_ORDER) and not beam_search:
             raise ValueError(f'share_identical=True: eps-greedy / zero-order search or beam_search=True only, got {sampling_method.name}')
@@ -744,6 +928,8 @@ def generate_image_grid(
                collectives=shards.collectives, shared_steps=sorted(L.shared), best_noises={i: torch.stack(v) for i, v in L.best_noises.items()})
     if row_seeds is not None:
         res['row_seeds'] = row_seeds
+    if mcts_lockstep:
+        res.update(search_rows=L.search_rows, mcts_ragged_launches=L.mcts_ragged_launches, mcts_mixed_launches=L.mcts_mixed_launches)
     return res
 
 

@@ -64,7 +64,10 @@ enum dts_status { DTS_OK = 0, DTS_ERR_ARG = -1, DTS_ERR_LAUNCH = -2, DTS_ERR_UNS
                                      125: dts_candidate_noise_sd_rows, dts_ddim_candidates_groups (the SD backend's searches of several seeds in lock-step);
                                      125, domain widened without a signature change: dts_attention (16-bit types) and dts_cross_attention take
                                           head dims 40 / 80 / 160 at their true width (SD-1.x's heads without zero padding); dts_conv_args.up
-                                          takes -1 (3x3, stride 2: SD-1.x's downsamplers without space-to-depth; it was read as "upsample" before)) */
+                                          takes -1 (3x3, stride 2: SD-1.x's downsamplers without space-to-depth; it was read as "upsample" before);
+                                     125, entry points added without a change of an existing signature: dts_heun_xhat_rows, dts_heun_euler_rows,
+                                          dts_heun_correct_rows (K9 with the step's scalars per row: the MCTS expansions of several seeds' searches,
+                                          each at its own sigma step, in one launch); a binding that needs them finds them by name or refuses the library) */
 int dts_version(void);            /* == DTS_ABI_VERSION of the build; a binding must refuse any other value */
 const char* dts_last_error(void);
 /* Tuning knobs (measurement aid; a knob only selects between kernels / block orders / ring depths that give correct results -- the
@@ -391,6 +394,17 @@ int dts_heun_euler(const double* x_hat, const float* D, double t_hat, double t_n
 /* x_next = x_hat + (t_next - t_hat)*(0.5*d_cur + 0.5*(x_next - D2)/t_next)   (in place on x_next) */
 int dts_heun_correct(const double* x_hat, const float* D2, const double* d_cur, double t_hat, double t_next,
                      double* x_next, int64_t count, dts_stream s);
+/* The per-row forms of the three: noise_coef[nb], t_hat[n], t_next[n] are float64 DEVICE arrays, one entry per row of chw elements, read
+ * by the kernel and never by the host (the launches stay capturable).  Row i holds, bit for bit, what the scalar entry point computes for
+ * that row when launched with noise_coef[i], t_hat[i], t_next[i]: one body per op, the scalar entry is its broadcast case; a row with
+ * noise_coef[i] == 0.0 is its source row of x_cur unchanged.  t_hat[i] != 0 (euler) and t_next[i] != 0 (correct) are the CALLER's to
+ * check on its host copy before the upload: they cannot be refused here without a host read. */
+int dts_heun_xhat_rows(const double* x_cur, int xb, int bcast, const void* eps, int eps_f32, const double* noise_coef,
+                       double* x_hat, int nb, int chw, dts_stream s);
+int dts_heun_euler_rows(const double* x_hat, const float* D, const double* t_hat, const double* t_next,
+                        double* d_cur, double* x_next, int n, int chw, dts_stream s);
+int dts_heun_correct_rows(const double* x_hat, const float* D2, const double* d_cur, const double* t_hat, const double* t_next,
+                          double* x_next, int n, int chw, dts_stream s);
 
 /* ---- K9b: the general ODE step of the ablation sampler, fp64 state (edm/generate.py:156-174) -------
  * dx/dt = a(t) x - b(t) D(x / s(t); sigma(t)) with a = sigma'/sigma + s'/s and b = sigma' s / sigma.  Every scalar is evaluated once per

@@ -46,11 +46,16 @@ Additions (the reference hard-codes a checkpoint URL, main.py:157-158; there is 
     --seeds LIST --outdir DIR [--subdirs] [--class N]: bulk mode (flags of the reference's edm/generate.py): one search per
                   seed, <outdir>/<seed:06d>.png; with torch.distributed.run the SEEDS are split over the ranks (no collective)
     --search-batch S: bulk mode: the searches of S seeds run in lock-step as ONE batch (S x the rows per denoiser call; every image draws
-                  from its own seed's stream, so a seed's search does not depend on its companions; default 1; --method mcts runs per seed)
+                  from its own seed's stream, so a seed's search does not depend on its companions; default 1; --method mcts runs per seed
+                  unless --mcts-lockstep is given)
                   --backend sd: the same flags (--seeds --outdir [--subdirs] [--search-batch S]); seed s draws what `--seed s` draws, --method
                   rejection runs its N naive trajectories as N rows per seed, and `--decode-rows R` caps the rows per VAE decode and scorer
                   call (at [n,3,512,512] the decoder needs it for large S x N)
     python main.py --backend sd --scorer clip --method eps_greedy --N 4 --K 2 --unet hip --seeds 0-63 --search-batch 8 --decode-rows 16 --outdir out
+    --mcts-lockstep: EDM backend, bulk mode, --method mcts: the trees of the S seeds of a search batch advance as one batch, aligned by
+                  simulation index (generate_image_grid(mcts_lockstep=True)); seed s draws its rollout children from
+                  numpy.random.RandomState(s) instead of numpy's global generator
+    python main.py --backend edm --scorer imagenet --method mcts --N 4 --S 16 --seeds 0-15 --search-batch 16 --mcts-lockstep --outdir out
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`; the N candidates of every
 search iteration are sharded across the ranks (diffusion_tts_amd/parallel.py).
 """
@@ -298,6 +303,9 @@ def build_parser():
     parser.add_argument('--subdirs', action='store_true', help='bulk mode: one subdirectory per 1000 seeds')
     parser.add_argument('--search-batch', type=int, default=1,
                         help='bulk mode: run the searches of this many seeds in lock-step as one batch (default 1; mcts: one search per seed)')
+    parser.add_argument('--mcts-lockstep', dest='mcts_lockstep', action='store_true',
+                        help='EDM backend, bulk mode, --method mcts: run the MCTS searches of a search batch in lock-step as one batch '
+                             '(generate_image_grid(mcts_lockstep=True)); without it mcts runs one search per seed')
     parser.add_argument('--decode-rows', dest='decode_rows', type=int, default=None,
                         help='SD backend, bulk mode: at most this many rows per VAE decode and scorer call (default: all rows of a batch at once)')
     parser.add_argument('--class', dest='class_idx', type=int, default=None, help='bulk mode: class label (default: per-seed random)')
@@ -308,6 +316,11 @@ def check_bulk_args(args):
     """the bulk-mode flags that only go together: raised before anything is loaded"""
     if args.seeds is not None and args.search_batch < 1:
         raise ValueError(f'--search-batch: a positive number of seeds per lock-step batch, got {args.search_batch}')
+    if getattr(args, 'mcts_lockstep', False):
+        if args.backend != 'edm' or args.method != 'mcts':
+            raise ValueError('--mcts-lockstep is an EDM option of --method mcts (the SD backend\'s MCTS runs one search per seed)')
+        if args.seeds is None:
+            raise ValueError('--mcts-lockstep goes with --seeds (bulk mode: the searches of a --search-batch run as one batch)')
     if args.decode_rows is not None:
         if args.backend != 'sd':
             raise ValueError('--decode-rows is an SD option (the rows per VAE decode of a lock-step batch)')
@@ -365,6 +378,8 @@ def main(argv=None):
     extras = dict(beam_search=True) if beam_run else {}
     if getattr(args, 'share_identical', False):
         extras['share_identical'] = True
+    if getattr(args, 'mcts_lockstep', False):
+        extras['mcts_lockstep'] = True
     if args.seeds is not None:                                                        # bulk mode: seeds sharded over the ranks
         from diffusion_tts_amd.bulk import generate_seeds
         mm = {'naive': SamplingMethod.NAIVE, 'rejection': SamplingMethod.REJECTION_SAMPLING, 'beam': SamplingMethod.BEAM_SEARCH,
