@@ -280,7 +280,8 @@ extern "C" int dts_conv_in3(const float* x, const float* w, const float* bias, v
   DTS_CHECK_ARG(n > 0 && h > 0 && w_ > 0 && cout % 8 == 0 && cout <= 512, "dts_conv_in3: bad shape (cout=%d)", cout);
   hipStream_t st = to_stream(s);
   const long long nseg = (long long)n * h * (w_ / 16);
-  if (w_ % 16 == 0 && (cout == 192 || cout == 128 || cout == 64) && nseg < (1ll << 31) &&
+  // (nseg + the kernel's last `seg += gridDim.x * 4`, at most 2048 * 4, must stay an int)
+  if (w_ % 16 == 0 && (cout == 192 || cout == 128 || cout == 64) && nseg < (1ll << 31) - 2048 * 4 &&
       (bias == nullptr || ((uintptr_t)bias & 15) == 0)) {
     // up to 8 segments per wave (the 7*NT weight registers are loaded once per wave), fewer when that would leave CUs idle
     long long spw = nseg / 2048;

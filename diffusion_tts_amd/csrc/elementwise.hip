@@ -1075,7 +1075,8 @@ extern "C" int dts_candidate_noise_rows(const double* pivot, const double* g, co
 extern "C" int dts_candidate_noise_sd(const void* pivot, const void* u, const int32_t* mode, const float* scale, void* cand, int dtype, int n,
                                       int64_t count, dts_stream s) {
   DTS_CHECK_ARG(pivot && u && mode && scale && cand, "dts_candidate_noise_sd: null pointer");
-  DTS_CHECK_ARG(n > 0 && count > 0 && count < (1ll << 31), "dts_candidate_noise_sd: n=%d count=%lld", n, (long long)count);
+  // (the kernel walks a candidate with `int i += blockDim.x`: the step past the last element must stay an int)
+  DTS_CHECK_ARG(n > 0 && count > 0 && count <= (1ll << 31) - 256, "dts_candidate_noise_sd: n=%d count=%lld", n, (long long)count);
   ST;
   DTS_DISPATCH_DTYPE(dtype, {
     hipLaunchKernelGGL((candidate_noise_sd_kernel<T, false>), dim3(n), dim3(256), 0, st, (const T*)pivot, (const T*)u, mode, scale, (T*)cand,
@@ -1087,7 +1088,7 @@ extern "C" int dts_candidate_noise_sd(const void* pivot, const void* u, const in
 extern "C" int dts_candidate_noise_sd_rows(const void* pivot, const void* u, const int32_t* mode, const float* scale, void* cand, int dtype,
                                            int searches, int per, int64_t count, dts_stream s) {
   DTS_CHECK_ARG(pivot && u && mode && scale && cand, "dts_candidate_noise_sd_rows: null pointer");
-  DTS_CHECK_ARG(searches > 0 && per > 0 && (long long)searches * per < (1ll << 31) && count > 0 && count < (1ll << 31),
+  DTS_CHECK_ARG(searches > 0 && per > 0 && (long long)searches * per < (1ll << 31) && count > 0 && count <= (1ll << 31) - 256,
                 "dts_candidate_noise_sd_rows: searches=%d per=%d count=%lld", searches, per, (long long)count);
   ST;
   DTS_DISPATCH_DTYPE(dtype, {

@@ -468,6 +468,7 @@ extern "C" int dts_gn_coef(const void* x1, int c1, const void* x2, int c2, int d
   const int epv = dtype == DTS_F32 ? 4 : 8;
   DTS_CHECK_ARG(c1 % epv == 0 && c2 % epv == 0, "dts_gn_coef: channels (%d,%d) unsupported", c1, c2);
   DTS_CHECK_ARG(scale_shift == nullptr || ld_ss >= 2 * C, "dts_gn_coef: ld_ss=%d < 2*C=%d", ld_ss, 2 * C);
+  DTS_CHECK_ARG(n <= 65535, "dts_gn_coef: n too large for grid.y");
   const int splits = gn_splits(hw);
   hipStream_t st = to_stream(s);
   DTS_DISPATCH_DTYPE(dtype, {

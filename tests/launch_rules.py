@@ -147,3 +147,272 @@ JPEG_SCAN_SHAPES = {
 # (n, h, w) of every call of the stream tests
 JPEG_STREAM_CALLS = [(9, 16, 16), (9, 48, 80), (9, 80, 48), (9, 112, 112), (9, 176, 160), (9, 48, 688), (1, 512, 512), (9, 32, 32),
                      (1, 64, 64), (5, 64, 64), (64, 64, 64)]
+
+
+# ---- batches past 2^31 / 2^32 bytes per tensor (tests/large_rows.py, tests/test_gpu_large_rows.py) -------------------------------------------
+# Every case of tests/test_gpu_large_rows.py: a batch of n rows made of 7 distinct samples (large_rows.row_map), ONE launch.  Per tensor: the
+# shape of one sample, the element size, the bytes of the whole tensor, and which boundaries lie inside it -- '31': byte offset 2^31, '32':
+# byte offset 2^32, 'e31': element index 2^31 (the last two coincide for 16-bit types).  Written out as numbers; tests/test_large_rows_cpu.py
+# recomputes every one of them, holds the seeded map to the samples that straddle the boundaries and asks dts_conv_plan for the route of every
+# dts_conv2d case (`plan`: the fields that must come back, besides splits == 1).
+LargeTensor = collections.namedtuple('LargeTensor', 'name sample_shape itemsize bytes crosses')
+LargeCase = collections.namedtuple('LargeCase', 'name family n tensors spec')
+LARGE_CASES = collections.OrderedDict()
+
+
+def _large(name, family, n, tensors, spec):
+    assert name not in LARGE_CASES
+    LARGE_CASES[name] = LargeCase(name, family, n, tuple(LargeTensor(t[0], t[1], t[2], t[3], tuple(t[4].split())) for t in tensors), spec)
+
+
+_large('igemm_1x1_bf16', 'conv2d', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('bias_nc', (64,), 2, 16778112, ''),
+], {'mode': 'bf16', 'h': 16, 'w': 16, 'c1': 64, 'cout': 64, 'k': 1, 'up': 0, 'ep': 'bn', 'stats': False, 'gn': False, 'plan': {'kernel': 0, 'tile': 64}})
+_large('igemm_3x3_f16', 'conv2d', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('residual', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'mode': 'f16', 'h': 16, 'w': 16, 'c1': 64, 'cout': 64, 'k': 3, 'up': 0, 'ep': 'br', 'stats': False, 'gn': False, 'plan': {'kernel': 0, 'tile': 64}})
+_large('pp192_bf16', 'conv2d', 65535, [
+    ('x', (16, 16, 64), 2, 2147450880, ''),
+    ('out', (16, 16, 192), 2, 6442352640, '31 32 e31'),
+], {'mode': 'bf16', 'h': 16, 'w': 16, 'c1': 64, 'cout': 192, 'k': 3, 'up': 0, 'ep': 'b', 'stats': False, 'gn': False, 'plan': {'kernel': 6}})
+_large('pp192_res_stats_f16', 'conv2d', 65535, [
+    ('x', (16, 16, 64), 2, 2147450880, ''),
+    ('out', (16, 16, 192), 2, 6442352640, '31 32 e31'),
+    ('residual', (16, 16, 192), 2, 6442352640, '31 32 e31'),
+    ('stats', (4, 192, 2), 4, 402647040, ''),
+], {'mode': 'f16', 'h': 16, 'w': 16, 'c1': 64, 'cout': 192, 'k': 3, 'up': 0, 'ep': 'br', 'stats': True, 'gn': False, 'plan': {'kernel': 6, 'stats_in_kernel': 1}})
+_large('pp192_gn_bf16', 'conv2d', 65535, [
+    ('x', (16, 16, 64), 2, 2147450880, ''),
+    ('out', (16, 16, 192), 2, 6442352640, '31 32 e31'),
+    ('gn_coef', (64, 2), 4, 33553920, ''),
+], {'mode': 'bf16', 'h': 16, 'w': 16, 'c1': 64, 'cout': 192, 'k': 3, 'up': 0, 'ep': 'b', 'stats': False, 'gn': True, 'plan': {'kernel': 6, 'gn': 1}})
+_large('x3_3x3', 'conv2d', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (16, 16, 64), 4, 8590393344, '31 32 e31'),
+], {'mode': 'f16x3', 'h': 16, 'w': 16, 'c1': 32, 'cout': 64, 'k': 3, 'up': 0, 'ep': 'b', 'stats': False, 'gn': False, 'plan': {'kernel': 0, 'tile': 64}})
+_large('f32_3x3', 'conv2d', 131079, [
+    ('x', (16, 16, 32), 4, 4295196672, '31 32'),
+    ('out', (16, 16, 64), 4, 8590393344, '31 32 e31'),
+], {'mode': 'f32', 'h': 16, 'w': 16, 'c1': 32, 'cout': 64, 'k': 3, 'up': 0, 'ep': 'b', 'stats': False, 'gn': False, 'plan': {'kernel': 0, 'tile': 64}})
+_large('up1_bf16', 'conv2d', 131079, [
+    ('x', (8, 8, 128), 2, 2147598336, '31'),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'mode': 'bf16', 'h': 8, 'w': 8, 'c1': 128, 'cout': 64, 'k': 3, 'up': 1, 'ep': 'b', 'stats': False, 'gn': False, 'plan': {'kernel': 0, 'tile': 64}})
+_large('stride2_f16', 'conv2d', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (8, 8, 256), 2, 4295196672, '31 32 e31'),
+], {'mode': 'f16', 'h': 16, 'w': 16, 'c1': 64, 'cout': 256, 'k': 3, 'up': -1, 'ep': 'b', 'stats': False, 'gn': False, 'plan': {'kernel': 0, 'tile': 128}})
+_large('in3_mfma_bf16', 'conv_in3', 131079, [
+    ('x', (3, 16, 16), 4, 402674688, ''),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'mode': 'bf16', 'h': 16, 'w': 16, 'cout': 64, 'route': 'in3_mfma'})
+_large('in3_direct_f16', 'conv_in3', 139818, [
+    ('x', (3, 12, 20), 4, 402675840, ''),
+    ('out', (12, 20, 64), 2, 4295208960, '31 32 e31'),
+], {'mode': 'f16', 'h': 12, 'w': 20, 'cout': 64, 'route': 'in3_direct'})
+_large('out3_tiled_bf16', 'conv_out3', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (3, 16, 16), 4, 402674688, ''),
+], {'mode': 'bf16', 'h': 16, 'w': 16, 'c': 64, 'route': 'out3_tiled'})
+_large('out3_direct_f16', 'conv_out3', 139818, [
+    ('x', (12, 20, 64), 2, 4295208960, '31 32 e31'),
+    ('out', (3, 12, 20), 4, 402675840, ''),
+], {'mode': 'f16', 'h': 12, 'w': 20, 'c': 64, 'route': 'out3_direct'})
+_large('gn_bf16_c192', 'groupnorm', 43698, [
+    ('x', (16, 16, 192), 2, 4295688192, '31 32 e31'),
+    ('out', (16, 16, 192), 2, 4295688192, '31 32 e31'),
+    ('out_pool', (8, 8, 192), 2, 1073922048, ''),
+    ('scale_shift', (384,), 2, 33560064, ''),
+], {'mode': 'bf16', 'c': 192, 'h': 16, 'w': 16, 'routes': ('split', 'fused', 'strips'), 'apply': 'rows'})
+_large('gn_f32_c192', 'groupnorm', 21853, [
+    ('x', (16, 16, 192), 4, 4296474624, '31 32'),
+    ('out', (16, 16, 192), 4, 4296474624, '31 32'),
+    ('out_split', (16, 16, 384), 2, 4296474624, '31 32 e31'),
+    ('out_pool', (8, 8, 192), 4, 1074118656, ''),
+    ('scale_shift', (384,), 4, 33566208, ''),
+], {'mode': 'f32', 'c': 192, 'h': 16, 'w': 16, 'routes': ('split', 'fused', 'strips'), 'apply': 'rows'})
+_large('att16_d64_bf16', 'attention', 119845, [
+    ('qkv', (70, 384), 2, 6442867200, '31 32 e31'),
+    ('out', (70, 128), 2, 2147622400, '31'),
+], {'form': '64/QT1', 'mode': 'bf16', 't': 70, 'heads': 2, 'd': 64})
+_large('att_mask_d64_f16', 'attention', 119845, [
+    ('qkv', (70, 384), 2, 6442867200, '31 32 e31'),
+    ('out', (70, 128), 2, 2147622400, '31'),
+], {'form': '64/MASK', 'mode': 'f16', 't': 70, 'heads': 2, 'd': 64})
+_large('att_x3_d64', 'attention', 59926, [
+    ('qkv_image', (70, 768), 2, 6443243520, '31 32 e31'),
+    ('out', (70, 128), 4, 2147747840, '31'),
+], {'form': 'x3/QT1', 'mode': 'f32', 't': 70, 'heads': 2, 'd': 64})
+_large('att16_d40_bf16', 'attention', 191747, [
+    ('qkv', (70, 240), 2, 6442699200, '31 32 e31'),
+    ('out', (70, 80), 2, 2147566400, '31'),
+], {'form': 'native/40', 'mode': 'bf16', 't': 70, 'heads': 2, 'd': 40})
+_large('xattn_f16_kv_rows', 'rows', 239682, [
+    ('q', (70, 128), 2, 4295101440, '31 32 e31'),
+    ('out', (70, 128), 2, 4295101440, '31 32 e31'),
+    ('kv_rows', (1,), 4, 958728, ''),
+], {'op': 'xattn_f16_kv_rows', 'mode': 'f16', 'tq': 70, 'tk': 77, 'heads': 2, 'd': 64, 'contexts': 2})
+_large('layer_norm_bf16', 'rows', 131079, [
+    ('x', (8, 2048), 2, 4295196672, '31 32 e31'),
+    ('out', (8, 2048), 2, 4295196672, '31 32 e31'),
+], {'op': 'layer_norm_bf16', 'mode': 'bf16'})
+_large('geglu_f16', 'rows', 262151, [
+    ('x', (4, 4096), 2, 8590163968, '31 32 e31'),
+    ('out', (4, 2048), 2, 4295081984, '31 32 e31'),
+], {'op': 'geglu_f16', 'mode': 'f16'})
+_large('cast_from_f32_bf16', 'rows', 131079, [
+    ('x', (16384,), 4, 8590393344, '31 32 e31'),
+    ('out', (16384,), 2, 4295196672, '31 32 e31'),
+], {'op': 'cast_from_f32_bf16', 'mode': 'bf16'})
+_large('cast_to_f32_f16', 'rows', 131079, [
+    ('x', (16384,), 2, 4295196672, '31 32 e31'),
+    ('out', (16384,), 4, 8590393344, '31 32 e31'),
+], {'op': 'cast_to_f32_f16', 'mode': 'f16'})
+_large('quantize_u8_f32', 'rows', 174770, [
+    ('x', (3, 64, 64), 4, 8590295040, '31 32 e31'),
+    ('out', (3, 64, 64), 1, 2147573760, '31 e31'),
+], {'op': 'quantize_u8_f32'})
+_large('u8_to_unit_f32', 'rows', 174770, [
+    ('img', (3, 64, 64), 1, 2147573760, '31 e31'),
+    ('out', (3, 64, 64), 4, 8590295040, '31 32 e31'),
+], {'op': 'u8_to_unit_f32'})
+_large('brightness', 'rows', 349533, [
+    ('img', (3, 64, 64), 1, 4295061504, '31 32 e31'),
+    ('out', (1,), 4, 1398132, ''),
+], {'op': 'brightness'})
+_large('cfg_combine_bf16', 'rows', 131079, [
+    ('uncond', (16384,), 2, 4295196672, '31 32 e31'),
+    ('cond', (16384,), 2, 4295196672, '31 32 e31'),
+    ('out', (16384,), 2, 4295196672, '31 32 e31'),
+], {'op': 'cfg_combine_bf16', 'mode': 'bf16'})
+_large('nchw_to_nhwc_bf16', 'rows', 131079, [
+    ('x', (64, 16, 16), 4, 8590393344, '31 32 e31'),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'op': 'nchw_to_nhwc_bf16', 'mode': 'bf16'})
+_large('nchw_to_nhwc_pad_f16', 'rows', 32775, [
+    ('x', (4, 32, 32), 4, 536985600, ''),
+    ('out', (32, 32, 64), 2, 4295884800, '31 32 e31'),
+], {'op': 'nchw_to_nhwc_pad_f16', 'mode': 'f16'})
+_large('nhwc_to_nchw_bf16', 'rows', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (64, 16, 16), 4, 8590393344, '31 32 e31'),
+], {'op': 'nhwc_to_nchw_bf16', 'mode': 'bf16'})
+_large('split3_f16', 'rows', 131079, [
+    ('x', (16, 16, 32), 4, 4295196672, '31 32'),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'op': 'split3_f16'})
+_large('split2_f16', 'rows', 131079, [
+    ('x', (16, 16, 32), 4, 4295196672, '31 32'),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'op': 'split2_f16'})
+_large('resample2x_up_bf16', 'rows', 131079, [
+    ('x', (8, 8, 64), 2, 1073799168, ''),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'op': 'resample2x_up_bf16', 'mode': 'bf16'})
+_large('resample2x_down_f16', 'rows', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (8, 8, 64), 2, 1073799168, ''),
+], {'op': 'resample2x_down_f16', 'mode': 'f16'})
+_large('resample_fir_up_f16', 'rows', 131079, [
+    ('x', (8, 8, 64), 2, 1073799168, ''),
+    ('out', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+], {'op': 'resample_fir_up_f16', 'mode': 'f16'})
+_large('resample_fir_down_bf16', 'rows', 131079, [
+    ('x', (16, 16, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (8, 8, 64), 2, 1073799168, ''),
+], {'op': 'resample_fir_down_bf16', 'mode': 'bf16'})
+_large('edm_precond_in', 'rows', 174770, [
+    ('x', (3072,), 8, 4295147520, '31 32'),
+    ('sigma', (1,), 8, 1398160, ''),
+    ('xin', (3072,), 4, 2147573760, '31'),
+    ('coef', (4,), 4, 2796320, ''),
+], {'op': 'edm_precond_in'})
+_large('edm_precond_out', 'rows', 174770, [
+    ('x', (3072,), 8, 4295147520, '31 32'),
+    ('F', (3072,), 4, 2147573760, '31'),
+    ('coef', (4,), 4, 2796320, ''),
+    ('D', (3072,), 4, 2147573760, '31'),
+], {'op': 'edm_precond_out'})
+_large('heun_xhat_rows', 'rows', 174770, [
+    ('x_cur', (3072,), 8, 4295147520, '31 32'),
+    ('eps', (3072,), 4, 2147573760, '31'),
+    ('noise_coef', (1,), 8, 1398160, ''),
+    ('x_hat', (3072,), 8, 4295147520, '31 32'),
+], {'op': 'heun_xhat_rows'})
+_large('heun_euler_rows', 'rows', 174770, [
+    ('x_hat', (3072,), 8, 4295147520, '31 32'),
+    ('D', (3072,), 4, 2147573760, '31'),
+    ('d_cur', (3072,), 8, 4295147520, '31 32'),
+    ('x_next', (3072,), 8, 4295147520, '31 32'),
+], {'op': 'heun_euler_rows'})
+_large('heun_correct_rows', 'rows', 174770, [
+    ('x_hat', (3072,), 8, 4295147520, '31 32'),
+    ('D2', (3072,), 4, 2147573760, '31'),
+    ('d_cur', (3072,), 8, 4295147520, '31 32'),
+    ('x_next', (3072,), 8, 4295147520, '31 32'),
+], {'op': 'heun_correct_rows'})
+_large('candidate_noise_rows', 'rows', 174770, [
+    ('pivot', (3072,), 8, 4295147520, '31 32'),
+    ('g', (3072,), 8, 4295147520, '31 32'),
+    ('out', (3072,), 8, 4295147520, '31 32'),
+], {'op': 'candidate_noise_rows'})
+
+_large('up2_phase_x3', 'conv2d', 32775, [
+    ('x', (8, 8, 64), 2, 268492800, ''),
+    ('out', (16, 16, 128), 4, 4295884800, '31 32'),
+    ('residual', (16, 16, 128), 4, 4295884800, '31 32'),
+], {'mode': 'f16x3', 'h': 8, 'w': 8, 'c1': 32, 'cout': 128, 'k': 3, 'up': 2, 'ep': 'br', 'stats': False, 'gn': False, 'plan': {'kernel': 0, 'tile': 128, 'phases': 1}})
+_large('gelu_erf_bf16', 'rows', 131079, [
+    ('x', (16384,), 2, 4295196672, '31 32 e31'),
+    ('out', (16384,), 2, 4295196672, '31 32 e31'),
+], {'op': 'gelu_erf_bf16', 'mode': 'bf16', 'kind': 'gelu'})
+_large('quick_gelu_f16', 'rows', 131079, [
+    ('x', (16384,), 2, 4295196672, '31 32 e31'),
+    ('out', (16384,), 2, 4295196672, '31 32 e31'),
+], {'op': 'quick_gelu_f16', 'mode': 'f16', 'kind': 'quick_gelu'})
+_large('ddim_candidates_groups_bf16', 'rows', 65543, [
+    ('x', (16384,), 2, 2147713024, '31'),
+    ('e', (16384,), 2, 2147713024, '31'),
+    ('z', (2, 16384), 2, 4295426048, '31 32 e31'),
+    ('prev', (2, 16384), 2, 4295426048, '31 32 e31'),
+    ('x0', (16384,), 2, 2147713024, '31'),
+], {'op': 'ddim_candidates_groups_bf16', 'mode': 'bf16', 'ncand': 2})
+_large('ddim_candidates_f16', 'rows', 131079, [
+    ('x', (16384,), 2, 4295196672, '31 32 e31'),
+    ('e', (16384,), 2, 4295196672, '31 32 e31'),
+    ('prev', (16384,), 2, 4295196672, '31 32 e31'),
+], {'op': 'ddim_candidates_f16', 'mode': 'f16'})
+_large('candidate_noise_sd_rows_f16', 'rows', 131079, [
+    ('pivot', (4, 64, 64), 2, 4295196672, '31 32 e31'),
+    ('u', (4, 64, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (4, 64, 64), 2, 4295196672, '31 32 e31'),
+    ('mode', (1,), 4, 524316, ''),
+    ('scale', (3,), 4, 1572948, ''),
+], {'op': 'candidate_noise_sd_rows_f16', 'mode': 'f16'})
+_large('candidate_noise_sd_f16', 'rows', 131079, [
+    ('u', (4, 64, 64), 2, 4295196672, '31 32 e31'),
+    ('out', (4, 64, 64), 2, 4295196672, '31 32 e31'),
+    ('mode', (1,), 4, 524316, ''),
+    ('scale', (3,), 4, 1572948, ''),
+], {'op': 'candidate_noise_sd_f16', 'mode': 'f16'})
+_large('jpeg_size_cap', 'rows', 43690, [
+    ('img', (3, 128, 128), 1, 2147450880, ''),
+    ('sizes', (1,), 4, 174760, ''),
+    ('ws_coef', (384, 64), 2, 2147450880, ''),
+    ('ws_bitbuf', (384, 256), 1, 4294901760, '31 e31'),
+], {'op': 'jpeg_size_cap', 'h': 128, 'w': 128, 'cap_blocks': 16777216})
+_large('group_rows_cap', 'rows', 1024, [
+    ('rows', (1055796,), 4, 4324540416, '31 32'),
+    ('slot', (1,), 4, 4096, ''),
+], {'op': 'group_rows_cap', 'cap_rows': 1024})
+
+
+# The switch of dts_conv2d at the 32-bit limits, from both sides (64 -> 192 channels, 3x3, 16x16 samples, bf16): the ping-pong kernel's
+# buffer descriptors carry 32-bit byte counts, so conv_pp_eligible hands the layer to the implicit GEMM once an operand reaches 2^31 bytes
+# (n = 65535: the input is 32 KiB short of it), and conv_plan refuses 2^30 pixels (n = 2^22 samples of 256).
+LARGE_CONV_SWITCH = dict(c1=64, cout=192, k=3, h=16, w=16, mode='bf16', last_pp=(65535, 6), first_igemm=(65536, 0),
+                         last_accepted=(1 << 22) - 1, first_refused=1 << 22, refusal='too many pixels')
